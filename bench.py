@@ -34,6 +34,10 @@ Besides `value` the line carries
   rccl        (N>1) what RCCL itself reports for the communicator, the exchange time per frame (HIP events around
               lpt_renderer_exchange on rank 0), per-rank ray counts, and whether rank 0's presented frame was complete;
   cpu_baseline  the oracle ("port") on the host cores, bounded sample.
+
+`--dump-outputs DIR` writes the presented frame of the last timed step (rank 0's read_radiance(): H x W x RGBA float32) to
+DIR/radiance.npy.  The inputs depend on the arguments alone (seeded scene, fixed camera, a renderer's seed counter counts its
+frames), so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -47,7 +51,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # read by the HIP runtime at initialisation: one hardware queue per stream
 os.environ.setdefault("GLOO_SOCKET_IFNAME", "lo")  # single-node control plane; the box's hostname may not resolve
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: what RCCL needs on this pool
 
@@ -104,6 +107,8 @@ def parse_args(argv=None):
                     "so it needs LPT_RCCL_LIBRARY = the test stand-in (tests/tools/fake_rccl.c)")
     ap.add_argument("--spawn-dry-run", action="store_true", help="start the ranks and rendezvous over gloo only: no GPU is touched (CPU test of the launcher)")
     ap.add_argument("--spawn-timeout", type=float, default=1500.0, help="seconds the self-started ranks may take")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write the presented frame of the last one (read_radiance(), float32) "
+                    "to DIR/radiance.npy; a frame over 64 MB keeps a fixed, seeded sample of its pixels")
     return ap.parse_args(argv)
 
 
@@ -349,6 +354,24 @@ def roofline_fractions(achieved_gbps, traffic_bytes, avg_launch_ms):
     frac = achieved_gbps / HBM_PEAK_GBS
     frac_fabric = (traffic_bytes / (avg_launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (traffic_bytes and avg_launch_ms > 0) else None
     return frac, frac_fabric
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_radiance(out_dir, img, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the frame as out_dir/radiance.npy in float32.  A frame of more than `limit` bytes keeps a sample of its pixels that depends
+    on the frame size alone (seeded, in pixel order): an (n, channels) array, so that runs at the same size still compare pixel for pixel."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    if img.nbytes > limit:
+        px = img.reshape(-1, img.shape[-1])
+        keep = np.random.default_rng(0).choice(px.shape[0], (limit - 4096) // px[0].nbytes, replace=False)   # (room for the .npy header)
+        img = px[np.sort(keep)]
+    path = os.path.join(out_dir, "radiance.npy")
+    np.save(path, img)
+    return path
 
 
 # ------------------------------------------------------------------------------------------------ one rank
@@ -673,6 +696,11 @@ def run(args):
             frame_ms.append((time.perf_counter() - tf) * 1e3)
     fence([r])
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        if rank == 0:
+            dump_radiance(args.dump_outputs, last["img"])
+        if use_dist:
+            dist.barrier()   # the host-side gather's frame is shared memory: no rank renders into it before rank 0 has written it out
     sub1 = r.submission_stats()
     slowest_frame = max(range(len(frame_ms)), key=lambda i: frame_ms[i]) if frame_ms else -1
     frame_ms.sort()

@@ -522,8 +522,7 @@ extern "C" {
 int lpt_device_create(int hip_ordinal, lpt_device **out) {
     if (!out) return fail(LPT_ERR_INVALID_ARG, "lpt_device_create: null out");
     // A renderer spreads its work over several HIP streams (wavefront lanes, several renderers in flight).  The ROCm runtime
-    // maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a queue serialise: a host that
-    // keeps more than two frames in flight sets GPU_MAX_HW_QUEUES=8 in its environment BEFORE its first HIP call
+    // maps streams onto a fixed number of hardware queues (the machine's setting) and streams that share a queue serialise
     // (INTEGRATION.md §8).  The library does not touch the process environment.
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);

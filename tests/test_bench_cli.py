@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_help_and_contract_flags():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
-    for flag in ("--gpus", "--steps", "--warmup", "--exchange", "--pipeline", "--emulate-shard", "--spawn-dry-run", "--gltf", "--probe", "--camera"):
+    for flag in ("--gpus", "--steps", "--warmup", "--exchange", "--pipeline", "--emulate-shard", "--spawn-dry-run", "--gltf", "--probe", "--camera", "--dump-outputs"):
         assert flag in p.stdout
     sys.path.insert(0, ROOT)
     import bench
@@ -66,6 +66,28 @@ def test_bench_fails_loudly_without_a_gpu():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0"], capture_output=True, text=True, timeout=600)
     assert p.returncode != 0
     assert not any(l.startswith("{") for l in p.stdout.splitlines())
+
+
+def test_dump_outputs_writes_the_frame_in_float32_and_samples_a_large_one(tmp_path):
+    """--dump-outputs DIR: the presented frame as DIR/radiance.npy in float32; a frame over the 64 MB cap keeps a sample of its pixels that depends on the
+    frame size alone, so that two runs (two builds) at the same arguments compare pixel for pixel"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args(["--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path) and bench.parse_args([]).dump_outputs is None
+    img = np.random.default_rng(1).random((27, 48, 4)).astype(np.float32)
+    path = bench.dump_radiance(str(tmp_path / "small"), img)
+    got = np.load(path)
+    assert path == str(tmp_path / "small" / "radiance.npy") and got.dtype == np.float32 and np.array_equal(got, img)
+    big = np.random.default_rng(2).random((64, 100, 4)).astype(np.float32)
+    limit = 20000
+    a = np.load(bench.dump_radiance(str(tmp_path / "a"), big, limit=limit))
+    b = np.load(bench.dump_radiance(str(tmp_path / "b"), big + 1.0, limit=limit))
+    assert os.path.getsize(tmp_path / "a" / "radiance.npy") <= limit and a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == 4
+    rows = big.reshape(-1, 4)
+    idx = [int(np.flatnonzero((rows == p).all(1))[0]) for p in a]
+    assert idx == sorted(set(idx)) and np.array_equal(b, rows[idx] + 1.0)     # distinct pixels in pixel order, the same ones for every frame of that size
+    assert bench.DUMP_LIMIT_BYTES <= 64 * 10 ** 6 and 1920 * 1080 * 16 < bench.DUMP_LIMIT_BYTES    # the bench frame travels whole
 
 
 def test_metric_string_is_baseline_jsons():

@@ -58,6 +58,19 @@ def _one():
     return _ONE["j"]
 
 
+def test_dump_outputs_gives_the_same_frame_for_the_same_arguments_at_any_rank_count(fake_rccl, tmp_path):
+    """`--dump-outputs DIR`: rank 0's presented frame of the last timed step as DIR/radiance.npy (float32, 270 x 480 x RGBA).  Same arguments, same
+    frame: a second run, here with two ranks exchanging tiles (equal shares), writes the same pixels bit for bit"""
+    import numpy as np
+    one = _bench(["--no-extras", "--dump-outputs", str(tmp_path / "one")])
+    img = np.load(tmp_path / "one" / "radiance.npy")
+    assert img.dtype == np.float32 and img.shape == (270, 480, 4) and one["steps"] == 1 and one["ms_per_step"] > 0
+    assert np.all(img[..., 3] == 1.0) and np.all(np.isfinite(img)) and float(img[..., :3].mean()) > 0.0
+    _bench(["--gpus", "2", "--oversubscribe", "--root-weight", "8", "--exchange", "gather", "--no-extras", "--dump-outputs", str(tmp_path / "two")] + NOXF,
+           {"LPT_RCCL_LIBRARY": fake_rccl})
+    assert np.array_equal(np.load(tmp_path / "two" / "radiance.npy"), img)
+
+
 def test_self_started_ranks_exchange_the_single_gpu_frame(fake_rccl):
     one = _one()
     assert one["n_gpus"] == 1 and one["config"]["frame_complete"] is True
