@@ -534,7 +534,11 @@ __device__ __forceinline__ bool ray_step_any(const DScene &sc, RayState &rs, uin
 // every size measured.  Round 6: within the step the fetched triangle is tested BEFORE the node's children (its rows are dead by
 // then: 72 VGPRs where the other order needed 78-79, and the children are tested against the hit it may have found).
 // The host picks the variant per wavefront (device.hip: pipe_rays); the default is this one.
-template <bool STATS>
+// PLACE (k_trace's per-lane launches): rs.best.prim holds the winning triangle's leaf PLACE, not its primitive id — the id (leaf_prim) is only needed for the exact-tie rule
+// and for the hit record, and loading it right behind an accepted Woop test put a second, dependent memory round trip into every step in which a lane of the wave found
+// a hit (vmcnt retires in order: the wait for it drained the node rows as well).  The tie branch loads both places' ids; k_trace resolves the place when the ray is
+// done.  A shadow ray only needs "something was hit": its place is never resolved.
+template <bool STATS, bool PLACE = false>
 __device__ __forceinline__ bool ray_step_pipe(const DScene &sc, RayState &rs, uint2 *stack, const bool ANY, uint32_t &n_nodes, uint32_t &n_tris, const uint8_t *lut = nullptr) {
     const bool node_work = (rs.ng.y & 0xFF000000u) != 0u || rs.sp != 0;
     const bool tri_work = (rs.tg.y != 0u);      // rs.tg2 is only ever occupied while rs.tg is
@@ -561,8 +565,15 @@ __device__ __forceinline__ bool ray_step_pipe(const DScene &sc, RayState &rs, ui
     if (tri_work) {
         float t, u, v;
         if (ray_triangle(r0, r1, r2, rs.o, rs.d, rs.best.t, t, u, v)) {
-            const uint32_t prim = sc.leaf_prim[ti];
-            if (t < rs.best.t || prim < rs.best.prim) { rs.best.t = t; rs.best.u = u; rs.best.v = v; rs.best.prim = prim; }
+            if (PLACE) {
+                // the rule of the other branch, `t < best.t || prim < best.prim`: t <= best.t here, and no hit yet (~0) loses to any id
+                bool take = t < rs.best.t || rs.best.prim == 0xFFFFFFFFu;
+                if (!take) take = sc.leaf_prim[ti] < sc.leaf_prim[rs.best.prim];   // an exact tie with an earlier hit (rare)
+                if (take) { rs.best.t = t; rs.best.u = u; rs.best.v = v; rs.best.prim = ti; }
+            } else {
+                const uint32_t prim = sc.leaf_prim[ti];
+                if (t < rs.best.t || prim < rs.best.prim) { rs.best.t = t; rs.best.u = u; rs.best.v = v; rs.best.prim = prim; }
+            }
             if (STATS && ANY) rs.best.v = __uint_as_float(ti);   // the occluder's leaf slot, for the occluder-cache probe (an any-hit ray's v is not read)
             if (ANY) return true;
         }
@@ -632,22 +643,30 @@ __device__ __forceinline__ void puller_pull(ChunkPuller &p) {
 }
 
 // SPEC §8: rectangular emitters (front face only, strictly closer than any triangle)
+__device__ __forceinline__ void intersect_light(const float4 *L, const uint32_t l, f3 o, f3 d, Hit &best) {
+    const float4 n4 = L[0], t4 = L[1], b4 = L[2], o4 = L[3];
+    const f3 nl = mk3(n4.x, n4.y, n4.z);
+    float dn = dot(d, nl);
+    if (!(dn < 0.0f)) return;
+    const f3 ctr = mk3(o4.x, o4.y, o4.z);
+    float t = dot(ctr - o, nl) / dn;
+    if (!(t > 0.0f && t < best.t)) return;
+    f3 p = mk3(fmaf(d.x, t, o.x), fmaf(d.y, t, o.y), fmaf(d.z, t, o.z));
+    f3 r = p - ctr;
+    float a = dot(r, mk3(t4.x, t4.y, t4.z));
+    float b = dot(r, mk3(b4.x, b4.y, b4.z));
+    if (fabsf(a) <= t4.w && fabsf(b) <= b4.w) { best.t = t; best.u = a; best.v = b; best.prim = LPT_LIGHT_BIT | l; }
+}
 __device__ __forceinline__ void intersect_lights(const DScene &sc, f3 o, f3 d, Hit &best) {
-    for (uint32_t l = 0; l < sc.n_lights; ++l) {
-        const float4 *L = reinterpret_cast<const float4 *>(sc.lights + l);
-        const float4 n4 = L[0], t4 = L[1], b4 = L[2], o4 = L[3];
-        const f3 nl = mk3(n4.x, n4.y, n4.z);
-        float dn = dot(d, nl);
-        if (!(dn < 0.0f)) continue;
-        const f3 ctr = mk3(o4.x, o4.y, o4.z);
-        float t = dot(ctr - o, nl) / dn;
-        if (!(t > 0.0f && t < best.t)) continue;
-        f3 p = mk3(fmaf(d.x, t, o.x), fmaf(d.y, t, o.y), fmaf(d.z, t, o.z));
-        f3 r = p - ctr;
-        float a = dot(r, mk3(t4.x, t4.y, t4.z));
-        float b = dot(r, mk3(b4.x, b4.y, b4.z));
-        if (fabsf(a) <= t4.w && fabsf(b) <= b4.w) { best.t = t; best.u = a; best.v = b; best.prim = LPT_LIGHT_BIT | l; }
-    }
+    for (uint32_t l = 0; l < sc.n_lights; ++l) intersect_light(reinterpret_cast<const float4 *>(sc.lights + l), l, o, d, best);
+}
+// the same with the first kLightTable records from a copy in LDS (k_trace's per-lane throughput variant: the records are the same for every lane, and read from memory
+// they cost two dependent round trips per light in every refill that finishes a closest-hit ray); the lights beyond, if any, as above — same order, same result
+constexpr uint32_t kLightTable = 4u;   // 64 B each
+__device__ __forceinline__ void intersect_lights_lds(const DScene &sc, const float4 *table, f3 o, f3 d, Hit &best) {
+    const uint32_t n = sc.n_lights;
+    for (uint32_t l = 0; l < min(n, kLightTable); ++l) intersect_light(table + 4u * l, l, o, d, best);
+    for (uint32_t l = kLightTable; l < n; ++l) intersect_light(reinterpret_cast<const float4 *>(sc.lights + l), l, o, d, best);
 }
 
 // dynamic LDS: sc.stack_entries * kTraceBlock uint2 (16-byte aligned, Guideline 17)
@@ -925,6 +944,15 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(TAI
         __syncthreads();
         lut = s_perm;
     }
+    // the per-lane throughput variant (PIPE without the cooperative tail: the bench's launches): the hit's primitive id looked up when the ray is done (ray_step_pipe),
+    // the emitter records read from LDS (intersect_lights_lds)
+    constexpr bool PLACE = PIPE && !TAIL;
+    __shared__ float4 s_lights[PLACE ? 4u * kLightTable : 1u];
+    if (PLACE) {
+        const float4 *src = reinterpret_cast<const float4 *>(sc.lights);
+        for (uint32_t e = threadIdx.x; e < 4u * min(sc.n_lights, kLightTable); e += kTraceBlock) s_lights[e] = src[e];
+        __syncthreads();
+    }
     RayState rs;
     bool active = false, finished = false, shadow = false;
     uint32_t ray = 0;
@@ -968,7 +996,9 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(TAI
                         Lsum[slot] = L;
                     }
                 } else {
-                    intersect_lights(sc, rs.o, rs.d, rs.best);
+                    if (PLACE && rs.best.prim != 0xFFFFFFFFu) rs.best.prim = sc.leaf_prim[rs.best.prim];   // the hit's place -> its primitive id (ray_step_pipe<.., PLACE>)
+                    if (PLACE) intersect_lights_lds(sc, s_lights, rs.o, rs.d, rs.best);
+                    else intersect_lights(sc, rs.o, rs.d, rs.best);
                     st_nt(hits + ray, make_float4(rs.best.t, rs.best.u, rs.best.v, __uint_as_float(rs.best.prim)));
                 }
                 finished = false;
@@ -1005,7 +1035,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(TAI
             w_node += (uint32_t)__popcll(__ballot(PIPE ? active && (rs.tg2.y == 0u) && ((rs.ng.y & 0xFF000000u) != 0u || rs.sp != 0) : active && (rs.tg.y == 0u)));
         }
         if ((STATS || budget) && active) my_steps++;
-        if (active && (PIPE ? ray_step_pipe<STATS>(sc, rs, stack, shadow, dn, dt, lut) : ray_step_any<STATS>(sc, rs, stack, shadow, dn, dt, lut))) {
+        if (active && (PIPE ? ray_step_pipe<STATS, PLACE>(sc, rs, stack, shadow, dn, dt, lut) : ray_step_any<STATS>(sc, rs, stack, shadow, dn, dt, lut))) {
             active = false;
             finished = true;
         }
