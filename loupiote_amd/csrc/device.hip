@@ -17,9 +17,11 @@
 #include <algorithm>
 #include <cmath>
 #include <map>
+#include <memory>
 #include <cstdlib>
 #include <mutex>
 #include <new>
+#include <numeric>
 
 #include "common.h"
 #include "kernels.h"
@@ -30,6 +32,7 @@
 using namespace lpt;
 using namespace lptd;
 
+#define TRY(expr) do { const int st__ = (expr); if (st__ != LPT_OK) return st__; } while (0)
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t e__ = (expr);                                                                   \
@@ -111,28 +114,44 @@ static const Rccl *rccl() {
         if (r__ != ncclSuccess) return fail(LPT_ERR_RCCL, "%s failed: %s", #expr, rccl() ? rccl()->GetErrorString(r__) : "?"); \
     } while (0)
 
+// device memory, freed when its handle goes (hipFree waits for the device)
+struct HipFree { void operator()(void *p) const { hipFree(p); } };
+using DevMem = std::unique_ptr<void, HipFree>;
+template <typename T> static inline T *as(const DevMem &m) { return (T *)m.get(); }
+
+// The wide BVH on the device: what a build makes and a rebuild swaps in whole.  Nodes are stored breadth first: level l = [level_start[l], level_start[l+1]).
+struct DevTree {
+    DevMem nodes, woop, leaf_prim;
+    DevMem node_lo, node_hi;   // per-node world box (refits)
+    std::vector<uint32_t> level_start;
+    uint32_t n_nodes = 0, max_depth = 0;
+    float build_ms = 0.f;
+};
+
+// paired textures (kernels.h DScene::pair_texels): (albedo image, mra image) -> pair index, for the materials whose two textures have one size; the shading
+// records of such materials carry kPairedBit | pair index instead of two image ids
+struct TexturePairs {
+    std::map<std::pair<uint32_t, uint32_t>, uint32_t> map;
+    std::vector<DImage> descs;   // a paired material's record carries its pair's offset and size directly
+    // which images the tiled atlas holds on their own: an image that only ever appears as half of a pair is not stored a second
+    // time (scene.rs:172-184 keeps each image once)
+    std::vector<uint8_t> image_resident;
+};
+
 struct lpt_scene_gpu {
     lpt_device *dev = nullptr;
     DScene d{};
     float max_abs = 0.f;            // the scene's largest |coordinate|: d.pad_abs = kScenePad x this (host build: Accel::max_abs; GPU build: the bounds pass; refit: the root box)
-    void *nodes = nullptr, *woop = nullptr, *leaf_prim = nullptr, *tri_verts = nullptr;
-    void *materials = nullptr, *lights = nullptr, *texels = nullptr, *images = nullptr, *srgb_lut = nullptr;
-    // paired textures (kernels.h DScene::pair_texels): (albedo image, mra image) -> pair index, for the materials whose two
-    // textures have one size; the shading records of such materials carry kPairedBit | pair index instead of two image ids
-    void *pair_texels = nullptr, *pair_images = nullptr;
-    std::map<std::pair<uint32_t, uint32_t>, uint32_t> pair_map;
-    std::vector<DImage> pair_descs;   // host copy: a paired material's record carries its pair's offset and size directly
-    // which images the tiled atlas holds on their own: an image that only ever appears as half of a pair is not stored a second
-    // time (scene.rs:172-184 keeps each image once)
-    std::vector<uint8_t> image_resident;
+    DevTree tree;
+    DevMem tri_verts, materials, lights, texels, images, srgb_lut, pair_texels, pair_images;
+    TexturePairs pairs;
     lpt_accel_stats stats{};
     // refit bookkeeping (lpt_scene_gpu_update_instances)
-    void *node_lo = nullptr, *node_hi = nullptr;  // per-node world box
-    void *obj_verts = nullptr, *obj_indices = nullptr, *bad_flag = nullptr;  // object-space meshes for device-side re-baking
-    void *arena = nullptr;                                                    // scratch of the GPU builder, kept for rebuilds
+    DevMem obj_verts, obj_indices, bad_flag;   // object-space meshes for device-side re-baking
+    DevMem arena;                              // scratch of the GPU builder, kept for rebuilds
     size_t arena_bytes = 0;
-    std::vector<uint32_t> inst_first, inst_count, level_start;
-    std::vector<lpt_instance> instances;                                // as baked
+    std::vector<uint32_t> inst_first, inst_count;
+    std::vector<lpt_instance> instances;       // as baked
     size_t n_entries = 0, n_vertices = 0, n_indices = 0;
 };
 
@@ -319,30 +338,33 @@ static int check_device_error(lpt_renderer *r) {
 }
 static inline size_t stack_bytes(const DScene &sc) { return (size_t)sc.stack_entries * kTraceBlock * sizeof(uint2); }
 
-template <typename T>
-static int upload(void **dst, const T *src, size_t count, hipStream_t s) {
-    const size_t bytes = sizeof(T) * (count ? count : 1);
-    HIP_TRY(hipMalloc(dst, bytes));
-    if (count) HIP_TRY(hipMemcpyAsync(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice, s));
+static int dev_alloc(DevMem &m, size_t bytes) {
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, bytes));
+    m.reset(p);
     return LPT_OK;
 }
 
-// ---------------------------------------------------------------------------- GPU builder (build_kernels.h)
-// Fills sg->nodes / woop / leaf_prim / node_lo / node_hi / level_start from the baked triangles that are
-// already on the device (sg->d.tri_verts).  `woop_prim` = the Woop maps in prim order (host, SPEC §6).
-// `host_woop`: the Woop maps in prim order on the host (upload path) or nullptr when `dev_woop` (device, prim order) is given.
+template <typename T>
+static int upload(DevMem &dst, const std::vector<T> &src, hipStream_t s) {
+    TRY(dev_alloc(dst, sizeof(T) * std::max<size_t>(src.size(), 1u)));
+    if (!src.empty()) HIP_TRY(hipMemcpyAsync(dst.get(), src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice, s));
+    return LPT_OK;
+}
+
+// ---------------------------------------------------------------------------- GPU builder (build_kernels.h) and refit
 // Scene bounds from the baked triangles on the device (blocking), and what follows from them for every kernel that pads a triangle or writes a node: the scene-wide part
 // of the triangle padding (bvh.cpp padded_box; it never shrinks — a pad a little too wide costs nothing) and the scene grid of the node origins (common.h scene_grid, of the
 // bounds widened by that padding).  Before a build and before every refit.
 static int scene_bounds_and_grid(lpt_scene_gpu *sg, uint32_t n, hipStream_t s, float blo[3], float bhi[3], bool keep_pad) {
-    int *db = nullptr, hb[6];
+    int hb[6];
     const int init[6] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, (int)0x80000000, (int)0x80000000, (int)0x80000000};
-    HIP_TRY(hipMalloc(&db, sizeof init));
-    HIP_TRY(hipMemcpyAsync(db, init, sizeof init, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_lbvh_bounds, dim3(std::min<uint32_t>(div_up(n, 256u), 1024u)), dim3(256), 0, s, sg->d, n, db);
-    HIP_TRY(hipMemcpyAsync(hb, db, sizeof hb, hipMemcpyDeviceToHost, s));
+    DevMem db;
+    TRY(dev_alloc(db, sizeof init));
+    HIP_TRY(hipMemcpyAsync(db.get(), init, sizeof init, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_lbvh_bounds, dim3(std::min<uint32_t>(div_up(n, 256u), 1024u)), dim3(256), 0, s, sg->d, n, as<int>(db));
+    HIP_TRY(hipMemcpyAsync(hb, db.get(), sizeof hb, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    hipFree(db);
     for (int a = 0; a < 6; ++a) { const int o = hb[a] >= 0 ? hb[a] : hb[a] ^ 0x7FFFFFFF; float f; memcpy(&f, &o, 4); (a < 3 ? blo[a] : bhi[a - 3]) = f; }
     float now_abs = 0.0f;
     for (int a = 0; a < 3; ++a) now_abs = std::max(now_abs, std::max(fabsf(blo[a]), fabsf(bhi[a])));
@@ -360,160 +382,331 @@ static int scene_bounds_and_grid(lpt_scene_gpu *sg, uint32_t n, hipStream_t s, f
     return LPT_OK;
 }
 
-static int build_lbvh(lpt_scene_gpu *sg, uint32_t n, const WoopTri *host_woop, const float4 *dev_woop, hipStream_t s) {
+// the boxes of every node of `t`, from the bottom level up, over the triangles and grid of `d`
+static void refit_levels(const DScene &d, const DevTree &t, hipStream_t s) {
+    for (size_t l = t.level_start.size() - 1; l-- > 0;) {
+        const uint32_t a = t.level_start[l], b = t.level_start[l + 1];
+        if (b > a) hipLaunchKernelGGL(k_refit_level, dim3(div_up(b - a, 64u)), dim3(64), 0, s, d, as<uint4>(t.nodes), as<float4>(t.node_lo), as<float4>(t.node_hi), a, b);
+    }
+}
+
+// the prim-ordered Woop maps of triangles [first, first + count) to their places in `t` (a split triangle has several)
+static void scatter_woop(const DevTree &t, const void *woop_prim, uint32_t first, uint32_t count, hipStream_t s) {
+    const uint32_t n_places = kNodeTris * t.n_nodes;
+    hipLaunchKernelGGL(k_lbvh_scatter_woop, dim3(div_up(n_places, 256u)), dim3(256), 0, s, (const float4 *)woop_prim, as<float4>(t.woop), as<const uint32_t>(t.leaf_prim),
+                       n_places, first, count);
+}
+
+// A new tree over the n baked triangles already on the device (sg->d.tri_verts); `woop_prim` = their Woop maps in prim order (device).  The tree goes to
+// `out` only when the build succeeds.  Of sg it sets the padding and grid of the new scene (scene_bounds_and_grid, max_abs reset) and reuses the scratch arena.
+static int build_lbvh(lpt_scene_gpu *sg, uint32_t n, const void *woop_prim, hipStream_t s, DevTree &out) {
     const auto t0 = std::chrono::steady_clock::now();
     float blo[3], bhi[3];
-    { const int bst = scene_bounds_and_grid(sg, n, s, blo, bhi, false); if (bst != LPT_OK) return bst; }
+    TRY(scene_bounds_and_grid(sg, n, s, blo, bhi, false));
     float binv[3];
     for (int a = 0; a < 3; ++a) binv[a] = bhi[a] > blo[a] ? 1.0f / (bhi[a] - blo[a]) : 0.0f;
 
-    // scratch: one arena per scene, kept for the next rebuild (about 400 B per triangle); a bump allocator over it
+    // scratch: one arena per scene, kept for the next rebuild (about 400 B per triangle); every piece is carved from it before the first launch
     size_t sort_bytes = 0, scan_bytes = 0;
     hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (int)n, 0, 30, s);
     hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (int)n, s);
-    const size_t need = (size_t)n * 400u + std::max(sort_bytes, scan_bytes) + 64u * 256u;
+    const size_t cub_cap = std::max(sort_bytes, scan_bytes);
+    const size_t need = (size_t)n * 400u + cub_cap + 64u * 256u;
     if (sg->arena_bytes < need) {
-        if (sg->arena) hipFree(sg->arena);
-        sg->arena = nullptr; sg->arena_bytes = 0;
-        if (hipMalloc(&sg->arena, need) != hipSuccess) return fail(LPT_ERR_HIP, "GPU BVH build: out of device memory (%zu bytes of scratch)", need);
+        sg->arena.reset();
+        sg->arena_bytes = 0;
+        if (dev_alloc(sg->arena, need) != LPT_OK) return fail(LPT_ERR_HIP, "GPU BVH build: out of device memory (%zu bytes of scratch)", need);
         sg->arena_bytes = need;
     }
     size_t arena_used = 0;
-    auto scratch = [&](size_t bytes) -> void * {
+    auto carve = [&](auto *&p, size_t count) {
         const size_t at = (arena_used + 255u) & ~(size_t)255u;
-        if (at + bytes > sg->arena_bytes) return nullptr;
-        arena_used = at + bytes;
-        return (char *)sg->arena + at;
+        p = (std::remove_reference_t<decltype(p)>)((char *)sg->arena.get() + at);
+        arena_used = at + sizeof(*p) * count;
     };
-    auto done = [&](int st) { hipStreamSynchronize(s); return st; };
-#define LB_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return done(fail(LPT_ERR_HIP, "GPU BVH build: %s", hipGetErrorString(e_))); } while (0)
-#define SCR(type, name, count) type *name = (type *)scratch(sizeof(type) * (size_t)(count)); if (!name) return done(fail(LPT_ERR_HIP, "GPU BVH build: out of device memory"));
-    SCR(uint32_t, keys, n) SCR(uint32_t, vals, n) SCR(uint32_t, keys_s, n) SCR(uint32_t, vals_s, n)
+    uint32_t *keys, *vals, *keys_s, *vals_s, *leaf_big, *inner_count, *tri_count, *inner_off, *tri_off;
+    uint8_t *cub_tmp;
+    uint4 *nodes_big;
+    int *items_a, *items_b, *kid_ref;
     LbvhTree T{};
-    SCR(int, t_left, n) SCR(int, t_right, n) SCR(int, t_parent, n) SCR(int, t_leafp, n)
-    SCR(uint32_t, t_first, n) SCR(uint32_t, t_last, n) SCR(float4, t_lo, n) SCR(float4, t_hi, n) SCR(float4, t_tlo, n) SCR(float4, t_thi, n) SCR(uint32_t, t_flag, n)
-    T.left = t_left; T.right = t_right; T.parent = t_parent; T.leaf_parent = t_leafp; T.first = t_first; T.last = t_last;
-    T.lo = t_lo; T.hi = t_hi; T.tri_lo = t_tlo; T.tri_hi = t_thi; T.flag = t_flag; T.sorted_tri = vals_s; T.keys = keys_s; T.n = n;
+    carve(keys, n); carve(vals, n); carve(keys_s, n); carve(vals_s, n);
+    carve(T.left, n); carve(T.right, n); carve(T.parent, n); carve(T.leaf_parent, n);
+    carve(T.first, n); carve(T.last, n); carve(T.lo, n); carve(T.hi, n); carve(T.tri_lo, n); carve(T.tri_hi, n); carve(T.flag, n);
+    carve(cub_tmp, cub_cap);
+    // wide tree, level by level
+    carve(nodes_big, 4u * (size_t)n);            // <= n-1 wide nodes
+    carve(leaf_big, (size_t)kNodeTris * n);      // their triangle places (16 per node; the final array is cut to the nodes there are)
+    carve(items_a, n); carve(items_b, n); carve(kid_ref, 8u * (size_t)n);
+    carve(inner_count, n); carve(tri_count, n); carve(inner_off, n); carve(tri_off, n);
+    if (arena_used > sg->arena_bytes) return fail(LPT_ERR_HIP, "GPU BVH build: out of device memory");
+    T.sorted_tri = vals_s; T.keys = keys_s; T.n = n;
+
     const uint32_t b256 = div_up(n, 256u);
     hipLaunchKernelGGL(k_lbvh_morton, dim3(b256), dim3(256), 0, s, sg->d, n, make_float3(blo[0], blo[1], blo[2]), make_float3(binv[0], binv[1], binv[2]), keys, vals);
-    void *cub_tmp = scratch(std::max(sort_bytes, scan_bytes));
-    if (!cub_tmp) return done(fail(LPT_ERR_HIP, "GPU BVH build: out of device memory"));
-    size_t cub_bytes = std::max(sort_bytes, scan_bytes);
-    if (hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, keys, keys_s, vals, vals_s, (int)n, 0, 30, s) != hipSuccess) return done(fail(LPT_ERR_HIP, "GPU BVH build: sort failed"));
+    size_t cub_bytes = cub_cap;
+    if (hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, keys, keys_s, vals, vals_s, (int)n, 0, 30, s) != hipSuccess) return fail(LPT_ERR_HIP, "GPU BVH build: sort failed");
     hipLaunchKernelGGL(k_lbvh_leaf_boxes, dim3(b256), dim3(256), 0, s, sg->d, T);
-    LB_TRY(hipMemsetAsync(t_flag, 0, sizeof(uint32_t) * n, s));
+    HIP_TRY(hipMemsetAsync(T.flag, 0, sizeof(uint32_t) * n, s));
     hipLaunchKernelGGL(k_lbvh_tree, dim3(b256), dim3(256), 0, s, T);
     hipLaunchKernelGGL(k_lbvh_fit, dim3(b256), dim3(256), 0, s, T);
 
-    // wide tree, level by level
-    SCR(uint4, nodes_big, 4u * (size_t)n)           // <= n-1 wide nodes
-    SCR(uint32_t, leaf_big, (size_t)kNodeTris * n)  // their triangle places (16 per node; the final array is cut to the nodes there are)
-    SCR(int, items_a, n) SCR(int, items_b, n) SCR(int, kid_ref, 8u * (size_t)n)
-    SCR(uint32_t, inner_count, n) SCR(uint32_t, tri_count, n) SCR(uint32_t, inner_off, n) SCR(uint32_t, tri_off, n)
-    LB_TRY(hipMemsetAsync(leaf_big, 0xFF, sizeof(uint32_t) * (size_t)kNodeTris * n, s));   // holes: LPT_INVALID_INDEX
-    LB_TRY(hipMemsetAsync(items_a, 0, sizeof(int), s));  // level 0 = the binary root
+    HIP_TRY(hipMemsetAsync(leaf_big, 0xFF, sizeof(uint32_t) * (size_t)kNodeTris * n, s));   // holes: LPT_INVALID_INDEX
+    HIP_TRY(hipMemsetAsync(items_a, 0, sizeof(int), s));  // level 0 = the binary root
     int *items_cur = items_a, *items_next = items_b;
     uint32_t n_items = 1, level_first = 0, tri_running = 0;
-    sg->level_start.clear();
+    DevTree t;
     while (n_items) {
-        if (sg->level_start.size() > 64) return done(fail(LPT_ERR_ACCEL_BUILD, "GPU BVH build: tree deeper than 64 levels"));
+        if (t.level_start.size() > 64) return fail(LPT_ERR_ACCEL_BUILD, "GPU BVH build: tree deeper than 64 levels");
         LbvhLevel L{items_cur, n_items, kid_ref, inner_count, tri_count};
         hipLaunchKernelGGL(k_lbvh_collapse, dim3(div_up(n_items, 64u)), dim3(64), 0, s, T, L);
-        cub_bytes = std::max(sort_bytes, scan_bytes);
+        cub_bytes = cub_cap;
         hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_bytes, inner_count, inner_off, (int)n_items, s);
-        cub_bytes = std::max(sort_bytes, scan_bytes);
+        cub_bytes = cub_cap;
         hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_bytes, tri_count, tri_off, (int)n_items, s);
         uint32_t tail[4];
-        LB_TRY(hipMemcpyAsync(&tail[0], inner_off + (n_items - 1), 4, hipMemcpyDeviceToHost, s));
-        LB_TRY(hipMemcpyAsync(&tail[1], inner_count + (n_items - 1), 4, hipMemcpyDeviceToHost, s));
-        LB_TRY(hipMemcpyAsync(&tail[2], tri_off + (n_items - 1), 4, hipMemcpyDeviceToHost, s));
-        LB_TRY(hipMemcpyAsync(&tail[3], tri_count + (n_items - 1), 4, hipMemcpyDeviceToHost, s));
-        LB_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpyAsync(&tail[0], inner_off + (n_items - 1), 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&tail[1], inner_count + (n_items - 1), 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&tail[2], tri_off + (n_items - 1), 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&tail[3], tri_count + (n_items - 1), 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
         const uint32_t inner_total = tail[0] + tail[1], tri_total = tail[2] + tail[3];
-        if ((size_t)level_first + n_items + inner_total > n) return done(fail(LPT_ERR_ACCEL_BUILD, "GPU BVH build: node budget exceeded"));
+        if ((size_t)level_first + n_items + inner_total > n) return fail(LPT_ERR_ACCEL_BUILD, "GPU BVH build: node budget exceeded");
         hipLaunchKernelGGL(k_lbvh_emit, dim3(div_up(n_items, 64u)), dim3(64), 0, s, T, L, inner_off, tri_off, level_first, level_first + n_items, tri_running,
                            nodes_big, leaf_big, items_next);
-        sg->level_start.push_back(level_first);
+        t.level_start.push_back(level_first);
         level_first += n_items;
         tri_running += tri_total;
         n_items = inner_total;
         std::swap(items_cur, items_next);
     }
-    sg->level_start.push_back(level_first);
-    if (tri_running != n) return done(fail(LPT_ERR_ACCEL_BUILD, "GPU BVH build: %u of %u triangles referenced", tri_running, n));
-    const uint32_t n_nodes = level_first;
-    LB_TRY(hipMalloc(&sg->nodes, sizeof(Node8) * (size_t)n_nodes));
-    LB_TRY(hipMemcpyAsync(sg->nodes, nodes_big, sizeof(Node8) * (size_t)n_nodes, hipMemcpyDeviceToDevice, s));
-    LB_TRY(hipMalloc(&sg->node_lo, sizeof(float4) * (size_t)n_nodes));
-    LB_TRY(hipMalloc(&sg->node_hi, sizeof(float4) * (size_t)n_nodes));
-    LB_TRY(hipMalloc(&sg->leaf_prim, sizeof(uint32_t) * (size_t)kNodeTris * n_nodes));
-    LB_TRY(hipMemcpyAsync(sg->leaf_prim, leaf_big, sizeof(uint32_t) * (size_t)kNodeTris * n_nodes, hipMemcpyDeviceToDevice, s));
-    // Woop maps: prim order (host, double precision) -> their places (holes stay zero)
-    LB_TRY(hipMalloc(&sg->woop, sizeof(WoopTri) * (size_t)kNodeTris * n_nodes));
-    LB_TRY(hipMemsetAsync(sg->woop, 0, sizeof(WoopTri) * (size_t)kNodeTris * n_nodes, s));
-    const float4 *woop_src = dev_woop;
-    if (host_woop) {
-        SCR(float4, woop_prim, 3u * (size_t)n)
-        LB_TRY(hipMemcpyAsync(woop_prim, host_woop, sizeof(WoopTri) * (size_t)n, hipMemcpyHostToDevice, s));
-        woop_src = woop_prim;
-    }
-    hipLaunchKernelGGL(k_lbvh_scatter_woop, dim3(div_up(kNodeTris * n_nodes, 256u)), dim3(256), 0, s, woop_src, (float4 *)sg->woop, (const uint32_t *)sg->leaf_prim, kNodeTris * n_nodes, 0u, n);
-    sg->d.nodes = (const DNode8 *)sg->nodes;
-    sg->d.leaf_prim = (const uint32_t *)sg->leaf_prim;
-    sg->d.woop = (const float4 *)sg->woop;
-    for (size_t l = sg->level_start.size() - 1; l-- > 0;) {
-        const uint32_t a = sg->level_start[l], b = sg->level_start[l + 1];
-        if (b > a) hipLaunchKernelGGL(k_refit_level, dim3(div_up(b - a, 64u)), dim3(64), 0, s, sg->d, (uint4 *)sg->nodes, (float4 *)sg->node_lo, (float4 *)sg->node_hi, a, b);
-    }
-    LB_TRY(hipGetLastError());
-    sg->stats.nodes = n_nodes;
-    sg->stats.max_depth = (uint32_t)sg->level_start.size() - 1u;
-    const int st = done(LPT_OK);
-    sg->stats.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return st;
-#undef LB_TRY
-#undef SCR
+    t.level_start.push_back(level_first);
+    if (tri_running != n) return fail(LPT_ERR_ACCEL_BUILD, "GPU BVH build: %u of %u triangles referenced", tri_running, n);
+    t.n_nodes = level_first;
+    t.max_depth = (uint32_t)t.level_start.size() - 1u;
+    const size_t places = (size_t)kNodeTris * t.n_nodes;
+    TRY(dev_alloc(t.nodes, sizeof(Node8) * (size_t)t.n_nodes));
+    HIP_TRY(hipMemcpyAsync(t.nodes.get(), nodes_big, sizeof(Node8) * (size_t)t.n_nodes, hipMemcpyDeviceToDevice, s));
+    TRY(dev_alloc(t.node_lo, sizeof(float4) * (size_t)t.n_nodes));
+    TRY(dev_alloc(t.node_hi, sizeof(float4) * (size_t)t.n_nodes));
+    TRY(dev_alloc(t.leaf_prim, sizeof(uint32_t) * places));
+    HIP_TRY(hipMemcpyAsync(t.leaf_prim.get(), leaf_big, sizeof(uint32_t) * places, hipMemcpyDeviceToDevice, s));
+    // Woop maps: prim order -> their places (holes stay zero)
+    TRY(dev_alloc(t.woop, sizeof(WoopTri) * places));
+    HIP_TRY(hipMemsetAsync(t.woop.get(), 0, sizeof(WoopTri) * places, s));
+    scatter_woop(t, woop_prim, 0u, n, s);
+    DScene d = sg->d;   // the scene's triangles and grid, the new tree's leaves
+    d.leaf_prim = as<const uint32_t>(t.leaf_prim);
+    refit_levels(d, t, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    t.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    out = std::move(t);
+    return LPT_OK;
+}
+
+// The current tree's boxes from the shading records as they are now (topology kept), after the padding and grid that follow from them: the padding's
+// scene-wide part follows the scene's largest coordinate (ANY growth counts — ADVICE r05 —; it never shrinks).  Blocking.
+static int refit(lpt_scene_gpu *sg) {
+    hipStream_t s = sg->dev->stream;
+    float blo[3], bhi[3];
+    TRY(scene_bounds_and_grid(sg, sg->stats.triangles, s, blo, bhi, true));
+    refit_levels(sg->d, sg->tree, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    return LPT_OK;
+}
+
+// what the kernels see of the current tree, and its part of lpt_accel_stats
+static void bind_view(lpt_scene_gpu *sg) {
+    const DevTree &t = sg->tree;
+    sg->d.nodes = as<const DNode8>(t.nodes);
+    sg->d.leaf_prim = as<const uint32_t>(t.leaf_prim);
+    sg->d.woop = as<const float4>(t.woop);
+    // a stack entry holds the unvisited siblings below a node at depth 1..max_depth-1 (the root's own group has one
+    // member and is never pushed, the deepest nodes have no inner children): max_depth-1 entries are enough
+    sg->d.stack_entries = t.max_depth > 2u ? t.max_depth - 1u : 1u;
+    sg->stats.nodes = t.n_nodes;
+    sg->stats.max_depth = t.max_depth;
+    sg->stats.build_ms = t.build_ms;
 }
 
 // The material as the shading records carry it: a material whose albedo and mra textures were paired at upload names the pair.
 // Every other texture id is an index into the atlas or LPT_INVALID_INDEX: an id beyond the images means "no texture" (SPEC §9, as
 // the oracle reads it) and must not reach the kernel as a value it would take for the paired encoding.  `ok` = false:
 // the material samples an image on its own that the atlas does not hold (it was only known as half of a pair at upload time).
-static lpt_material device_material(const lpt_scene_gpu *sg, const lpt_material &m, bool *ok = nullptr) {
+static lpt_material device_material(const TexturePairs &p, const lpt_material &m, bool *ok = nullptr) {
     lpt_material d = m;
     if (ok) *ok = true;
-    const auto it = sg->pair_map.find(std::make_pair(m.albedo_texture, m.mra_texture));
-    if (it != sg->pair_map.end()) {
-        const DImage &di = sg->pair_descs[it->second];
+    const auto it = p.map.find(std::make_pair(m.albedo_texture, m.mra_texture));
+    if (it != p.map.end()) {
+        const DImage &di = p.descs[it->second];
         d.albedo_texture = kPairedBit | di.offset;          // in 8-byte texels, < 2^30
         d.mra_texture = di.width | (di.height << 16);       // both <= 65535 (checked when the pair is built)
         return d;
     }
     uint32_t *ids[2] = {&d.albedo_texture, &d.mra_texture};
     for (uint32_t *id : ids) {
-        if (*id >= sg->image_resident.size()) *id = LPT_INVALID_INDEX;
-        else if (!sg->image_resident[*id] && ok) *ok = false;
+        if (*id >= p.image_resident.size()) *id = LPT_INVALID_INDEX;
+        else if (!p.image_resident[*id] && ok) *ok = false;
     }
     return d;
 }
 
-// kernel arguments for re-baking instance i on the device (k_bake_instance)
-static int make_bake_args(const lpt_scene_gpu *sg, const lpt_scene &scene, size_t i, uint32_t first, uint32_t n, BakeArgs &a) {
-    const lpt_instance &now = scene.instances[i];
-    const lpt_blas_entry &e = scene.entries[now.blas_index];
-    if (e.index_count / 3u != n) return fail(LPT_ERR_INVALID_ARG, "triangle count of instance %zu changed since the upload", i);
-    memcpy(a.m, now.model_to_world, sizeof a.m);
-    const float *m = a.m;
-    const float a00 = m[0], a10 = m[1], a20 = m[2], a01 = m[4], a11 = m[5], a21 = m[6], a02 = m[8], a12 = m[9], a22 = m[10];
-    a.c[0] = a11 * a22 - a12 * a21; a.c[1] = a12 * a20 - a10 * a22; a.c[2] = a10 * a21 - a11 * a20;   // bvh.cpp bake_one
-    a.c[3] = a02 * a21 - a01 * a22; a.c[4] = a00 * a22 - a02 * a20; a.c[5] = a01 * a20 - a00 * a21;
-    a.c[6] = a01 * a12 - a02 * a11; a.c[7] = a02 * a10 - a00 * a12; a.c[8] = a00 * a11 - a01 * a10;
-    a.vertex_offset = e.vertex_offset; a.index_offset = e.index_offset; a.first_tri = first; a.n_tris = n;
-    bool resident = true;
-    const lpt_material dm = device_material(sg, scene.materials[now.material_index < scene.materials.size() ? now.material_index : 0u], &resident);
-    if (!resident) return fail(LPT_ERR_INVALID_ARG, "instance %zu now samples a texture on its own that was uploaded only as half of an (albedo, mra) pair: upload the scene again", i);
-    memcpy(a.mat, &dm, 32);
+// Bakes the instances `which` on the device (fp32 transform, cofactor normals, binary64 Woop maps: bit-identical to the host bake): their shading
+// records in place, their Woop maps in prim order into `woop_prim`.  Every instance is checked before the first launch.  A non-finite vertex is
+// LPT_ERR_ACCEL_BUILD, found before any kernel reads the triangles; the flag is reset for the next bake.
+static int bake_instances(lpt_scene_gpu *sg, const lpt_scene &scene, const std::vector<uint32_t> &which, void *woop_prim) {
+    std::vector<BakeArgs> args;
+    for (uint32_t i : which) {
+        const lpt_instance &now = scene.instances[i];
+        const uint32_t n = sg->inst_count[i];
+        if (!n) continue;
+        const lpt_blas_entry &e = scene.entries[now.blas_index];
+        if (e.index_count / 3u != n) return fail(LPT_ERR_INVALID_ARG, "triangle count of instance %u changed since the upload", i);
+        BakeArgs a;
+        memcpy(a.m, now.model_to_world, sizeof a.m);
+        const float *m = a.m;
+        const float a00 = m[0], a10 = m[1], a20 = m[2], a01 = m[4], a11 = m[5], a21 = m[6], a02 = m[8], a12 = m[9], a22 = m[10];
+        a.c[0] = a11 * a22 - a12 * a21; a.c[1] = a12 * a20 - a10 * a22; a.c[2] = a10 * a21 - a11 * a20;   // bvh.cpp bake_one
+        a.c[3] = a02 * a21 - a01 * a22; a.c[4] = a00 * a22 - a02 * a20; a.c[5] = a01 * a20 - a00 * a21;
+        a.c[6] = a01 * a12 - a02 * a11; a.c[7] = a02 * a10 - a00 * a12; a.c[8] = a00 * a11 - a01 * a10;
+        a.vertex_offset = e.vertex_offset; a.index_offset = e.index_offset; a.first_tri = sg->inst_first[i]; a.n_tris = n;
+        bool resident = true;
+        const lpt_material dm = device_material(sg->pairs, scene.materials[now.material_index < scene.materials.size() ? now.material_index : 0u], &resident);
+        if (!resident) return fail(LPT_ERR_INVALID_ARG, "instance %u now samples a texture on its own that was uploaded only as half of an (albedo, mra) pair: upload the scene again", i);
+        memcpy(a.mat, &dm, 32);
+        args.push_back(a);
+    }
+    if (args.empty()) return LPT_OK;
+    hipStream_t s = sg->dev->stream;
+    for (const BakeArgs &a : args)
+        hipLaunchKernelGGL(k_bake_instance, dim3(div_up(a.n_tris, 256u)), dim3(256), 0, s, a, as<const float4>(sg->obj_verts), as<const uint32_t>(sg->obj_indices),
+                           as<float4>(sg->tri_verts), (float4 *)woop_prim, as<uint32_t>(sg->bad_flag));
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, sg->bad_flag.get(), sizeof bad, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!bad) return LPT_OK;
+    HIP_TRY(hipMemsetAsync(sg->bad_flag.get(), 0, sizeof bad, s));
+    return fail(LPT_ERR_ACCEL_BUILD, "non-finite vertex in a baked instance");
+}
+
+static std::vector<uint32_t> every_instance(const lpt_scene &scene) {
+    std::vector<uint32_t> all(scene.instances.size());
+    std::iota(all.begin(), all.end(), 0u);
+    return all;
+}
+
+// update and rebuild: the scene's meshes and instance list must be the ones that were uploaded; anything else needs lpt_scene_upload again
+static int check_same_layout(const lpt_scene_gpu *sg, const lpt_scene &scene, const char *fn) {
+    if (scene.instances.size() != sg->instances.size() || scene.entries.size() != sg->n_entries ||
+        scene.vertices.size() != sg->n_vertices || scene.indices.size() != sg->n_indices)
+        return fail(LPT_ERR_INVALID_ARG, "%s: the scene's meshes / instance list changed since the upload; upload again", fn);
+    for (size_t i = 0; i < scene.instances.size(); ++i)
+        if (scene.instances[i].blas_index != sg->instances[i].blas_index) return fail(LPT_ERR_INVALID_ARG, "%s: instance %zu refers to another mesh; upload again", fn, i);
     return LPT_OK;
+}
+
+// ---------------------------------------------------------------------------- upload: host steps
+// the GPU build's layout: which run of baked triangles every instance owns (SPEC §2.5 order).  No vertex is touched on the host
+static int instance_layout(const lpt_scene &scene, Accel &acc, uint32_t &n_tris) {
+    size_t total = 0;
+    for (const lpt_instance &in : scene.instances) {
+        const uint32_t cnt = in.blas_index < scene.entries.size() ? scene.entries[in.blas_index].index_count / 3u : 0u;
+        acc.inst_first.push_back((uint32_t)total);
+        acc.inst_count.push_back(cnt);
+        total += cnt;
+    }
+    if (total >= (1u << 29)) return fail(LPT_ERR_ACCEL_BUILD, "too many triangles (%zu)", total);
+    n_tris = (uint32_t)total;
+    return LPT_OK;
+}
+
+// Paired textures: a material that has both an albedo and an mra texture of one size gets the two interleaved — 8 B per texel
+// (albedo RGBA8, mra RGBA8) in apron tiles of 128 B — so that ONE set of four taps, in ONE cache line, serves both lookups of a shaded hit:
+// 1 line per hit instead of 2 x 1.4 (1.56 with plain 4x4 tiles) (k_shade is bound by HBM traffic, most of it texels).  Lossless: the taps and
+// the filter arithmetic are those of two separate lookups.  An image that some material samples on its own (no partner, a partner
+// of another size, another partner's pair over the budget) also stays in the tiled atlas; one that only ever appears as half of a
+// pair does not (scene.rs:172-184: each image once) — `image_resident`.  Returns the pairs' texels.
+static std::vector<uint64_t> pair_textures(const lpt_scene &scene, bool enable, TexturePairs &p) {
+    std::vector<uint64_t> texels;
+    const size_t budget = (size_t)1 << 30;   // bytes of paired texels per scene
+    for (const lpt_material &m : scene.materials) {
+        if (!enable) break;
+        const uint32_t a = m.albedo_texture, r = m.mra_texture;
+        if (a >= scene.images.size() || r >= scene.images.size()) continue;
+        const Image &ia = scene.images[a], &ir = scene.images[r];
+        if (ia.width != ir.width || ia.height != ir.height || !ia.width || !ia.height || ia.width > 65535u || ia.height > 65535u) continue;
+        if (p.map.count(std::make_pair(a, r))) continue;
+        // apron tiles (kernels.h texture_lookup_pair): a stored 4x4 tile covers a 3x3 block of the image + its right / lower neighbours
+        const uint32_t tx = (ia.width + 2u) / 3u, ty = (ia.height + 2u) / 3u;
+        if ((texels.size() + (size_t)tx * ty * 16u) * 8u > budget || texels.size() + (size_t)tx * ty * 16u > 0x3FFFFFFFull) continue;
+        DImage di;
+        di.offset = (uint32_t)texels.size();   // in 8-byte texels
+        di.width = ia.width; di.height = ia.height; di.pad = tx;
+        const size_t base = texels.size();
+        texels.resize(base + (size_t)tx * ty * 16u, 0);
+        for (uint32_t tyi = 0; tyi < ty; ++tyi)
+            for (uint32_t txi = 0; txi < tx; ++txi)
+                for (uint32_t j = 0; j < 4u; ++j)
+                    for (uint32_t i = 0; i < 4u; ++i) {
+                        const uint32_t x = (3u * txi + i) % ia.width, y = (3u * tyi + j) % ia.height;   // SPEC §9: repeat wrap
+                        uint32_t wa, wr;
+                        memcpy(&wa, &ia.rgba8[4u * ((size_t)y * ia.width + x)], 4);
+                        memcpy(&wr, &ir.rgba8[4u * ((size_t)y * ir.width + x)], 4);
+                        texels[base + ((size_t)tyi * tx + txi) * 16u + j * 4u + i] = (uint64_t)wa | ((uint64_t)wr << 32);
+                    }
+        p.map[std::make_pair(a, r)] = (uint32_t)p.descs.size();
+        p.descs.push_back(di);
+    }
+    // an image no material references is kept: a later material edit (lpt_scene_gpu_update_instances) may start to sample it
+    std::vector<uint8_t> referenced(scene.images.size(), 0), alone(scene.images.size(), 0);
+    for (const lpt_material &m : scene.materials) {
+        const bool paired = p.map.count(std::make_pair(m.albedo_texture, m.mra_texture)) != 0;
+        for (uint32_t id : {m.albedo_texture, m.mra_texture})
+            if (id < scene.images.size()) { referenced[id] = 1; if (!paired) alone[id] = 1; }
+    }
+    p.image_resident.assign(scene.images.size(), 1);
+    for (size_t i = 0; i < scene.images.size(); ++i) p.image_resident[i] = (!referenced[i] || alone[i]) ? 1 : 0;
+    return texels;
+}
+
+// The tiled atlas of the images the pairs do not hold: texels are stored in 8x4-texel tiles of 128 B (one cache line): the 2x2 bilinear footprint then
+// touches 1.4 lines on average instead of 2 (k_shade is bound by L2-miss traffic); `pad` = tiles per row.  Returns the texels, one descriptor per image in `descs`.
+static std::vector<uint8_t> tiled_atlas(const lpt_scene &scene, const std::vector<uint8_t> &image_resident, std::vector<DImage> &descs) {
+    std::vector<uint8_t> texels;
+    for (size_t ii = 0; ii < scene.images.size(); ++ii) {
+        const Image &im = scene.images[ii];
+        DImage di;
+        di.offset = (uint32_t)(texels.size() / 4);
+        if (!image_resident[ii]) {   // only ever half of a pair: lives in the pairs' texels, no shading record carries its id
+            di.width = di.height = di.pad = 0u;
+            descs.push_back(di);
+            continue;
+        }
+        di.width = im.width; di.height = im.height;
+        const uint32_t tx = (im.width + 7u) / 8u, ty = (im.height + 3u) / 4u;
+        di.pad = tx;
+        descs.push_back(di);
+        const size_t base = texels.size();
+        texels.resize(base + (size_t)tx * ty * 128u, 0);
+        for (uint32_t y = 0; y < im.height; ++y)
+            for (uint32_t x = 0; x < im.width; ++x)
+                memcpy(&texels[base + 4u * (((size_t)(y >> 2) * tx + (x >> 3)) * 32u + (y & 3u) * 8u + (x & 7u))], &im.rgba8[4u * ((size_t)y * im.width + x)], 4);
+    }
+    return texels;
+}
+
+// shading records (kernels.h DScene::tri_verts) of the host-baked triangles: three vertices + the material, 128 B per triangle
+struct TriRec { float4 v[kTriRec]; };
+static_assert(sizeof(TriRec) == 128 && sizeof(lpt_vertex) * 3 == 96 && sizeof(lpt_material) == 32, "shading record layout");
+static std::vector<TriRec> shading_records(const lpt_scene &scene, const Accel &acc, const TexturePairs &p) {
+    std::vector<TriRec> recs(acc.tri_material.size());
+    for (size_t t = 0; t < recs.size(); ++t) {
+        memcpy(recs[t].v, &acc.tri_verts[3 * t], 96);
+        const lpt_material dm = device_material(p, scene.materials[acc.tri_material[t] < scene.materials.size() ? acc.tri_material[t] : 0]);
+        memcpy(&recs[t].v[6], &dm, 32);
+    }
+    return recs;
 }
 
 extern "C" {
@@ -581,10 +774,7 @@ int lpt_scene_gpu_destroy(lpt_scene_gpu *sg) {
     // pointer): its next raytrace() is the no-op of a renderer without resources (renderer.rs:403-407) until set_resources is called again
     for (lpt_renderer *r : sg->dev->renderers)
         if (r->sg == sg) { r->sg = nullptr; r->resources_set = false; }
-    void *ptrs[] = {sg->nodes, sg->woop, sg->leaf_prim, sg->tri_verts, sg->materials, sg->lights, sg->texels, sg->images, sg->srgb_lut,
-                    sg->node_lo, sg->node_hi, sg->obj_verts, sg->obj_indices, sg->bad_flag, sg->arena, sg->pair_texels, sg->pair_images};
-    for (void *p : ptrs) if (p) hipFree(p);
-    delete sg;
+    delete sg;   // its device memory with it
     return LPT_OK;
 }
 
@@ -593,222 +783,105 @@ int lpt_scene_upload(lpt_device *dev, const lpt_scene *scene, lpt_scene_gpu **ou
 int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags, lpt_scene_gpu **out) {
     if (!dev || !scene || !out) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_upload: null");
     if ((flags & ~LPT_UPLOAD_NO_TEXTURE_PAIRS) > LPT_ACCEL_BUILD_GPU_LBVH) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_upload_ex: unknown flags %u", flags);
-    const bool pair_textures = !(flags & LPT_UPLOAD_NO_TEXTURE_PAIRS);
+    const bool enable_pairs = !(flags & LPT_UPLOAD_NO_TEXTURE_PAIRS);
     flags &= ~LPT_UPLOAD_NO_TEXTURE_PAIRS;
     HIP_TRY(hipSetDevice(dev->ordinal));
     const auto t_upload = std::chrono::steady_clock::now();
+    // the layout; the host bake and build unless the GPU builds the tree (tiny scenes always go to the host builder: a radix tree needs >= 2 leaves)
     Accel acc;
-    bool gpu_build = flags == LPT_ACCEL_BUILD_GPU_LBVH;
     uint32_t n_tris = 0;
-    int st = LPT_OK;
+    bool gpu_build = flags == LPT_ACCEL_BUILD_GPU_LBVH;
     if (gpu_build) {
-        // layout only: which run of baked triangles every instance owns (SPEC §2.5 order).  No vertex is touched on the
-        // host; the instances are baked on the device below (k_bake_instance)
-        acc.inst_first.assign(scene->instances.size(), 0u);
-        acc.inst_count.assign(scene->instances.size(), 0u);
-        size_t total = 0;
-        for (size_t i = 0; i < scene->instances.size(); ++i) {
-            const lpt_instance &in = scene->instances[i];
-            const uint32_t cnt = in.blas_index < scene->entries.size() ? scene->entries[in.blas_index].index_count / 3u : 0u;
-            acc.inst_first[i] = (uint32_t)total;
-            acc.inst_count[i] = cnt;
-            total += cnt;
-        }
-        if (total >= (1u << 29)) return fail(LPT_ERR_ACCEL_BUILD, "too many triangles (%zu)", total);
-        n_tris = (uint32_t)total;
-        if (n_tris < 16u) gpu_build = false;   // tiny scenes: the host builder (a radix tree needs >= 2 leaves)
+        TRY(instance_layout(*scene, acc, n_tris));
+        gpu_build = n_tris >= 16u;
     }
     if (!gpu_build) {
-        st = bake_and_build(*scene, acc);
-        if (st != LPT_OK) return st;
+        TRY(bake_and_build(*scene, acc));
         n_tris = (uint32_t)acc.tri_material.size();
     }
-    lpt_scene_gpu *sg = new lpt_scene_gpu();
-    sg->dev = dev;
-    hipStream_t s = dev->stream;
-#define UP(field, vec)                                                         \
-    if ((st = upload(&sg->field, (vec).data(), (vec).size(), s)) != LPT_OK) {  \
-        lpt_scene_gpu_destroy(sg);                                             \
-        return st;                                                             \
-    }
-    static_assert(sizeof(float4) * kTriRec == 128 && sizeof(lpt_vertex) * 3 == 96 && sizeof(lpt_material) == 32, "shading record layout");
-    // Paired textures: a material that has both an albedo and an mra texture of one size gets the two interleaved — 8 B per texel
-    // (albedo RGBA8, mra RGBA8) in apron tiles of 128 B — so that ONE set of four taps, in ONE cache line, serves both lookups of a shaded hit:
-    // 1 line per hit instead of 2 x 1.4 (1.56 with plain 4x4 tiles) (k_shade is bound by HBM traffic, most of it texels).  Lossless: the taps and
-    // the filter arithmetic are those of two separate lookups.  An image that some material samples on its own (no partner, a partner
-    // of another size, another partner's pair over the budget) also stays in the tiled atlas; one that only ever appears as half of a
-    // pair does not (scene.rs:172-184: each image once) — `image_resident`.
-    std::vector<DImage> pair_descs;
-    std::vector<uint64_t> pair_texels;
-    {
-        const bool enable = pair_textures;
-        const size_t budget = (size_t)1 << 30;   // bytes of paired texels per scene
-        for (const lpt_material &m : scene->materials) {
-            if (!enable) break;
-            const uint32_t a = m.albedo_texture, r = m.mra_texture;
-            if (a >= scene->images.size() || r >= scene->images.size()) continue;
-            const Image &ia = scene->images[a], &ir = scene->images[r];
-            if (ia.width != ir.width || ia.height != ir.height || !ia.width || !ia.height || ia.width > 65535u || ia.height > 65535u) continue;
-            if (sg->pair_map.count(std::make_pair(a, r))) continue;
-            // apron tiles (kernels.h texture_lookup_pair): a stored 4x4 tile covers a 3x3 block of the image + its right / lower neighbours
-            const uint32_t tx = (ia.width + 2u) / 3u, ty = (ia.height + 2u) / 3u;
-            if ((pair_texels.size() + (size_t)tx * ty * 16u) * 8u > budget || pair_texels.size() + (size_t)tx * ty * 16u > 0x3FFFFFFFull) continue;
-            DImage di;
-            di.offset = (uint32_t)pair_texels.size();   // in 8-byte texels
-            di.width = ia.width; di.height = ia.height; di.pad = tx;
-            const size_t base = pair_texels.size();
-            pair_texels.resize(base + (size_t)tx * ty * 16u, 0);
-            for (uint32_t tyi = 0; tyi < ty; ++tyi)
-                for (uint32_t txi = 0; txi < tx; ++txi)
-                    for (uint32_t j = 0; j < 4u; ++j)
-                        for (uint32_t i = 0; i < 4u; ++i) {
-                            const uint32_t x = (3u * txi + i) % ia.width, y = (3u * tyi + j) % ia.height;   // SPEC §9: repeat wrap
-                            uint32_t wa, wr;
-                            memcpy(&wa, &ia.rgba8[4u * ((size_t)y * ia.width + x)], 4);
-                            memcpy(&wr, &ir.rgba8[4u * ((size_t)y * ir.width + x)], 4);
-                            pair_texels[base + ((size_t)tyi * tx + txi) * 16u + j * 4u + i] = (uint64_t)wa | ((uint64_t)wr << 32);
-                        }
-            sg->pair_map[std::make_pair(a, r)] = (uint32_t)pair_descs.size();
-            pair_descs.push_back(di);
-            sg->pair_descs.push_back(di);
-        }
-        // an image no material references is kept: a later material edit (lpt_scene_gpu_update_instances) may start to sample it
-        std::vector<uint8_t> referenced(scene->images.size(), 0), alone(scene->images.size(), 0);
-        for (const lpt_material &m : scene->materials) {
-            const bool paired = sg->pair_map.count(std::make_pair(m.albedo_texture, m.mra_texture)) != 0;
-            for (uint32_t id : {m.albedo_texture, m.mra_texture})
-                if (id < scene->images.size()) { referenced[id] = 1; if (!paired) alone[id] = 1; }
-        }
-        sg->image_resident.assign(scene->images.size(), 1);
-        for (size_t i = 0; i < scene->images.size(); ++i) sg->image_resident[i] = (!referenced[i] || alone[i]) ? 1 : 0;
-    }
-    if (!gpu_build) {
-        UP(nodes, acc.nodes)
-        UP(woop, acc.woop)
-        UP(leaf_prim, acc.leaf_prim)
-        // shading records (kernels.h DScene::tri_verts): three vertices + the material, 128 B per triangle
-        struct TriRec { float4 v[kTriRec]; };
-        std::vector<TriRec> recs(acc.tri_material.size());
-        for (size_t t = 0; t < recs.size(); ++t) {
-            memcpy(recs[t].v, &acc.tri_verts[3 * t], 96);
-            const lpt_material dm = device_material(sg, scene->materials[acc.tri_material[t] < scene->materials.size() ? acc.tri_material[t] : 0]);
-            memcpy(&recs[t].v[6], &dm, 32);
-        }
-        UP(tri_verts, recs)
-    } else {
-        hipError_t e = hipMalloc(&sg->tri_verts, sizeof(float4) * kTriRec * (size_t)n_tris);   // written by k_bake_instance
-        if (e != hipSuccess) { lpt_scene_gpu_destroy(sg); return fail(LPT_ERR_HIP, "scene upload failed: %s", hipGetErrorString(e)); }
-    }
-    UP(materials, scene->materials)
-    UP(lights, scene->lights)
+    TexturePairs pairs;
+    const std::vector<uint64_t> pair_texels = pair_textures(*scene, enable_pairs, pairs);
     std::vector<DImage> descs;
-    std::vector<uint8_t> texels;
-    for (size_t ii = 0; ii < scene->images.size(); ++ii) {
-        const Image &im = scene->images[ii];
-        // texels are stored in 8x4-texel tiles of 128 B (one cache line): the 2x2 bilinear footprint then touches
-        // 1.4 lines on average instead of 2 (k_shade is bound by L2-miss traffic); `pad` = tiles per row
-        DImage di;
-        di.offset = (uint32_t)(texels.size() / 4);
-        if (!sg->image_resident[ii]) {   // only ever half of a pair: lives in pair_texels, no shading record carries its id
-            di.width = di.height = di.pad = 0u;
-            descs.push_back(di);
-            continue;
-        }
-        di.width = im.width; di.height = im.height;
-        const uint32_t tx = (im.width + 7u) / 8u, ty = (im.height + 3u) / 4u;
-        di.pad = tx;
-        descs.push_back(di);
-        const size_t base = texels.size();
-        texels.resize(base + (size_t)tx * ty * 128u, 0);
-        for (uint32_t y = 0; y < im.height; ++y)
-            for (uint32_t x = 0; x < im.width; ++x)
-                memcpy(&texels[base + 4u * (((size_t)(y >> 2) * tx + (x >> 3)) * 32u + (y & 3u) * 8u + (x & 7u))], &im.rgba8[4u * ((size_t)y * im.width + x)], 4);
-    }
-    UP(images, descs)
-    UP(texels, texels)
-    UP(pair_images, pair_descs)
-    UP(pair_texels, pair_texels)
+    const std::vector<uint8_t> texels = tiled_atlas(*scene, pairs.image_resident, descs);
+    const std::vector<TriRec> recs = gpu_build ? std::vector<TriRec>() : shading_records(*scene, acc, pairs);
     std::vector<float> lut(256);
     for (int i = 0; i < 256; ++i) {
         const double c = (double)i / 255.0;
         lut[i] = (float)(c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4));
     }
-    UP(srgb_lut, lut)
-    if (!gpu_build) {
-        std::vector<float4> boxes(acc.nodes.size(), make_float4(0.f, 0.f, 0.f, 0.f));  // filled by the first refit
-        UP(node_lo, boxes)
-        UP(node_hi, boxes)
+    const std::vector<uint32_t> zero(1, 0u);
+
+    // the upload (the host vectors above outlive it: a failure destroys the scene, which waits for the device)
+    std::unique_ptr<lpt_scene_gpu, int (*)(lpt_scene_gpu *)> sg(new lpt_scene_gpu(), lpt_scene_gpu_destroy);
+    sg->dev = dev;
+    sg->pairs = std::move(pairs);
+    hipStream_t s = dev->stream;
+    if (gpu_build) {
+        TRY(dev_alloc(sg->tri_verts, sizeof(TriRec) * (size_t)n_tris));   // written by k_bake_instance
+    } else {   // the host-built tree; its boxes are filled by the first refit
+        DevTree &t = sg->tree;
+        t.n_nodes = (uint32_t)acc.nodes.size();
+        t.max_depth = acc.max_depth;
+        t.level_start = acc.level_start;
+        t.build_ms = acc.build_ms;
+        TRY(upload(t.nodes, acc.nodes, s));
+        TRY(upload(t.woop, acc.woop, s));
+        TRY(upload(t.leaf_prim, acc.leaf_prim, s));
+        const size_t box_bytes = sizeof(float4) * std::max<size_t>(t.n_nodes, 1u);
+        TRY(dev_alloc(t.node_lo, box_bytes));
+        TRY(dev_alloc(t.node_hi, box_bytes));
+        HIP_TRY(hipMemsetAsync(t.node_lo.get(), 0, box_bytes, s));
+        HIP_TRY(hipMemsetAsync(t.node_hi.get(), 0, box_bytes, s));
+        TRY(upload(sg->tri_verts, recs, s));
     }
-    UP(obj_verts, scene->vertices)
-    UP(obj_indices, scene->indices)
-    { std::vector<uint32_t> zero(1, 0u); UP(bad_flag, zero) }
-#undef UP
-    sg->inst_first = acc.inst_first; sg->inst_count = acc.inst_count; sg->level_start = acc.level_start;
+    TRY(upload(sg->materials, scene->materials, s));
+    TRY(upload(sg->lights, scene->lights, s));
+    TRY(upload(sg->images, descs, s));
+    TRY(upload(sg->texels, texels, s));
+    TRY(upload(sg->pair_images, sg->pairs.descs, s));
+    TRY(upload(sg->pair_texels, pair_texels, s));
+    TRY(upload(sg->srgb_lut, lut, s));
+    TRY(upload(sg->obj_verts, scene->vertices, s));
+    TRY(upload(sg->obj_indices, scene->indices, s));
+    TRY(upload(sg->bad_flag, zero, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    sg->inst_first = acc.inst_first; sg->inst_count = acc.inst_count;
     sg->instances = scene->instances;
     sg->n_entries = scene->entries.size(); sg->n_vertices = scene->vertices.size(); sg->n_indices = scene->indices.size();
-    hipError_t e = hipStreamSynchronize(s);  // host vectors die at scope exit
-    if (e != hipSuccess) { lpt_scene_gpu_destroy(sg); return fail(LPT_ERR_HIP, "scene upload failed: %s", hipGetErrorString(e)); }
+
     DScene &d = sg->d;
-    d.nodes = (const DNode8 *)sg->nodes;
-    // a stack entry holds the unvisited siblings below a node at depth 1..max_depth-1 (the root's own group has one
-    // member and is never pushed, the deepest nodes have no inner children): max_depth-1 entries are enough
-    d.stack_entries = acc.max_depth > 2u ? acc.max_depth - 1u : 1u;
     sg->max_abs = acc.max_abs;      // 0 on the GPU-build path: build_lbvh sets it from its bounds pass
     d.pad_abs = kScenePad * acc.max_abs;
     for (int a = 0; a < 3; ++a) { d.grid_lo[a] = acc.grid_lo[a]; d.grid_step[a] = acc.grid_step[a]; }   // (the GPU-build path: build_lbvh sets its own)
-    d.woop = (const float4 *)sg->woop;
-    d.leaf_prim = (const uint32_t *)sg->leaf_prim;
-    d.tri_verts = (const float4 *)sg->tri_verts;
-    d.materials = (const lpt_material *)sg->materials;
-    d.lights = (const lpt_light *)sg->lights;
-    d.texels = (const uint8_t *)sg->texels;
-    d.images = (const DImage *)sg->images;
-    d.srgb_lut = (const float *)sg->srgb_lut;
-    d.pair_texels = (const uint2 *)sg->pair_texels;
-    d.pair_images = (const DImage *)sg->pair_images;
-    d.n_pairs = (uint32_t)pair_descs.size();
+    d.tri_verts = as<const float4>(sg->tri_verts);
+    d.materials = as<const lpt_material>(sg->materials);
+    d.lights = as<const lpt_light>(sg->lights);
+    d.texels = as<const uint8_t>(sg->texels);
+    d.images = as<const DImage>(sg->images);
+    d.srgb_lut = as<const float>(sg->srgb_lut);
+    d.pair_texels = as<const uint2>(sg->pair_texels);
+    d.pair_images = as<const DImage>(sg->pair_images);
+    d.n_pairs = (uint32_t)sg->pairs.descs.size();
     d.n_tris = n_tris;
     d.n_materials = (uint32_t)scene->materials.size();
     d.n_lights = (uint32_t)scene->lights.size();
     d.n_images = (uint32_t)scene->images.size();
     sg->stats.triangles = d.n_tris;
-    sg->stats.nodes = (uint32_t)acc.nodes.size();
     sg->stats.node_bytes = (uint32_t)sizeof(Node8);
     sg->stats.tri_bytes = (uint32_t)sizeof(WoopTri);
-    sg->stats.max_depth = acc.max_depth;
-    sg->stats.build_ms = acc.build_ms;
     sg->stats.host_baked_triangles = gpu_build ? 0u : n_tris;
     sg->stats.texture_bytes_resident = (uint64_t)texels.size() + 8u * (uint64_t)pair_texels.size();
-    sg->stats.texture_pairs = (uint32_t)pair_descs.size();
-    if (gpu_build) {
-        // bake every instance on the device (fp32 transform, cofactor normals, binary64 Woop maps: bit-identical to the
-        // host bake), then build the tree there
-        void *woop_prim = nullptr;
-        e = hipMalloc(&woop_prim, sizeof(WoopTri) * (size_t)n_tris);
-        if (e != hipSuccess) { lpt_scene_gpu_destroy(sg); return fail(LPT_ERR_HIP, "scene upload failed: %s", hipGetErrorString(e)); }
-        for (size_t i = 0; i < scene->instances.size() && st == LPT_OK; ++i) {
-            const uint32_t first = sg->inst_first[i], cnt = sg->inst_count[i];
-            if (!cnt) continue;
-            BakeArgs a;
-            st = make_bake_args(sg, *scene, i, first, cnt, a);
-            if (st == LPT_OK)
-                hipLaunchKernelGGL(k_bake_instance, dim3(div_up(cnt, 256u)), dim3(256), 0, s, a, (const float4 *)sg->obj_verts, (const uint32_t *)sg->obj_indices,
-                                   (float4 *)sg->tri_verts, (float4 *)woop_prim, (uint32_t *)sg->bad_flag);
-        }
-        uint32_t bad = 0;
-        if (st == LPT_OK) {
-            e = hipMemcpyAsync(&bad, sg->bad_flag, sizeof bad, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) st = fail(LPT_ERR_HIP, "scene upload failed: %s", hipGetErrorString(e));
-            else if (bad) st = fail(LPT_ERR_ACCEL_BUILD, "non-finite vertex in a baked triangle");
-        }
-        if (st == LPT_OK) st = build_lbvh(sg, n_tris, nullptr, (const float4 *)woop_prim, s);
-        hipFree(woop_prim);
-        if (st != LPT_OK) { lpt_scene_gpu_destroy(sg); return st; }
-        d.stack_entries = sg->stats.max_depth > 2u ? sg->stats.max_depth - 1u : 1u;
+    sg->stats.texture_pairs = d.n_pairs;
+
+    if (gpu_build) {   // bake every instance on the device, then build the tree there
+        DevMem woop_prim;
+        TRY(dev_alloc(woop_prim, sizeof(WoopTri) * (size_t)n_tris));
+        TRY(bake_instances(sg.get(), *scene, every_instance(*scene), woop_prim.get()));
+        TRY(build_lbvh(sg.get(), n_tris, woop_prim.get(), s, sg->tree));
     }
+    bind_view(sg.get());
     sg->stats.upload_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_upload).count();
-    *out = sg;
+    *out = sg.release();
     return LPT_OK;
 }
 
@@ -824,62 +897,31 @@ int lpt_scene_gpu_stats(const lpt_scene_gpu *sg, lpt_accel_stats *out) {
 // must be the ones that were uploaded; anything else needs lpt_scene_upload again.
 int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, uint32_t *out_rebaked) {
     if (!sg || !scene) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_update_instances: null");
-    if (scene->instances.size() != sg->instances.size() || scene->entries.size() != sg->n_entries ||
-        scene->vertices.size() != sg->n_vertices || scene->indices.size() != sg->n_indices)
-        return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_update_instances: the scene's meshes / instance list changed since the upload; upload again");
+    TRY(check_same_layout(sg, *scene, "lpt_scene_gpu_update_instances"));
     HIP_TRY(hipSetDevice(sg->dev->ordinal));
-    hipStream_t s = sg->dev->stream;
     // renderers trace on their own streams and raytrace() is asynchronous: frames still in flight read the triangles and
     // nodes this call rewrites in place, so wait for every stream of the device first
-    { const int fst = flush_device(sg->dev); if (fst != LPT_OK) return fst; }
+    TRY(flush_device(sg->dev));
     HIP_TRY(hipDeviceSynchronize());
-    uint32_t changed = 0;
-    // the re-baked triangles' Woop maps in prim order; a place-driven scatter then takes them to every place a triangle has in the tree (a split triangle has several)
-    void *woop_prim = nullptr;
-    const uint32_t n_places = kNodeTris * sg->stats.nodes;
-    for (size_t i = 0; i < scene->instances.size(); ++i) {
-        const lpt_instance &now = scene->instances[i];
-        lpt_instance &was = sg->instances[i];
-        if (now.blas_index != was.blas_index)
-            return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_update_instances: instance %zu refers to another mesh; upload again", i);
-        if (memcmp(&now, &was, sizeof now) == 0) continue;
-        const uint32_t first = sg->inst_first[i], n = sg->inst_count[i];
-        if (n) {
-            // re-bake on the device: the object-space mesh is resident, only the transform travels
-            BakeArgs a;
-            int bst = make_bake_args(sg, *scene, i, first, n, a);
-            if (bst != LPT_OK) { if (woop_prim) hipFree(woop_prim); return bst; }
-            if (!woop_prim) HIP_TRY(hipMalloc(&woop_prim, sizeof(WoopTri) * (size_t)std::max(sg->stats.triangles, 1u)));
-            hipLaunchKernelGGL(k_bake_instance, dim3(div_up(n, 256u)), dim3(256), 0, s, a, (const float4 *)sg->obj_verts, (const uint32_t *)sg->obj_indices,
-                               (float4 *)sg->tri_verts, (float4 *)woop_prim, (uint32_t *)sg->bad_flag);
-            hipLaunchKernelGGL(k_lbvh_scatter_woop, dim3(div_up(n_places, 256u)), dim3(256), 0, s, (const float4 *)woop_prim, (float4 *)sg->woop, (const uint32_t *)sg->leaf_prim, n_places, first, n);
+    std::vector<uint32_t> changed;
+    for (size_t i = 0; i < scene->instances.size(); ++i)
+        if (memcmp(&scene->instances[i], &sg->instances[i], sizeof(lpt_instance)) != 0) changed.push_back((uint32_t)i);
+    if (!changed.empty()) {
+        // re-bake on the device (the object-space meshes are resident, only the transforms travel); a place-driven scatter then takes the new
+        // Woop maps to every place a triangle has in the tree (a split triangle has several)
+        DevMem woop_prim;
+        TRY(dev_alloc(woop_prim, sizeof(WoopTri) * (size_t)std::max(sg->stats.triangles, 1u)));
+        const int st = bake_instances(sg, *scene, changed, woop_prim.get());
+        if (st == LPT_ERR_INVALID_ARG) return st;   // found before anything was baked
+        // recorded as baked even when a vertex was not finite: the next valid edit of the instance re-bakes it
+        for (uint32_t i : changed) {
+            sg->instances[i] = scene->instances[i];
+            if (sg->inst_count[i]) scatter_woop(sg->tree, woop_prim.get(), sg->inst_first[i], sg->inst_count[i], sg->dev->stream);
         }
-        was = now;
-        ++changed;
+        if (st != LPT_OK) return st;
+        if (sg->stats.triangles) TRY(refit(sg));
     }
-    if (changed) {
-        uint32_t bad = 0;
-        HIP_TRY(hipMemcpyAsync(&bad, sg->bad_flag, sizeof bad, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (woop_prim) { hipFree(woop_prim); woop_prim = nullptr; }
-        if (bad) {
-            HIP_TRY(hipMemsetAsync(sg->bad_flag, 0, sizeof bad, s));
-            return fail(LPT_ERR_ACCEL_BUILD, "non-finite vertex in a re-baked instance");
-        }
-    }
-    if (changed && sg->stats.triangles) {
-        // the moved triangles' bounds first: the padding's scene-wide part follows the scene's largest coordinate (ANY growth counts — ADVICE r05 —; it never shrinks) and
-        // the node origins sit on a grid over the scene — both are inputs of the refit, which then runs once
-        float blo[3], bhi[3];
-        { const int bst = scene_bounds_and_grid(sg, sg->stats.triangles, s, blo, bhi, true); if (bst != LPT_OK) return bst; }
-        for (size_t l = sg->level_start.size() - 1; l-- > 0;) {
-            const uint32_t a = sg->level_start[l], b = sg->level_start[l + 1];
-            if (b > a) hipLaunchKernelGGL(k_refit_level, dim3(div_up(b - a, 64u)), dim3(64), 0, s, sg->d, (uint4 *)sg->nodes, (float4 *)sg->node_lo, (float4 *)sg->node_hi, a, b);
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    if (out_rebaked) *out_rebaked = changed;
+    if (out_rebaked) *out_rebaked = (uint32_t)changed.size();
     return LPT_OK;
 }
 
@@ -888,67 +930,29 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
 // lpt_scene_gpu_update_instances; scenes of fewer than 16 triangles are refitted instead.
 int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
     if (!sg || !scene) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_rebuild: null");
-    if (scene->instances.size() != sg->instances.size() || scene->entries.size() != sg->n_entries ||
-        scene->vertices.size() != sg->n_vertices || scene->indices.size() != sg->n_indices)
-        return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_rebuild: the scene's meshes / instance list changed since the upload; upload again");
+    TRY(check_same_layout(sg, *scene, "lpt_scene_gpu_rebuild"));
     const uint32_t n = sg->stats.triangles;
     if (n < 16u) return lpt_scene_gpu_update_instances(sg, scene, nullptr);
     HIP_TRY(hipSetDevice(sg->dev->ordinal));
-    hipStream_t s = sg->dev->stream;
-    { const int fst = flush_device(sg->dev); if (fst != LPT_OK) return fst; }
+    TRY(flush_device(sg->dev));
     HIP_TRY(hipDeviceSynchronize());  // frames in flight on the renderers' streams still read what is rebuilt here
-    void *woop_prim = nullptr;
-    HIP_TRY(hipMalloc(&woop_prim, sizeof(WoopTri) * (size_t)n));
-    for (size_t i = 0; i < scene->instances.size(); ++i) {
-        if (scene->instances[i].blas_index != sg->instances[i].blas_index) { hipFree(woop_prim); return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_rebuild: instance %zu refers to another mesh; upload again", i); }
-        const uint32_t first = sg->inst_first[i], cnt = sg->inst_count[i];
-        if (!cnt) continue;
-        BakeArgs a;
-        int bst = make_bake_args(sg, *scene, i, first, cnt, a);
-        if (bst != LPT_OK) { hipFree(woop_prim); return bst; }
-        hipLaunchKernelGGL(k_bake_instance, dim3(div_up(cnt, 256u)), dim3(256), 0, s, a, (const float4 *)sg->obj_verts, (const uint32_t *)sg->obj_indices,
-                           (float4 *)sg->tri_verts, (float4 *)woop_prim, (uint32_t *)sg->bad_flag);
+    DevMem woop_prim;
+    TRY(dev_alloc(woop_prim, sizeof(WoopTri) * (size_t)n));
+    TRY(bake_instances(sg, *scene, every_instance(*scene), woop_prim.get()));
+    // the new tree replaces the old one only when its build succeeds: bound renderers and later updates never see freed memory
+    DevTree t;
+    const int st = build_lbvh(sg, n, woop_prim.get(), sg->dev->stream, t);
+    if (st == LPT_OK) {
+        sg->tree = std::move(t);
+        bind_view(sg);
+    } else {
+        // the shading records were re-baked in place: put the old tree in step with them as an update does (new Woop maps into the old leaf
+        // order, boxes refitted, topology kept); the refit also replaces the grid build_lbvh had set for the new tree
+        scatter_woop(sg->tree, woop_prim.get(), 0u, n, sg->dev->stream);
+        refit(sg);
     }
-    uint32_t bad = 0;
-    hipError_t e = hipMemcpyAsync(&bad, sg->bad_flag, sizeof bad, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess || bad) {
-        hipMemsetAsync(sg->bad_flag, 0, sizeof bad, s);
-        hipFree(woop_prim);
-        return e != hipSuccess ? fail(LPT_ERR_HIP, "lpt_scene_gpu_rebuild: %s", hipGetErrorString(e)) : fail(LPT_ERR_ACCEL_BUILD, "non-finite vertex in a re-baked instance");
-    }
-    // build into NEW buffers and swap them in only on success: a failed build (out of memory, node budget) leaves the
-    // scene exactly as it was, so bound renderers and later updates never see freed memory
-    void **slots[] = {&sg->nodes, &sg->woop, &sg->leaf_prim, &sg->node_lo, &sg->node_hi};
-    void *old[5];
-    for (int k = 0; k < 5; ++k) { old[k] = *slots[k]; *slots[k] = nullptr; }
-    const DScene old_d = sg->d;
-    const lpt_accel_stats old_stats = sg->stats;
-    const std::vector<uint32_t> old_levels = sg->level_start;
-    int st = build_lbvh(sg, n, nullptr, (const float4 *)woop_prim, s);
-    if (st != LPT_OK) {
-        for (int k = 0; k < 5; ++k) { if (*slots[k]) hipFree(*slots[k]); *slots[k] = old[k]; }
-        sg->d = old_d; sg->stats = old_stats; sg->level_start = old_levels;
-        // the shading records were re-baked in place: put the old tree back in step with them (new Woop maps into the
-        // old leaf order, boxes refitted; topology kept)
-        hipLaunchKernelGGL(k_lbvh_scatter_woop, dim3(div_up(kNodeTris * sg->stats.nodes, 256u)), dim3(256), 0, s, (const float4 *)woop_prim, (float4 *)sg->woop, (const uint32_t *)sg->leaf_prim,
-                           kNodeTris * sg->stats.nodes, 0u, n);
-        if (sg->stats.triangles) { float blo[3], bhi[3]; scene_bounds_and_grid(sg, n, s, blo, bhi, true); }   // (build_lbvh had set the NEW scene's grid in sg->d before old_d came back)
-        if (sg->stats.triangles)
-            for (size_t l = sg->level_start.size() - 1; l-- > 0;) {
-                const uint32_t a = sg->level_start[l], b = sg->level_start[l + 1];
-                if (b > a) hipLaunchKernelGGL(k_refit_level, dim3(div_up(b - a, 64u)), dim3(64), 0, s, sg->d, (uint4 *)sg->nodes, (float4 *)sg->node_lo, (float4 *)sg->node_hi, a, b);
-            }
-        hipStreamSynchronize(s);
-        hipFree(woop_prim);
-        sg->instances = scene->instances;  // what is baked now
-        return st;
-    }
-    hipFree(woop_prim);
-    for (int k = 0; k < 5; ++k) if (old[k]) hipFree(old[k]);
-    sg->d.stack_entries = sg->stats.max_depth > 2u ? sg->stats.max_depth - 1u : 1u;
-    sg->instances = scene->instances;
-    return LPT_OK;
+    sg->instances = scene->instances;  // what is baked now
+    return st;
 }
 
 // ============================================================================ ProbeGPU

@@ -176,6 +176,7 @@ def test_lifecycle_does_not_leak_device_memory(device, cornell_glb):
                 r.set_blit_mode(lp.BlitMode.Pahtrace)
             assert r.read_pixels().shape == (h, w, 4)
         sg.update_instances(scene)
+        sg.rebuild(scene)
         r.close(); pr.close(); sg.close()
 
     for k in range(12):                                  # every variant once: the runtime's own pools are warm

@@ -97,6 +97,53 @@ def test_refit_rejects_a_changed_instance_list(device, cornell_glb):
     sg.close()
 
 
+def test_non_finite_transform_raises_and_the_scene_recovers(device, cornell_glb):
+    """A NaN / inf transform is an AccelBuild error from update_instances, rebuild and a GPU-built upload (the bake checks every vertex before
+    any kernel reads the triangles); the flag is reset, so the next valid edit of the same instance works: the scene then traces and renders
+    like a fresh upload"""
+    scene = lp.Scene()
+    lp.loaders.load_gltf(cornell_glb, scene)
+    scene.set_light(0, T.cornell_light())
+    sg = lp.SceneGPU.new_from_scene(scene, device)
+    idx = scene.counts().instances - 1
+    base = scene.instances[idx]["model_to_world"].reshape(-1).copy()
+    bad = base.copy()
+    bad[12], bad[13] = np.nan, np.inf
+    rng = np.random.default_rng(11)
+    o = np.zeros((20000, 4), np.float32); d = np.zeros((20000, 4), np.float32)
+    o[:, :3] = rng.uniform(-2.5, 2.5, (20000, 3))
+    v = rng.normal(size=(20000, 3)); d[:, :3] = v / np.linalg.norm(v, axis=1, keepdims=True)
+
+    def raises_accel_build(call):
+        with pytest.raises(lp.Error) as e:
+            call()
+        assert e.value.kind == "AccelBuild"
+
+    def same_as_fresh():
+        fresh = lp.SceneGPU.new_from_scene(scene, device)
+        assert sg.trace_closest(o, d).tobytes() == fresh.trace_closest(o, d).tobytes()
+        img, c = _render(device, sg, 96, 96, 3, 1)
+        ref, c_ref = _render(device, fresh, 96, 96, 3, 1)
+        assert img.tobytes() == ref.tobytes() and (c.closest, c.shadow) == (c_ref.closest, c_ref.shadow)
+        fresh.close()
+
+    scene.set_instance_transform(idx, bad)
+    raises_accel_build(lambda: sg.update_instances(scene))
+    scene.set_instance_transform(idx, (_trs(0.5, (0.8, 0.9, 0.6), 0.8).reshape(4, 4).T @ base.reshape(4, 4).T).T.astype(np.float32).reshape(-1))
+    assert sg.update_instances(scene) == 1                       # the failed edit was recorded: the valid one re-bakes the instance
+    same_as_fresh()
+
+    scene.set_instance_transform(idx, bad)
+    raises_accel_build(lambda: sg.rebuild(scene))
+    scene.set_instance_transform(idx, (_trs(-0.3, (-0.9, 0.0, -0.5)).reshape(4, 4).T @ base.reshape(4, 4).T).T.astype(np.float32).reshape(-1))
+    sg.rebuild(scene)
+    assert sg.update_instances(scene) == 0
+    same_as_fresh()
+
+    scene.set_instance_transform(idx, bad)
+    raises_accel_build(lambda: lp.SceneGPU.new_from_scene(scene, device, gpu_build=True))
+    sg.close()
+
 def test_refit_large_scene_statue_moves(device):
     """atrium: move one ~7k-triangle instance; refit == fresh upload on 100k random rays and a 480x270 frame"""
     desc = scenes.synthetic_atrium(textures=False)
