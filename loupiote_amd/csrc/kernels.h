@@ -2078,13 +2078,15 @@ __global__ __launch_bounds__(kBlock) void k_temporal(int W, int H, const float4 
         const f3 il = mk3(L.x / a.x, L.y / a.y, L.z / a.z);
         const float lm = lum(il);
         const float2 mo = motion[i];
-        const int mx = (int)floorf(((float)x + 0.5f) + mo.x * (float)W);
-        const int my = (int)floorf(((float)y + 0.5f) + mo.y * (float)H);
+        // the reprojected position is tested against [0, W) x [0, H) before any conversion: a NaN or huge motion is outside
+        // (v_cvt_i32_f32 would turn NaN into 0 and clamp the rest into range); inside, floor() is the pixel (SPEC §15.2)
+        const float fx = ((float)x + 0.5f) + mo.x * (float)W;
+        const float fy = ((float)y + 0.5f) + mo.y * (float)H;
         uint32_t hn = 1u;
         f3 col = il;
         float m1 = lm, m2 = lm * lm;
-        if (mx >= 0 && my >= 0 && mx < W && my < H) {
-            const size_t j = (size_t)my * W + mx;
+        if (fx >= 0.0f && fy >= 0.0f && fx < (float)W && fy < (float)H) {
+            const size_t j = (size_t)floorf(fy) * W + (size_t)floorf(fx);
             const uint4 gp = g_prev[j];
             const uint32_t hp = hist_prev[j];
             const float zc = __uint_as_float(g.y), zp = __uint_as_float(gp.y);

@@ -982,6 +982,7 @@ struct orc_denoiser {
     uint32_t w, h; int cur;
     uint32_t *gbuf[2]; float *rad[2]; float *mom[2]; uint32_t *hist[2];
     float *motion, *temp, *lsum;
+    uint32_t *gbuf_in; /* the rendered frame's G-buffer, handed to orc_denoise_filter like any other input */
     cam_t prev_cam;
 };
 
@@ -994,6 +995,7 @@ orc_denoiser *orc_denoiser_create(uint32_t w, uint32_t h) {
         d->mom[k] = (float *)calloc(n * 2, 4); d->hist[k] = (uint32_t *)calloc(n, 4);
     }
     d->motion = (float *)calloc(n * 2, 4); d->temp = (float *)calloc(n * 4, 4); d->lsum = (float *)calloc(n * 4, 4);
+    d->gbuf_in = (uint32_t *)calloc(n * 4, 4);
     /* prev_model_to_screen starts as the identity (renderer.rs:319) */
     d->prev_cam.origin = V3(0, 0, 0); d->prev_cam.right = V3(1, 0, 0); d->prev_cam.up = V3(0, 1, 0); d->prev_cam.fwd = V3(0, 0, 1);
     d->prev_cam.ax = d->prev_cam.ay = 1.0f;
@@ -1002,7 +1004,7 @@ orc_denoiser *orc_denoiser_create(uint32_t w, uint32_t h) {
 void orc_denoiser_destroy(orc_denoiser *d) {
     if (!d) return;
     for (int k = 0; k < 2; ++k) { free(d->gbuf[k]); free(d->rad[k]); free(d->mom[k]); free(d->hist[k]); }
-    free(d->motion); free(d->temp); free(d->lsum); free(d);
+    free(d->motion); free(d->temp); free(d->lsum); free(d->gbuf_in); free(d);
 }
 void orc_denoiser_read(const orc_denoiser *d, uint32_t *gbuf_cur, float *motion, float *rad_cur, uint32_t *hist_cur) {
     size_t n = (size_t)d->w * d->h;
@@ -1011,6 +1013,7 @@ void orc_denoiser_read(const orc_denoiser *d, uint32_t *gbuf_cur, float *motion,
     if (rad_cur) memcpy(rad_cur, d->rad[d->cur], n * 16);
     if (hist_cur) memcpy(hist_cur, d->hist[d->cur], n * 4);
 }
+void orc_denoiser_read_moments(const orc_denoiser *d, float *mom_cur) { memcpy(mom_cur, d->mom[d->cur], (size_t)d->w * d->h * 8); }
 
 static inline uint32_t oct_encode(v3 n) {
     float l1 = (fabsf(n.x) + fabsf(n.y)) + fabsf(n.z);
@@ -1056,9 +1059,9 @@ static inline int project(const cam_t *c, v3 P, float *u, float *v) {
 }
 static inline float pow128(float x) { x = x * x; x = x * x; x = x * x; x = x * x; x = x * x; x = x * x; x = x * x; return x; }
 
-static void atrous_pass(const orc_denoiser *d, const uint32_t *gb, const float *in, float *out, int step) {
+void orc_atrous_pass(uint32_t w, uint32_t h, const uint32_t *gb, const float *in, float *out, int step) {
     static const float kw[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
-    const int W = (int)d->w, H = (int)d->h;
+    const int W = (int)w, H = (int)h;
     for (int y = 0; y < H; ++y)
         for (int x = 0; x < W; ++x) {
             size_t i = (size_t)y * W + x;
@@ -1099,21 +1102,34 @@ static void atrous_pass(const orc_denoiser *d, const uint32_t *gb, const float *
 void orc_denoise_frame(orc_denoiser *d, const orc_scene *s, const orc_render_params *p, int mode, float *out_main) {
     const int W = (int)d->w, H = (int)d->h;
     cam_t cam = make_camera(p);
-    d->cur = 1 - d->cur; /* asvgf.start() (renderer.rs:467) */
-    const int cur = d->cur, prv = 1 - d->cur;
     /* 1. path trace one sample per pixel; the primary pass also writes G-buffer and motion */
     for (int y = 0; y < H; ++y)
         for (int x = 0; x < W; ++x) {
             size_t i = (size_t)y * W + x;
             primary_t pr; memset(&pr, 0, sizeof pr);
             trace_sample(s, p, &cam, (uint32_t)x, (uint32_t)y, p->seed_counter, d->lsum + 4 * i, NULL, &pr);
-            uint32_t *g = d->gbuf[cur] + 4 * i;
+            uint32_t *g = d->gbuf_in + 4 * i;
             g[0] = pr.prim; memcpy(&g[1], &pr.depth, 4); g[2] = oct_encode(pr.n); g[3] = pack_albedo(pr.albedo);
             float mu = 0.0f, mv = 0.0f, cu, cv, pu, pv;
             if (pr.has_P && project(&cam, pr.P, &cu, &cv) && project(&d->prev_cam, pr.P, &pu, &pv)) { mu = pu - cu; mv = pv - cv; }
             d->motion[2 * i] = mu; d->motion[2 * i + 1] = mv;
         }
-    /* 2. TemporalAccumulationPass (asvgf.rs:245-247): nearest reprojection, consistency test, moments, history */
+    /* 2. the passes over the frame's inputs */
+    orc_denoise_filter(d, d->lsum, d->gbuf_in, d->motion, mode, out_main);
+    d->prev_cam = cam; /* prev_model_to_screen = P * V^-1 (renderer.rs:542-546) */
+}
+
+/* the passes of one frame over given per-pixel inputs (noisy radiance float4, G-buffer uint4, motion float2): start()
+ * flips the ping-pong, then temporal -> copy -> a-trous x4 -> composite.  The inputs may be the denoiser's own buffers. */
+void orc_denoise_filter(orc_denoiser *d, const float *noisy, const uint32_t *gbuf, const float *motion, int mode, float *out_main) {
+    const int W = (int)d->w, H = (int)d->h;
+    const size_t n = (size_t)W * H;
+    d->cur = 1 - d->cur; /* asvgf.start() (renderer.rs:467) */
+    const int cur = d->cur, prv = 1 - d->cur;
+    if (noisy != d->lsum) memcpy(d->lsum, noisy, n * 16);
+    memcpy(d->gbuf[cur], gbuf, n * 16);
+    if (motion != d->motion) memcpy(d->motion, motion, n * 8);
+    /* TemporalAccumulationPass (asvgf.rs:245-247): nearest reprojection, consistency test, moments, history */
     for (int y = 0; y < H; ++y)
         for (int x = 0; x < W; ++x) {
             size_t i = (size_t)y * W + x;
@@ -1122,12 +1138,13 @@ void orc_denoise_frame(orc_denoiser *d, const orc_scene *s, const orc_render_par
             const float *L = d->lsum + 4 * i;
             v3 il = V3(L[0] / a.x, L[1] / a.y, L[2] / a.z);
             float lm = lum3(il);
-            int mx = (int)floorf(((float)x + 0.5f) + d->motion[2 * i] * (float)W);
-            int my = (int)floorf(((float)y + 0.5f) + d->motion[2 * i + 1] * (float)H);
+            /* tested against [0, W) x [0, H) before the conversion, so a NaN or huge motion is outside (SPEC §15.2) */
+            float fx = ((float)x + 0.5f) + d->motion[2 * i] * (float)W;
+            float fy = ((float)y + 0.5f) + d->motion[2 * i + 1] * (float)H;
             uint32_t hn = 1u;
             v3 col = il; float m1 = lm, m2 = lm * lm;
-            if (mx >= 0 && my >= 0 && mx < W && my < H) {
-                size_t j = (size_t)my * W + mx;
+            if (fx >= 0.0f && fy >= 0.0f && fx < (float)W && fy < (float)H) {
+                size_t j = (size_t)floorf(fy) * W + (size_t)floorf(fx);
                 const uint32_t *gp = d->gbuf[prv] + 4 * j;
                 uint32_t hp = d->hist[prv][j];
                 float zc, zp; memcpy(&zc, &g[1], 4); memcpy(&zp, &gp[1], 4);
@@ -1147,15 +1164,14 @@ void orc_denoise_frame(orc_denoiser *d, const orc_scene *s, const orc_render_par
             rc[0] = col.x; rc[1] = col.y; rc[2] = col.z; rc[3] = var;
             d->mom[cur][2 * i] = m1; d->mom[cur][2 * i + 1] = m2; d->hist[cur][i] = hn;
         }
-    /* 3. copy -> a-trous x4 (steps 1,2,4,8; main <-> temp, result in temp) -> composite (asvgf.rs:257-290) */
-    size_t n = (size_t)W * H;
+    /* copy -> a-trous x4 (steps 1,2,4,8; main <-> temp, result in temp) -> composite (asvgf.rs:257-290) */
     const float *result = d->rad[cur];
     if (mode == 1) {
         memcpy(d->temp, d->rad[cur], n * 16);
-        atrous_pass(d, d->gbuf[cur], d->temp, out_main, 1);
-        atrous_pass(d, d->gbuf[cur], out_main, d->temp, 2);
-        atrous_pass(d, d->gbuf[cur], d->temp, out_main, 4);
-        atrous_pass(d, d->gbuf[cur], out_main, d->temp, 8);
+        orc_atrous_pass(d->w, d->h, d->gbuf[cur], d->temp, out_main, 1);
+        orc_atrous_pass(d->w, d->h, d->gbuf[cur], out_main, d->temp, 2);
+        orc_atrous_pass(d->w, d->h, d->gbuf[cur], d->temp, out_main, 4);
+        orc_atrous_pass(d->w, d->h, d->gbuf[cur], out_main, d->temp, 8);
         result = d->temp;
     }
     for (size_t i = 0; i < n; ++i) { /* CompositingPass: re-modulate with the primary albedo */
@@ -1163,5 +1179,4 @@ void orc_denoise_frame(orc_denoiser *d, const orc_scene *s, const orc_render_par
         out_main[4 * i] = result[4 * i] * a.x; out_main[4 * i + 1] = result[4 * i + 1] * a.y; out_main[4 * i + 2] = result[4 * i + 2] * a.z;
         out_main[4 * i + 3] = 1.0f;
     }
-    d->prev_cam = cam; /* prev_model_to_screen = P * V^-1 (renderer.rs:542-546) */
 }

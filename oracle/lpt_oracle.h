@@ -91,7 +91,13 @@ orc_denoiser *orc_denoiser_create(uint32_t w, uint32_t h);
 void orc_denoiser_destroy(orc_denoiser *d);
 /* one raytrace() call: mode 1 = DenoisedPathrace, 2 = Temporal; uses p->view, p->seed_counter (frames ignored) */
 void orc_denoise_frame(orc_denoiser *d, const orc_scene *s, const orc_render_params *p, int mode, float *out_main);
+/* the passes of one frame (start(), temporal, a-trous x4 in mode 1, composite) over given inputs: noisy = w*h*4 floats
+ * (the frame's sample radiance), gbuf = w*h*4 words, motion = w*h*2 floats; orc_denoise_frame renders them, then calls this */
+void orc_denoise_filter(orc_denoiser *d, const float *noisy, const uint32_t *gbuf, const float *motion, int mode, float *out_main);
 void orc_denoiser_read(const orc_denoiser *d, uint32_t *gbuf_cur, float *motion, float *rad_cur, uint32_t *hist_cur);
+void orc_denoiser_read_moments(const orc_denoiser *d, float *mom_cur);   /* w*h*2 floats: first / second luminance moment */
+/* one a-trous pass (SPEC §15.3) at tap spacing `step` over a w*h frame: in, out = w*h*4 floats (rgb, variance) */
+void orc_atrous_pass(uint32_t w, uint32_t h, const uint32_t *gbuf, const float *in, float *out, int step);
 
 /* ---- known-answer surfaces ------------------------------------------------- */
 uint32_t orc_pcg_hash(uint32_t v);

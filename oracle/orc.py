@@ -85,6 +85,9 @@ def lib(path=None):
         L.orc_denoiser_destroy.argtypes = [vp]
         L.orc_denoise_frame.argtypes = [vp, vp, C.POINTER(RenderParams), C.c_int, vp]
         L.orc_denoiser_read.argtypes = [vp, vp, vp, vp, vp]
+        L.orc_denoise_filter.argtypes = [vp, vp, vp, vp, C.c_int, vp]
+        L.orc_denoiser_read_moments.argtypes = [vp, vp]
+        L.orc_atrous_pass.argtypes = [u32, u32, vp, vp, vp, C.c_int]
         L.orc_resolve.argtypes = [vp, u32, vp]
         L.orc_tonemap.argtypes = [vp, u32, vp]
         L.orc_pcg_hash.restype = u32
@@ -199,9 +202,10 @@ class OracleScene:
 
 
 class Denoiser:
-    """BlitMode::DenoisedPathrace (mode 1) / Temporal (mode 2) frame sequence on the oracle (SPEC §15)."""
+    """BlitMode::DenoisedPathrace (mode 1) / Temporal (mode 2) frame sequence on the oracle (SPEC §15).  `frame` renders the
+    inputs from `scene`; `filter` takes them as given (scene may then be None)."""
 
-    def __init__(self, scene, width, height, vfov, max_bounces, user_seed=0):
+    def __init__(self, scene, width, height, vfov=0.0, max_bounces=0, user_seed=0):
         self.scene, self.w, self.h = scene, width, height
         self.vfov, self.bounces, self.user_seed = vfov, max_bounces, user_seed
         self.seed_counter = 0
@@ -226,11 +230,37 @@ class Denoiser:
         self.seed_counter += self.bounces
         return out
 
+    def filter(self, noisy, gbuf, motion, mode=1):
+        """one frame's passes over given inputs: noisy (h, w, 4) float32, gbuf (h, w, 4) uint32, motion (h, w, 2) float32;
+        returns the main target (h, w, 4)"""
+        n = self.w * self.h
+        noisy, gbuf, motion = (np.ascontiguousarray(a, dt) for a, dt in ((noisy, np.float32), (gbuf, np.uint32), (motion, np.float32)))
+        if noisy.size != 4 * n or gbuf.size != 4 * n or motion.size != 2 * n:
+            raise ValueError("Denoiser.filter: inputs must hold %d pixels" % n)
+        out = np.zeros((self.h, self.w, 4), np.float32)
+        lib().orc_denoise_filter(self.h_, _p(noisy), _p(gbuf), _p(motion), int(mode), _p(out))
+        return out
+
+    def read_moments(self):
+        m = np.zeros((self.h, self.w, 2), np.float32)
+        lib().orc_denoiser_read_moments(self.h_, _p(m))
+        return m
+
     def read(self):
         g, m = np.zeros((self.h, self.w, 4), np.uint32), np.zeros((self.h, self.w, 2), np.float32)
         rad, hist = np.zeros((self.h, self.w, 4), np.float32), np.zeros((self.h, self.w), np.uint32)
         lib().orc_denoiser_read(self.h_, _p(g), _p(m), _p(rad), _p(hist))
         return g, m, rad, hist
+
+
+def atrous_pass(gbuf, rad, step):
+    """one a-trous pass (SPEC §15.3) at tap spacing `step`: gbuf (h, w, 4) uint32, rad (h, w, 4) float32 -> (h, w, 4)"""
+    g, r = np.ascontiguousarray(gbuf, np.uint32), np.ascontiguousarray(rad, np.float32)
+    if g.shape != r.shape or g.ndim != 3 or g.shape[2] != 4:
+        raise ValueError("atrous_pass: gbuf and rad must both be (h, w, 4)")
+    out = np.zeros_like(r)
+    lib().orc_atrous_pass(g.shape[1], g.shape[0], _p(g), _p(r), _p(out), int(step))
+    return out
 
 
 def resolve(accum):
