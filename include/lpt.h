@@ -583,8 +583,12 @@ typedef enum lpt_experiment {
                                      * (dense tiles, a multiple of four samples); 0 = always one sample of an 8x8-pixel patch */
     LPT_EXP_SPLIT_RAYS = 10,        /* a batch above this many rays that would still fit one wavefront leaves as two, on the renderer's lanes (default
                                      * 3 000 000; 0: never split below LPT_OPT_WAVEFRONT_RAYS) */
-    LPT_EXP_BUDGET_SPLIT = 11       /* 1: the tail in place / the step budget also apply to the pieces of a cut batch (default 0: only to submissions that leave
+    LPT_EXP_BUDGET_SPLIT = 11,      /* 1: the tail in place / the step budget also apply to the pieces of a cut batch (default 0: only to submissions that leave
                                      * as one wavefront — LPT_EXP_BUDGET_RAYS alone does not turn them on for the pieces) */
+    LPT_EXP_LANE_PHASE = 12         /* how the pieces of a cut batch on the renderer's lanes are ordered against each other (stream events, no host waits):
+                                     * 0 = free (both lanes run the same launch sequence in step), 1 (default) = offset start (a lane's first launch waits for
+                                     * the previous lane's primary traversal), 2 = alternating traversal (one piece's traversal launch at a time, the
+                                     * other pieces shade beside it) */
 } lpt_experiment;
 int lpt_renderer_set_option(lpt_renderer *r, int option, uint64_t value);
 int lpt_renderer_get_option(const lpt_renderer *r, int option, uint64_t *value);

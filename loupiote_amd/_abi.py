@@ -24,7 +24,7 @@ COMM_ID_BYTES = 128
 OPT_EXPERIMENT_BASE = 256
 OPTIONS = {"packet_primary": 1, "wavefront_rays": 2, "path_rays": 3, "coop_rays": 4, "tail_lanes": 5}
 EXPERIMENTS = {"pipe_rays": 0, "refill": 1, "trace_waves_per_cu": 2, "shade_blocks_per_cu": 3, "path_waves_per_cu": 4, "path_refill": 5, "occ_cell_milli": 6,
-               "step_budget": 7, "budget_rays": 8, "packet_quads": 9, "split_rays": 10, "budget_split": 11}
+               "step_budget": 7, "budget_rays": 8, "packet_quads": 9, "split_rays": 10, "budget_split": 11, "lane_phase": 12}
 OPTIONS.update({k: OPT_EXPERIMENT_BASE + v for k, v in EXPERIMENTS.items()})
 EXCHANGE_GATHER_TILES = 0
 HOST_FRAME_HOST_ONLY = 1

@@ -19,6 +19,7 @@
 #include <map>
 #include <memory>
 #include <cstdlib>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <numeric>
@@ -173,7 +174,7 @@ static const char *kStageLabel[ST_COUNT] = {"ray generation", "intersection", "s
 // its samples one raytrace() at a time.  Accumulation stays on the renderer's stream, in call order (the fp32 sums are
 // order-sensitive), so results do not depend on the number of lanes.
 struct Wavefront {
-    hipStream_t stream = nullptr;   // the lane's own stream (unused with one lane: everything runs on the renderer's)
+    hipStream_t stream = nullptr;   // the lane's own stream; lane 0 (and a renderer with one lane) runs on the renderer's stream and has none
     Queue q[2]{};
     ShadowQueue sq{};
     float4 *hits = nullptr, *Lsum = nullptr;
@@ -183,6 +184,7 @@ struct Wavefront {
     hipEvent_t done = nullptr;      // recorded on `stream` behind the lane's last traversal / shading launch
     hipEvent_t consumed = nullptr;  // recorded on the renderer's stream behind the accumulation that read this lane's Lsum
     bool consumed_recorded = false;
+    std::vector<hipEvent_t> trav;   // LPT_EXP_LANE_PHASE: trav[t] recorded on the lane's stream behind traversal launch t (0: the primary rays) of the lane's wavefront
 };
 constexpr int kMaxLanes = 4;
 constexpr uint32_t kStepBudget = 48u, kBudgetRays = 3000000u;  // defaults of LPT_EXP_STEP_BUDGET / LPT_EXP_BUDGET_RAYS (measured: profiles/r04_experiments_ab.txt H)
@@ -248,6 +250,9 @@ struct lpt_renderer {
     // other lane: the kernel alone is 10 % slower (2.75 -> 3.05 ms per frame), the frame 0.5 % faster (11.27-11.29 -> 11.19-11.24; profiles/r06_experiments_ab.txt O)
     uint32_t shade_blocks_per_cu = 0;
     uint32_t trace_waves_per_cu = 0;  // 0 = sized from the frame's ray count (below); LPT_EXP_TRACE_WAVES_PER_CU pins it
+    // the pieces of a cut batch against each other (LPT_EXP_LANE_PHASE; flush_pending): 0 free, 1 offset start, 2 alternating traversal.  1: the bench frame
+    // 10.44-10.47 ms against 10.52-10.53 free; 2: 11.87 (one traversal grid at a time gives up more than the shading beside it wins; profiles/r08_lane_phase_ab.txt)
+    uint32_t lane_phase = 1;
     // device memory
     uint32_t n_slots = 0;
     float4 *accum = nullptr, *scratch = nullptr;
@@ -1200,10 +1205,13 @@ static int alloc_ray_buffers(Wavefront &wf, size_t rays) {
     return LPT_OK;
 }
 
-// stream, events and counters of a lane (created on first use)
+// stream, events and counters of a lane (created on first use).  Lane 0 enqueues on the renderer's stream: the runtime maps
+// streams onto a fixed number of hardware queues (4 by default: the null stream, the device's, the renderer's and one more), and
+// streams that share a queue run back to back — with a stream of its own for every lane, the two lanes of the default renderer
+// shared one queue and never overlapped (profiles/r08_lane_phase_ab.txt)
 static int ensure_lane(lpt_renderer *r, int l) {
     Wavefront &wf = r->wf[l];
-    if (!wf.stream) HIP_TRY(hipStreamCreateWithFlags(&wf.stream, hipStreamNonBlocking));
+    if (l > 0 && !wf.stream) HIP_TRY(hipStreamCreateWithFlags(&wf.stream, hipStreamNonBlocking));
     if (!wf.done) HIP_TRY(hipEventCreateWithFlags(&wf.done, hipEventDisableTiming));
     if (!wf.consumed) HIP_TRY(hipEventCreateWithFlags(&wf.consumed, hipEventDisableTiming));
     if (!wf.ctr) HIP_TRY(hipMalloc(&wf.ctr, sizeof(FrameCounters)));
@@ -1291,6 +1299,7 @@ int lpt_renderer_destroy(lpt_renderer *r) {
         if (wf.stream) hipStreamDestroy(wf.stream);
         if (wf.done) hipEventDestroy(wf.done);
         if (wf.consumed) hipEventDestroy(wf.consumed);
+        for (hipEvent_t e : wf.trav) hipEventDestroy(e);
         if (wf.ctr) hipFree(wf.ctr);
     }
     if (r->totals) hipFree(r->totals);
@@ -1486,6 +1495,7 @@ int lpt_renderer_set_option(lpt_renderer *r, int option, uint64_t value) {
     case LPT_OPT_EXPERIMENT(LPT_EXP_PACKET_QUADS): r->packet_quads = value != 0; break;
     case LPT_OPT_EXPERIMENT(LPT_EXP_SPLIT_RAYS): r->split_rays = value; break;
     case LPT_OPT_EXPERIMENT(LPT_EXP_BUDGET_SPLIT): r->budget_split = value != 0; break;
+    case LPT_OPT_EXPERIMENT(LPT_EXP_LANE_PHASE): if (value > 2u) return fail(LPT_ERR_INVALID_ARG, "LPT_EXP_LANE_PHASE: 0 (free), 1 (offset start), 2 (alternating traversal)"); r->lane_phase = (uint32_t)value; break;
     case LPT_OPT_TAIL_LANES: r->tail_lanes = (uint32_t)std::min<uint64_t>(value, kTailMax); break;
     case LPT_OPT_COOP_RAYS: r->coop_rays = (uint32_t)std::min<uint64_t>(value, 0x7FFFFFFFu); break;
     default: return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_option: unknown option %d", option);
@@ -1510,6 +1520,7 @@ int lpt_renderer_get_option(const lpt_renderer *r, int option, uint64_t *value) 
     case LPT_OPT_EXPERIMENT(LPT_EXP_PACKET_QUADS): *value = r->packet_quads; break;
     case LPT_OPT_EXPERIMENT(LPT_EXP_SPLIT_RAYS): *value = r->split_rays; break;
     case LPT_OPT_EXPERIMENT(LPT_EXP_BUDGET_SPLIT): *value = r->budget_split; break;
+    case LPT_OPT_EXPERIMENT(LPT_EXP_LANE_PHASE): *value = r->lane_phase; break;
     case LPT_OPT_TAIL_LANES: *value = r->tail_lanes; break;
     case LPT_OPT_COOP_RAYS: *value = r->coop_rays; break;
     default: return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_get_option: unknown option %d", option);
@@ -1567,16 +1578,17 @@ static void harvest_slot(lpt_renderer *r, int slot) {
     r->ev_count[slot] = 0;
 }
 static inline int cur_slot(const lpt_renderer *r) { return (int)(r->ring_pos % lpt_renderer::kRing); }
-static inline void stage_begin(lpt_renderer *r, int stage, hipStream_t stream) {
+// `slot`: the ring slot of the wavefront the launch belongs to (-1: the current one; a phased piece's launches are enqueued after the next piece's set-up)
+static inline void stage_begin(lpt_renderer *r, int stage, hipStream_t stream, int slot = -1) {
     if (!r->timings) return;
-    const int slot = cur_slot(r);
+    if (slot < 0) slot = cur_slot(r);
     if (r->ev_count[slot] >= lpt_renderer::kMaxEvents) return;
     r->ev_stage[slot][r->ev_count[slot]] = stage;
     hipEventRecord(r->ev_start[slot * lpt_renderer::kMaxEvents + r->ev_count[slot]], stream);
 }
-static inline void stage_end(lpt_renderer *r, hipStream_t stream) {
+static inline void stage_end(lpt_renderer *r, hipStream_t stream, int slot = -1) {
     if (!r->timings) return;
-    const int slot = cur_slot(r);
+    if (slot < 0) slot = cur_slot(r);
     if (r->ev_count[slot] >= lpt_renderer::kMaxEvents) return;
     hipEventRecord(r->ev_stop[slot * lpt_renderer::kMaxEvents + r->ev_count[slot]], stream);
     r->ev_count[slot]++;
@@ -1610,19 +1622,26 @@ static void launch_filter(lpt_renderer *r, hipStream_t s) {
 
 extern "C" {
 
+// How one stage of a wavefront's launches is ordered against the other lanes (flush_pending, LPT_EXP_LANE_PHASE): events it waits
+// for before its first launch / before its traversal launch, and the event recorded behind its traversal launch
+struct PhaseHooks { hipEvent_t wait_start = nullptr, wait_trav = nullptr, rec_trav = nullptr; };
+
 // A wavefront between its two halves (flush_pending): what the second half needs to know about the first
 struct Ticket {
     FrameParams p;
     int lane = 0;
     bool split = false, denoise = false, packet = false;
     CamBasis cur{};
+    uint32_t stages = 0;                                 // the launches of the first half, stage by stage (wavefront_trace)
+    std::function<int(uint32_t, const PhaseHooks &)> run;
 };
 
 // First half of a wavefront: the launches of `n_samples` recorded raytrace() calls over the rank's pixel slots
 // [slot0, slot0 + piece_slots) — ray generation, traversal, shading — on the wavefront's lane, from the protocol state the first
 // of the calls saw (frame_count0, seed0, acc0 = its accumulate flag; the later ones ran with accumulate == true by construction).
+// `defer`: the launches are left in tk.run for the caller to enqueue stage by stage; otherwise they are enqueued here.
 static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_samples, uint32_t frame_count0, uint32_t seed0, bool acc0,
-                           uint32_t slot0, uint32_t piece_slots, Ticket &tk, bool solo) {
+                           uint32_t slot0, uint32_t piece_slots, Ticket &tk, bool solo, bool defer = false) {
     HIP_TRY(hipSetDevice(r->dev->ordinal));
     hipStream_t sm = r->stream;                  // accumulation, filter passes, bookkeeping, reads, the exchange: in call order
     const uint32_t nb = r->max_bounces;          // reference constant 3 (:398-399)
@@ -1659,7 +1678,7 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
         if (st != LPT_OK) return st;
     }
     Wavefront &wf = r->wf[lane];
-    hipStream_t s = split ? wf.stream : sm;
+    hipStream_t s = (split && lane > 0) ? wf.stream : sm;
     r->last_lane = lane;
     if ((size_t)n_rays > wf.ray_cap && p.n_slots) {
         HIP_TRY(hipStreamSynchronize(sm));       // everything that read this lane's buffers has been enqueued behind `sm`'s waits
@@ -1672,7 +1691,7 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
             if (l == lane || r->wf[l].ray_cap >= (size_t)n_rays) continue;
             st = ensure_lane(r, l);
             if (st != LPT_OK) return st;
-            HIP_TRY(hipStreamSynchronize(r->wf[l].stream));
+            if (r->wf[l].stream) HIP_TRY(hipStreamSynchronize(r->wf[l].stream));   // lane 0's work is behind `sm`, synchronised above
             st = alloc_ray_buffers(r->wf[l], n_rays);
             if (st != LPT_OK) return st;
         }
@@ -1707,8 +1726,8 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
     const DScene &sc = r->sg->d;
     if (r->timings) { r->ring_pos++; harvest_slot(r, cur_slot(r)); }
 
+    tk.stages = 0; tk.run = nullptr;
     if (p.n_slots) {
-        HIP_TRY(hipMemsetAsync(wf.ctr, 0, sizeof(FrameCounters), s));
         const uint32_t cus = (uint32_t)r->dev->compute_units;
         const uint32_t stream_blocks = std::min<uint32_t>(div_up(n_rays, kBlock), cus * 8u);
         const uint32_t shade_blocks = std::min<uint32_t>(div_up(n_rays, kBlock), cus * (r->shade_blocks_per_cu ? r->shade_blocks_per_cu : (solo ? 4u : 3u)));
@@ -1723,16 +1742,7 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
         waves = std::max(8u, waves & ~7u);  // whole groups of 8: one chunk head per XCD
         const uint32_t trace_blocks = std::min<uint32_t>(div_up(n_rays, kTraceBlock), waves);
         const size_t lds = stack_bytes(sc);
-
-        // "ray generation" (:444-448)
-        stage_begin(r, ST_RAYGEN, s);
         const bool dense = (r->w % r->tile_w == 0u) && (r->h % r->tile_h == 0u);
-        if (dense) {
-            hipLaunchKernelGGL(k_raygen<true>, dim3(stream_blocks), dim3(kBlock), 0, s, p, nz, wf.q[0], wf.Lsum, wf.ctr);
-        } else {
-            hipLaunchKernelGGL(k_raygen<false>, dim3(stream_blocks), dim3(kBlock), 0, s, p, nz, wf.q[0], wf.Lsum, wf.ctr);
-        }
-        stage_end(r, s);
 
         // Bounce 0 by packet traversal (one tree walk per 8x8-pixel patch) pays while the patch is narrow: at 1920x1080 a packet enters 17.9 nodes
         // for rays that need 14.9 each, and the walk runs at 11.5 Grays/s against 6.2 per ray; at 240x135 the same patch spans eight times the
@@ -1741,7 +1751,6 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
         const float pixel_rad = 2.0f * th / (float)std::max(r->h, 1u);
         const bool packet = (r->packet_primary == 1u || (r->packet_primary == 2u && pixel_rad <= kPacketMaxPixelRad));
         tk.packet = packet;
-        uint32_t seed = seed0;
         // Traversal launches: closest-hit rays of bounce b+1 and shadow rays of bounce b, both produced by shade(b), are traced by
         // ONE persistent launch (k_trace) — nb+1 traversal launches per frame instead of 2*nb.
         // the occluder-cache probe rides with the stats kernels only (kernels.h OccProbe); its table belongs to the renderer
@@ -1759,72 +1768,99 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
         // a TINY wavefront (fewer rays than the chip has wave slots): the per-bounce launches with EVERY ray traced by a whole wave (k_trace_coop over the queues) — a lane per
         // ray leaves the chip empty and the frame is one chain of dependent steps (64x36, 4 spp: k_path 0.72 ms per frame, the per-lane launches 0.83, this 0.39)
         const bool coop_all = !r->stats && r->coop_rays && n_rays <= r->coop_rays;
-        auto trace = [&](int cb, int sb) {
-            stage_begin(r, cb >= 0 ? ST_INTERSECT : ST_SHADOW, s);  // :457-464, :493-498
-            const Queue qin = wf.q[(uint32_t)(cb < 0 ? 0 : cb) & 1u];
-            const int launch_no = cb >= 0 ? cb : (int)nb;   // which strag_count[] this launch fills
-            if (coop_all) {
-                const size_t clds = sizeof(uint32_t) * coop_stack_entries(kCoopStack, r->sg->stats.max_depth);
-                hipLaunchKernelGGL(k_trace_coop<false>, dim3(std::min(2u * n_rays, cus * kCoopWavesPerCu)), dim3(kTraceBlock), clds, s, sc, qin, wf.hits, wf.sq, wf.Lsum, wf.ctr, cb, sb, (const uint32_t *)nullptr, launch_no);
-                stage_end(r, s);
-                return;
-            }
-            if (tail) {
-                if (pipe) hipLaunchKernelGGL((k_trace<false, true, true>), dim3(trace_blocks), dim3(kTraceBlock), lds + tail_lds, s, TraceKernargs{sc, qin, wf.hits, wf.sq, wf.Lsum, wf.ctr, cb, sb, r->refill, occ, 0u, wf.strag, launch_no, tail});
-                else hipLaunchKernelGGL((k_trace<false, false, true>), dim3(trace_blocks), dim3(kTraceBlock), lds + tail_lds, s, TraceKernargs{sc, qin, wf.hits, wf.sq, wf.Lsum, wf.ctr, cb, sb, r->refill, occ, 0u, wf.strag, launch_no, tail});
-            } else if (pipe) {
-                if (r->stats) hipLaunchKernelGGL((k_trace<true, true>), dim3(trace_blocks), dim3(kTraceBlock), lds + 64u, s, TraceKernargs{sc, qin, wf.hits, wf.sq, wf.Lsum, wf.ctr, cb, sb, r->refill, occ, budget, wf.strag, launch_no, 0u});
-                else hipLaunchKernelGGL((k_trace<false, true>), dim3(trace_blocks), dim3(kTraceBlock), lds, s, TraceKernargs{sc, qin, wf.hits, wf.sq, wf.Lsum, wf.ctr, cb, sb, r->refill, occ, budget, wf.strag, launch_no, 0u});
-            } else if (r->stats) hipLaunchKernelGGL((k_trace<true, false>), dim3(trace_blocks), dim3(kTraceBlock), lds + 64u, s, TraceKernargs{sc, qin, wf.hits, wf.sq, wf.Lsum, wf.ctr, cb, sb, r->refill, occ, budget, wf.strag, launch_no, 0u});
-            else hipLaunchKernelGGL((k_trace<false, false>), dim3(trace_blocks), dim3(kTraceBlock), lds, s, TraceKernargs{sc, qin, wf.hits, wf.sq, wf.Lsum, wf.ctr, cb, sb, r->refill, occ, budget, wf.strag, launch_no, 0u});
-            if (budget) {   // the launch's stragglers, a whole wave each (most waves of this grid find none and leave at once)
-                const size_t clds = sizeof(uint32_t) * coop_stack_entries(kCoopStack, r->sg->stats.max_depth);
-                if (r->stats) hipLaunchKernelGGL(k_trace_coop<true>, dim3(cus * kCoopWavesPerCu), dim3(kTraceBlock), clds, s, sc, qin, wf.hits, wf.sq, wf.Lsum, wf.ctr, cb, sb, wf.strag, launch_no);
-                else hipLaunchKernelGGL(k_trace_coop<false>, dim3(cus * kCoopWavesPerCu), dim3(kTraceBlock), clds, s, sc, qin, wf.hits, wf.sq, wf.Lsum, wf.ctr, cb, sb, wf.strag, launch_no);
-            }
-            stage_end(r, s);
-        };
-        {
-            if (packet) {
-                // the primary rays: 64 consecutive queue entries are an 8x8-pixel patch of one sample — packet traversal (k_trace_packet)
-                stage_begin(r, ST_PRIMARY, s);
-                const uint32_t packets = div_up(n_rays, 64u);
-                const size_t plds = (size_t)(48u + 7u * r->sg->stats.max_depth + 8u) * sizeof(uint32_t);   // 48 planes + the stack
-                // 4 samples of a 4x4-pixel quarter per packet instead of one sample of an 8x8 patch, where the queue order allows it: a dense frame
-                // (queue index = sample * slots + slot), 8x8 pixel blocks inside the tiles, whole blocks, a multiple of four samples
-                const uint32_t quad_slots = (r->packet_quads && dense && p.block8 && p.n_slots % 64u == 0u && p.slot0 % 64u == 0u && n_samples % 4u == 0u) ? p.n_slots : 0u;
-                if (r->stats) hipLaunchKernelGGL(k_trace_packet<true>, dim3(std::min(packets, cus * kPacketBlocksPerCu)), dim3(kTraceBlock), plds, s, sc, wf.q[0], wf.hits, wf.ctr, 0, quad_slots);
-                else hipLaunchKernelGGL(k_trace_packet<false>, dim3(std::min(packets, cus * kPacketBlocksPerCu)), dim3(kTraceBlock), plds, s, sc, wf.q[0], wf.hits, wf.ctr, 0, quad_slots);
-                stage_end(r, s);
-            } else if (coop_all || !(r->path_rays && n_rays <= r->path_rays)) trace(0, -1);   // a path-kernel wavefront traces its primary rays itself
-        }
-        // A small wavefront (the tile shard of a multi-GPU frame): every bounce behind the primary hits in ONE persistent launch — the
-        // passes of renderer.rs:484-509 without a chip-wide barrier between them (kernels.h k_path); same frame, same counters
+        // The launches in stages, so that the pieces of a cut batch can be enqueued stage by stage across the lanes (flush_pending,
+        // LPT_EXP_LANE_PHASE): stage 0 = counters, ray generation and the primary rays (with the path kernel: the whole wavefront),
+        // stage b + 1 = shade(b) and the traversal launch behind it.  `ph` orders the stage against the other lanes' (stream events only).
+        // The closure holds copies of what the launches read; `r`'s buffers and the scene do not change before the submission is enqueued.
         const bool path = r->path_rays && n_rays <= r->path_rays && !coop_all;   // the primary hits are there, whichever kernel found them
-        if (path) {
-            stage_begin(r, ST_PATH, s);
-            const uint32_t pblocks = std::min<uint32_t>(div_up(n_rays, kTraceBlock), std::max(8u, (cus * r->path_waves_per_cu) & ~7u));
-            const size_t plds = lds + kPathLdsExtra;   // stacks + sRGB table + per-bounce counters
-            if (denoise) {
-                if (r->stats) hipLaunchKernelGGL((k_path<true, true>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, wf.q[0], packet ? wf.hits : (const float4 *)nullptr, wf.Lsum, wf.ctr, seed0, gb, r->path_refill);
-                else hipLaunchKernelGGL((k_path<true, false>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, wf.q[0], packet ? wf.hits : (const float4 *)nullptr, wf.Lsum, wf.ctr, seed0, gb, r->path_refill);
-            } else if (r->stats) hipLaunchKernelGGL((k_path<false, true>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, wf.q[0], packet ? wf.hits : (const float4 *)nullptr, wf.Lsum, wf.ctr, seed0, gb, r->path_refill);
-            else hipLaunchKernelGGL((k_path<false, false>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, wf.q[0], packet ? wf.hits : (const float4 *)nullptr, wf.Lsum, wf.ctr, seed0, gb, r->path_refill);
-            stage_end(r, s);
+        const int slot = cur_slot(r);
+        Wavefront *w = &wf;
+        tk.stages = nb + 1u;
+        tk.run = [=](uint32_t t, const PhaseHooks &ph) -> int {
+            if (ph.wait_start) HIP_TRY(hipStreamWaitEvent(s, ph.wait_start, 0));
+            auto trace = [&](int cb, int sb) {
+                stage_begin(r, cb >= 0 ? ST_INTERSECT : ST_SHADOW, s, slot);  // :457-464, :493-498
+                const Queue qin = w->q[(uint32_t)(cb < 0 ? 0 : cb) & 1u];
+                const int launch_no = cb >= 0 ? cb : (int)nb;   // which strag_count[] this launch fills
+                if (coop_all) {
+                    const size_t clds = sizeof(uint32_t) * coop_stack_entries(kCoopStack, r->sg->stats.max_depth);
+                    hipLaunchKernelGGL(k_trace_coop<false>, dim3(std::min(2u * n_rays, cus * kCoopWavesPerCu)), dim3(kTraceBlock), clds, s, sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, (const uint32_t *)nullptr, launch_no);
+                    stage_end(r, s, slot);
+                    return;
+                }
+                if (tail) {
+                    if (pipe) hipLaunchKernelGGL((k_trace<false, true, true>), dim3(trace_blocks), dim3(kTraceBlock), lds + tail_lds, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, 0u, w->strag, launch_no, tail});
+                    else hipLaunchKernelGGL((k_trace<false, false, true>), dim3(trace_blocks), dim3(kTraceBlock), lds + tail_lds, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, 0u, w->strag, launch_no, tail});
+                } else if (pipe) {
+                    if (r->stats) hipLaunchKernelGGL((k_trace<true, true>), dim3(trace_blocks), dim3(kTraceBlock), lds + 64u, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, budget, w->strag, launch_no, 0u});
+                    else hipLaunchKernelGGL((k_trace<false, true>), dim3(trace_blocks), dim3(kTraceBlock), lds, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, budget, w->strag, launch_no, 0u});
+                } else if (r->stats) hipLaunchKernelGGL((k_trace<true, false>), dim3(trace_blocks), dim3(kTraceBlock), lds + 64u, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, budget, w->strag, launch_no, 0u});
+                else hipLaunchKernelGGL((k_trace<false, false>), dim3(trace_blocks), dim3(kTraceBlock), lds, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, budget, w->strag, launch_no, 0u});
+                if (budget) {   // the launch's stragglers, a whole wave each (most waves of this grid find none and leave at once)
+                    const size_t clds = sizeof(uint32_t) * coop_stack_entries(kCoopStack, r->sg->stats.max_depth);
+                    if (r->stats) hipLaunchKernelGGL(k_trace_coop<true>, dim3(cus * kCoopWavesPerCu), dim3(kTraceBlock), clds, s, sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, w->strag, launch_no);
+                    else hipLaunchKernelGGL(k_trace_coop<false>, dim3(cus * kCoopWavesPerCu), dim3(kTraceBlock), clds, s, sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, w->strag, launch_no);
+                }
+                stage_end(r, s, slot);
+            };
+            if (t == 0u) {
+                HIP_TRY(hipMemsetAsync(w->ctr, 0, sizeof(FrameCounters), s));
+                // "ray generation" (:444-448)
+                stage_begin(r, ST_RAYGEN, s, slot);
+                if (dense) {
+                    hipLaunchKernelGGL(k_raygen<true>, dim3(stream_blocks), dim3(kBlock), 0, s, p, nz, w->q[0], w->Lsum, w->ctr);
+                } else {
+                    hipLaunchKernelGGL(k_raygen<false>, dim3(stream_blocks), dim3(kBlock), 0, s, p, nz, w->q[0], w->Lsum, w->ctr);
+                }
+                stage_end(r, s, slot);
+                if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
+                if (packet) {
+                    // the primary rays: 64 consecutive queue entries are an 8x8-pixel patch of one sample — packet traversal (k_trace_packet)
+                    stage_begin(r, ST_PRIMARY, s, slot);
+                    const uint32_t packets = div_up(n_rays, 64u);
+                    const size_t plds = (size_t)(48u + 7u * r->sg->stats.max_depth + 8u) * sizeof(uint32_t);   // 48 planes + the stack
+                    // 4 samples of a 4x4-pixel quarter per packet instead of one sample of an 8x8 patch, where the queue order allows it: a dense frame
+                    // (queue index = sample * slots + slot), 8x8 pixel blocks inside the tiles, whole blocks, a multiple of four samples
+                    const uint32_t quad_slots = (r->packet_quads && dense && p.block8 && p.n_slots % 64u == 0u && p.slot0 % 64u == 0u && n_samples % 4u == 0u) ? p.n_slots : 0u;
+                    if (r->stats) hipLaunchKernelGGL(k_trace_packet<true>, dim3(std::min(packets, cus * kPacketBlocksPerCu)), dim3(kTraceBlock), plds, s, sc, w->q[0], w->hits, w->ctr, 0, quad_slots);
+                    else hipLaunchKernelGGL(k_trace_packet<false>, dim3(std::min(packets, cus * kPacketBlocksPerCu)), dim3(kTraceBlock), plds, s, sc, w->q[0], w->hits, w->ctr, 0, quad_slots);
+                    stage_end(r, s, slot);
+                } else if (coop_all || !path) trace(0, -1);   // a path-kernel wavefront traces its primary rays itself
+                // A small wavefront (the tile shard of a multi-GPU frame): every bounce behind the primary hits in ONE persistent launch — the
+                // passes of renderer.rs:484-509 without a chip-wide barrier between them (kernels.h k_path); same frame, same counters
+                if (path) {
+                    stage_begin(r, ST_PATH, s, slot);
+                    const uint32_t pblocks = std::min<uint32_t>(div_up(n_rays, kTraceBlock), std::max(8u, (cus * r->path_waves_per_cu) & ~7u));
+                    const size_t plds = lds + kPathLdsExtra;   // stacks + sRGB table + per-bounce counters
+                    if (denoise) {
+                        if (r->stats) hipLaunchKernelGGL((k_path<true, true>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill);
+                        else hipLaunchKernelGGL((k_path<true, false>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill);
+                    } else if (r->stats) hipLaunchKernelGGL((k_path<false, true>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill);
+                    else hipLaunchKernelGGL((k_path<false, false>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill);
+                    stage_end(r, s, slot);
+                }
+            } else if (!path) {
+                const uint32_t b = t - 1u;
+                const uint32_t seed = seed0 + t;     // += 1 per bounce (:453, :487)
+                const Queue qin = w->q[b & 1u], qout = w->q[(b + 1u) & 1u];
+                stage_begin(r, ST_SHADE, s, slot);            // :471-480, :502-508
+                if (denoise && b == 0u)  // PrimaryRayPass: bounce-0 shading + G-buffer + motion (renderer.rs:466-481)
+                    hipLaunchKernelGGL(k_shade<true>, dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues);
+                else
+                    hipLaunchKernelGGL(k_shade<false>, dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues);
+                stage_end(r, s, slot);
+                if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
+                trace(b + 1u < nb ? (int)(b + 1u) : -1, (int)b);
+            }
+            if (ph.rec_trav) HIP_TRY(hipEventRecord(ph.rec_trav, s));
+            if (t == nb && split) HIP_TRY(hipEventRecord(w->done, s));
+            HIP_TRY(hipGetLastError());
+            return LPT_OK;
+        };
+        for (uint32_t t = 0; !defer && t < tk.stages; ++t) {
+            const int st = tk.run(t, PhaseHooks{});
+            if (st != LPT_OK) return st;
         }
-        for (uint32_t b = 0; b < nb && !path; ++b) {
-            seed += 1u;                          // :453, :487
-            const Queue qin = wf.q[b & 1u], qout = wf.q[(b + 1u) & 1u];
-            stage_begin(r, ST_SHADE, s);            // :471-480, :502-508
-            if (denoise && b == 0u)  // PrimaryRayPass: bounce-0 shading + G-buffer + motion (renderer.rs:466-481)
-                hipLaunchKernelGGL(k_shade<true>, dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, wf.hits, qout, wf.sq, wf.Lsum, wf.ctr, (int)b, seed, gb, r->sort_queues);
-            else
-                hipLaunchKernelGGL(k_shade<false>, dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, wf.hits, qout, wf.sq, wf.Lsum, wf.ctr, (int)b, seed, gb, r->sort_queues);
-            stage_end(r, s);
-            trace(b + 1u < nb ? (int)(b + 1u) : -1, (int)b);
-        }
-        if (split) HIP_TRY(hipEventRecord(wf.done, s));
-        HIP_TRY(hipGetLastError());
     }
     tk.p = p; tk.lane = lane; tk.split = split; tk.denoise = denoise; tk.cur = gb.cur;
     return LPT_OK;
@@ -1934,12 +1970,46 @@ static int flush_pending(lpt_renderer *r, const ReadPlan *read) {
         hipStreamSynchronize(r->stream);
         return st;
     };
-    for (uint32_t k = 0; k < pieces; ++k) {
-        if (k >= ahead) { const int st = finish(k - ahead); if (st != LPT_OK) return bail(st); }
-        const uint32_t g0 = k * per_piece, g1 = std::min(granules, g0 + per_piece);
-        r->n_wavefronts++;
-        const int st = wavefront_trace(r, b.view, b.n, b.frame_count0, b.seed0, b.acc0, g0 * granule, (g1 - g0) * granule, tk[k % ahead], pieces == 1u);
-        if (st != LPT_OK) return bail(st);
+    // LPT_EXP_LANE_PHASE: the pieces that run side by side on the lanes (a group of `ahead`) are enqueued stage by stage — stage t of every
+    // piece of the group before stage t + 1 of any — so that the events that order them are always recorded before they are waited for.
+    // 1 (offset start): a piece's first launch waits for the previous piece's primary traversal; 2 (alternating traversal): a piece's
+    // traversal launch t waits for the previous piece's traversal t, the group's first piece's for the last piece's traversal t - 1,
+    // so one traversal grid at a time holds the chip and the other pieces shade beside it.
+    const uint32_t phase = (ahead > 1u && pieces > 1u) ? r->lane_phase : 0u;
+    const uint32_t group = phase ? ahead : 1u;
+    for (uint32_t k0 = 0; k0 < pieces; k0 += group) {
+        const uint32_t k1 = std::min(pieces, k0 + group);
+        for (uint32_t k = k0; k < k1; ++k) {
+            if (k >= ahead) { const int st = finish(k - ahead); if (st != LPT_OK) return bail(st); }
+            const uint32_t g0 = k * per_piece, g1 = std::min(granules, g0 + per_piece);
+            r->n_wavefronts++;
+            const int st = wavefront_trace(r, b.view, b.n, b.frame_count0, b.seed0, b.acc0, g0 * granule, (g1 - g0) * granule, tk[k % ahead], pieces == 1u, phase != 0u);
+            if (st != LPT_OK) return bail(st);
+        }
+        if (!phase) continue;
+        const uint32_t stages = tk[k0 % ahead].stages;   // nb + 1 for every piece
+        for (uint32_t k = k0; k < k1; ++k) {
+            Wavefront &wf = r->wf[tk[k % ahead].lane];
+            while (wf.trav.size() < stages) {
+                hipEvent_t e = nullptr;
+                const hipError_t he = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+                if (he != hipSuccess) return bail(fail(LPT_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(he)));
+                wf.trav.push_back(e);
+            }
+        }
+        for (uint32_t t = 0; t < stages; ++t) {
+            for (uint32_t k = k0; k < k1; ++k) {
+                const Ticket &cur = tk[k % ahead];
+                const Wavefront &prev = r->wf[tk[(k > k0 ? k - 1u : k1 - 1u) % ahead].lane];
+                PhaseHooks ph;
+                ph.rec_trav = r->wf[cur.lane].trav[t];
+                if (phase == 1u && t == 0u && k > k0) ph.wait_start = prev.trav[0];
+                if (phase == 2u && k > k0) ph.wait_trav = prev.trav[t];
+                if (phase == 2u && k == k0 && t > 0u) ph.wait_trav = prev.trav[t - 1u];
+                const int st = cur.run ? cur.run(t, ph) : LPT_OK;
+                if (st != LPT_OK) return bail(st);
+            }
+        }
     }
     for (uint32_t k = pieces > ahead ? pieces - ahead : 0u; k < pieces; ++k) { const int st = finish(k); if (st != LPT_OK) return bail(st); }
     return LPT_OK;
