@@ -252,6 +252,8 @@ impl Renderer {
     /// build-only knobs (the reference's constants: 3 bounces, `renderer.rs:398-399`)
     pub fn set_max_bounces(&mut self, bounces: u32) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_max_bounces(self.h, bounces) }) }
     pub fn set_seed(&mut self, seed: u32) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_seed(self.h, seed) }) }
+    /// `SPEC.md` §18: next-event estimation samples the environment probe too (off by default; frames change with it)
+    pub fn set_env_sampling(&mut self, on: bool) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_env_sampling(self.h, on as i32) }) }
     /// launch tuning (the `LPT_OPT_` constants of `ffi`): never changes a frame
     pub fn set_option(&mut self, option: i32, value: u64) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_option(self.h, option, value) }) }
     /// tile-sharded frames: bind a communicator (implies `set_shard(rank, world, 32, 8)`), then `exchange` after the frame's `raytrace` calls

@@ -120,6 +120,11 @@ class ProbeGPU {  // scene.rs:66-121
     ~ProbeGPU() { lpt_probe_destroy(h_); }
     ProbeGPU(const ProbeGPU &) = delete;
     lpt_probe *handle() const { return h_; }
+    /// SPEC.md §18, the renderer's sampler on the GPU: uniforms[n][6] = {r6, r7, r8, r9, r1, r2} -> dirs[n][3], pdf_s[n], radiance[n][3]
+    void sample(const Device &device, const float *uniforms, uint32_t n, float *dirs, float *pdf_s, float *radiance) const {
+        check(lpt_probe_sample(device.inner(), h_, uniforms, n, dirs, pdf_s, radiance));
+    }
+    void pdf(const Device &device, const float *dirs, uint32_t n, float *pdf_e) const { check(lpt_probe_pdf(device.inner(), h_, dirs, n, pdf_e)); }
 
    private:
     lpt_probe *h_ = nullptr;
@@ -165,6 +170,9 @@ class Renderer {  // renderer.rs:169-811
         return out;
     }
     void set_max_bounces(uint32_t n) { check(lpt_renderer_set_max_bounces(h_, n)); }
+    /// SPEC.md §18: next-event estimation samples the environment probe too (off by default; frames change with it)
+    void set_env_sampling(bool on) { check(lpt_renderer_set_env_sampling(h_, on ? 1 : 0)); }
+    bool env_sampling() const { int f = 0; check(lpt_renderer_get_env_sampling(h_, &f)); return f != 0; }
     void set_seed(uint32_t s) { check(lpt_renderer_set_seed(h_, s)); }
     void set_vfov(float radians) { check(lpt_renderer_set_vfov(h_, radians)); }
     /// `weights` (one small integer per rank, the same on every rank; nullptr = equal shares): unequal tile shares, e.g. fewer tiles for the rank that also assembles the frame

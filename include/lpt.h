@@ -307,6 +307,19 @@ int lpt_scene_gpu_stats(const lpt_scene_gpu *sg, lpt_accel_stats *out);
 int lpt_probe_upload(lpt_device *dev, const uint8_t *rgbe8, uint32_t width, uint32_t height,
                      lpt_probe **out);
 int lpt_probe_destroy(lpt_probe *probe);
+/* new (environment importance sampling, SPEC.md §18; no reference counterpart): the probe's sampling distribution, pure host
+ * arithmetic (no GPU).  For a width x height RGBE8 probe: pdf_uv[height][width] (the density over the unit square of (u, v)),
+ * the marginal over rows as an alias table (row_q, row_alias: height entries) and each row's conditional (col_q, col_alias:
+ * height x width entries, alias = a column of the same row); *total = the sum of the weights, 0 = the probe has no distribution
+ * (black).  NULL outputs are skipped. */
+int lpt_env_distribution(const uint8_t *rgbe8, uint32_t width, uint32_t height, float *pdf_uv, float *row_q, uint32_t *row_alias,
+                         float *col_q, uint32_t *col_alias, double *total);
+/* new (SPEC.md §18): the renderer's environment sampler run on the GPU, for tests and tools.  lpt_probe_sample: n draws of
+ * uniforms[n][6] = {r6, r7, r8, r9, r1, r2} -> dirs[n][3], their density pdf_s[n] (per steradian) and the probe's radiance
+ * radiance[n][3] (a draw without a sample, or a probe without a distribution: all zero).  lpt_probe_pdf: the density p_e of
+ * dirs[n][3] (0 without a distribution).  Blocking; host arrays.  The distribution is built on first use and kept with the probe. */
+int lpt_probe_sample(lpt_device *dev, lpt_probe *probe, const float *uniforms, uint32_t n, float *dirs, float *pdf_s, float *radiance);
+int lpt_probe_pdf(lpt_device *dev, lpt_probe *probe, const float *dirs, uint32_t n, float *pdf_e);
 
 /* ---- ray queries (the IntersectorPass on its own) -------------------------
  * replaces: passes::IntersectorPass dispatch (crates/lib/src/renderer.rs:458-463)
@@ -447,6 +460,11 @@ int lpt_renderer_enable_timings(lpt_renderer *r, int flag);
 /* ---- build-only extensions (no reference knob) -------- */
 /* reference constant STATIC/MOVING_NUM_BOUNCES = 3 (renderer.rs:398-399) */
 int lpt_renderer_set_max_bounces(lpt_renderer *r, uint32_t bounces);
+/* new (SPEC.md §18): next-event estimation samples the environment probe too (multiple importance sampling against the BSDF
+ * rays that miss).  Off (0) by default; off, every frame is what it was.  Frames change with it — unlike an lpt_option, so it is
+ * a call of its own.  Active while the bound probe has a distribution (not black); recorded calls are submitted first. */
+int lpt_renderer_set_env_sampling(lpt_renderer *r, int flag);
+int lpt_renderer_get_env_sampling(const lpt_renderer *r, int *flag);
 int lpt_renderer_set_seed(lpt_renderer *r, uint32_t user_seed);
 /* vertical field of view in radians (reference: Camera::default inside albedo) */
 int lpt_renderer_set_vfov(lpt_renderer *r, float radians);

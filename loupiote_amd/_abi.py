@@ -110,6 +110,9 @@ SIGNATURES = {
     "lpt_scene_gpu_update_instances": (_i, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "lpt_probe_upload": (_i, [_vp, _vp, _u32, _u32, _pvp]),
     "lpt_probe_destroy": (_i, [_vp]),
+    "lpt_env_distribution": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "lpt_probe_sample": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "lpt_probe_pdf": (_i, [_vp, _vp, _vp, _u32, _vp]),
     "lpt_trace_closest": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),
     "lpt_trace_occluded": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "lpt_renderer_create": (_i, [_vp, _u32, _u32, _pvp]),
@@ -148,6 +151,8 @@ SIGNATURES = {
     "lpt_renderer_get_timings": (_i, [_vp, _vp, C.POINTER(_i)]),
     "lpt_renderer_enable_timings": (_i, [_vp, _i]),
     "lpt_renderer_set_max_bounces": (_i, [_vp, _u32]),
+    "lpt_renderer_set_env_sampling": (_i, [_vp, _i]),
+    "lpt_renderer_get_env_sampling": (_i, [_vp, C.POINTER(_i)]),
     "lpt_renderer_set_seed": (_i, [_vp, _u32]),
     "lpt_renderer_set_vfov": (_i, [_vp, _f]),
     "lpt_renderer_set_shard": (_i, [_vp, _u32, _u32, _u32, _u32]),

@@ -290,6 +290,23 @@ class ProbeGPU:
         h = C.c_void_p()
         _check(A.lib().lpt_probe_upload(device.inner(), A.ptr(buf), width, height, C.byref(h)))
         self._h = h
+        self._dev = device
+
+    def sample(self, u):
+        """The renderer's environment sampler (SPEC.md §18) on the GPU: u[n, 6] = (r6, r7, r8, r9, r1, r2) uniforms ->
+        (dirs[n, 3], pdf_s[n] per steradian, radiance[n, 3]); all zero for a draw without a sample or a black probe."""
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 6)
+        n = u.shape[0]
+        dirs, pdf, rad = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+        _check(A.lib().lpt_probe_sample(self._dev.inner(), self._h, A.ptr(u), n, A.ptr(dirs), A.ptr(pdf), A.ptr(rad)))
+        return dirs, pdf, rad
+
+    def pdf(self, dirs):
+        """p_e(d) (SPEC.md §18): the density the renderer's MIS weights give unit directions dirs[n, 3]"""
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        out = np.zeros(d.shape[0], np.float32)
+        _check(A.lib().lpt_probe_pdf(self._dev.inner(), self._h, A.ptr(d), d.shape[0], A.ptr(out)))
+        return out
 
     def close(self):
         if self._h:
@@ -451,6 +468,15 @@ class Renderer:
 
     def set_max_bounces(self, n):
         _check(A.lib().lpt_renderer_set_max_bounces(self._h, int(n)))
+
+    def set_env_sampling(self, flag):
+        """SPEC.md §18: next-event estimation samples the environment probe too (off by default; frames change with it)"""
+        _check(A.lib().lpt_renderer_set_env_sampling(self._h, 1 if flag else 0))
+
+    def get_env_sampling(self):
+        f = C.c_int()
+        _check(A.lib().lpt_renderer_get_env_sampling(self._h, C.byref(f)))
+        return bool(f.value)
 
     def set_seed(self, s):
         _check(A.lib().lpt_renderer_set_seed(self._h, int(s)))
@@ -640,6 +666,22 @@ class loaders:
     @staticmethod
     def load_gltf_path(path, scene):
         _check(A.lib().lpt_load_gltf_path(scene._h, str(path).encode()))
+
+
+def env_distribution(rgbe):
+    """SPEC.md §18 on the host: the sampling distribution of an RGBE8 probe (array [h, w, 4]).  Returns a dict of pdf_uv [h, w],
+    row_q / row_alias [h], col_q / col_alias [h, w] and total (the sum of the weights; 0 = no distribution)."""
+    a = np.ascontiguousarray(rgbe, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise Error(A.LPT_ERR_INVALID_ARG, "env_distribution: expected an [h, w, 4] RGBE8 array")
+    h, w = a.shape[:2]
+    out = {"pdf_uv": np.zeros((h, w), np.float32), "row_q": np.zeros(h, np.float32), "row_alias": np.zeros(h, np.uint32),
+           "col_q": np.zeros((h, w), np.float32), "col_alias": np.zeros((h, w), np.uint32)}
+    total = C.c_double()
+    _check(A.lib().lpt_env_distribution(A.ptr(a), w, h, A.ptr(out["pdf_uv"]), A.ptr(out["row_q"]), A.ptr(out["row_alias"]),
+                                        A.ptr(out["col_q"]), A.ptr(out["col_alias"]), C.byref(total)))
+    out["total"] = total.value
+    return out
 
 
 def load_env(data):

@@ -25,6 +25,7 @@
 #include <numeric>
 
 #include "common.h"
+#include "env_dist.h"
 #include "kernels.h"
 #include "build_kernels.h"
 #include <hipcub/hipcub.hpp>
@@ -160,6 +161,10 @@ struct lpt_probe {
     lpt_device *dev = nullptr;
     DProbe d{};
     void *rgbe = nullptr;
+    // SPEC §18: the sampling distribution, built on first use (probe_env) — a probe never sampled costs nothing for it
+    int env_state = 0;         // 0: not built, 1: built (env), 2: the probe has none (black)
+    void *env_buf = nullptr;   // rows then cols, 16-byte entries
+    DEnv env{};
 };
 
 enum { ST_RAYGEN = 0, ST_INTERSECT, ST_SHADE, ST_SHADOW, ST_ACCUM, ST_ASVGF, ST_EXCHANGE, ST_PRIMARY, ST_PATH, ST_COUNT };
@@ -228,12 +233,13 @@ struct lpt_renderer {
     // wavefronts of at most this many rays run every bounce behind the primary hits in ONE launch (k_path: no chip-wide barrier per
     // bounce); larger ones take the per-bounce launches, whose drains are then a few per cent.  LPT_OPT_PATH_RAYS; 0: never
     uint32_t path_rays = kPathRays;
-    uint32_t path_waves_per_cu = 16;   // k_path: 4 waves per SIMD (kernels.h LPT_PATH_ATTR)
+    uint32_t path_waves_per_cu = 16;   // k_path: 4 waves per SIMD (kernels.h LPT_PATH_WAVES)
     int path_refill = 32;              // k_path: a batch of lanes is shaded (and idle lanes start new paths) when at most this many lanes are tracing
     uint64_t n_recorded = 0, n_wavefronts = 0;   // raytrace() calls recorded / wavefronts submitted so far (lpt_renderer_get_submission_stats)
     int mode = LPT_BLIT_PATHTRACE;
     // build-only knobs
     uint32_t max_bounces = 3, user_seed = 0;
+    int env_sampling = 0;      // SPEC §18 (lpt_renderer_set_env_sampling): the ENV kernels while the bound probe has a distribution
     float vfov = 0.78539816339744830962f;
     uint32_t rank = 0, world = 1, tile_w = 32, tile_h = 8;
     std::vector<uint32_t> weights;   // tile-ownership weights of the ranks (empty = every rank 1: tile id mod world)
@@ -975,6 +981,90 @@ int lpt_probe_upload(lpt_device *dev, const uint8_t *rgbe8, uint32_t w, uint32_t
     return LPT_OK;
 }
 
+static inline float bits_as_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
+// The probe's distribution (SPEC §18; env_dist.cpp) on the device, built the first time it is asked for; false: the probe has none.
+// The texels come back from the device, so that a probe keeps no host copy for a mode it may never be used with.
+static int probe_env(lpt_probe *p, bool &has) {
+    if (!p->env_state) {
+        const uint32_t W = p->d.w, H = p->d.h;
+        std::vector<uint8_t> rgbe((size_t)W * H * 4);
+        HIP_TRY(hipSetDevice(p->dev->ordinal));
+        HIP_TRY(hipMemcpy(rgbe.data(), p->rgbe, rgbe.size(), hipMemcpyDeviceToHost));
+        lpt::EnvDist d;
+        if (lpt::env_distribution(rgbe.data(), W, H, d) > 0.0) {
+            const size_t n = (size_t)W * H;
+            std::vector<float4> tab(H + n);
+            for (uint32_t y = 0; y < H; ++y) tab[y] = make_float4(d.row_q[y], bits_as_float(d.row_alias[y]), 0.0f, 0.0f);
+            for (size_t i = 0; i < n; ++i) {
+                const size_t a = i - i % W + d.col_alias[i];   // the alias's place: same row
+                tab[H + i] = make_float4(d.col_q[i], bits_as_float(d.col_alias[i]), d.pdf_uv[i], d.pdf_uv[a]);
+            }
+            HIP_TRY(hipMalloc(&p->env_buf, tab.size() * sizeof(float4)));
+            HIP_TRY(hipMemcpy(p->env_buf, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
+            const float4 *b = (const float4 *)p->env_buf;
+            p->env = DEnv{b, b + H, W, H};
+            p->env_state = 1;
+        } else {
+            p->env_state = 2;
+        }
+    }
+    has = p->env_state == 1;
+    return LPT_OK;
+}
+
+static int env_alloc(DevMem &m, size_t bytes) {
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, bytes));
+    m.reset(p);
+    return LPT_OK;
+}
+
+int lpt_probe_sample(lpt_device *dev, lpt_probe *probe, const float *u, uint32_t n, float *dirs, float *pdf_s, float *radiance) {
+    if (!dev || !probe || (n && (!u || !dirs || !pdf_s || !radiance))) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_sample: null");
+    if (probe->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_sample: the probe belongs to another device");
+    if (!n) return LPT_OK;
+    bool has = false;
+    TRY(probe_env(probe, has));
+    if (!has) {
+        std::fill(dirs, dirs + 3 * (size_t)n, 0.0f); std::fill(pdf_s, pdf_s + n, 0.0f); std::fill(radiance, radiance + 3 * (size_t)n, 0.0f);
+        return LPT_OK;
+    }
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    DevMem du, dd, dp, dr;
+    TRY(env_alloc(du, sizeof(float) * 6 * (size_t)n));
+    TRY(env_alloc(dd, sizeof(float) * 3 * (size_t)n));
+    TRY(env_alloc(dp, sizeof(float) * (size_t)n));
+    TRY(env_alloc(dr, sizeof(float) * 3 * (size_t)n));
+    HIP_TRY(hipMemcpy(du.get(), u, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_env_sample, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, probe->d, probe->env, as<const float>(du), n,
+                       as<float>(dd), as<float>(dp), as<float>(dr));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    HIP_TRY(hipMemcpy(dirs, dd.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pdf_s, dp.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(radiance, dr.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
+    return LPT_OK;
+}
+
+int lpt_probe_pdf(lpt_device *dev, lpt_probe *probe, const float *dirs, uint32_t n, float *pdf_e) {
+    if (!dev || !probe || (n && (!dirs || !pdf_e))) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_pdf: null");
+    if (probe->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_pdf: the probe belongs to another device");
+    if (!n) return LPT_OK;
+    bool has = false;
+    TRY(probe_env(probe, has));
+    if (!has) { std::fill(pdf_e, pdf_e + n, 0.0f); return LPT_OK; }
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    DevMem dd, dp;
+    TRY(env_alloc(dd, sizeof(float) * 3 * (size_t)n));
+    TRY(env_alloc(dp, sizeof(float) * (size_t)n));
+    HIP_TRY(hipMemcpy(dd.get(), dirs, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_env_pdf, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, probe->env, as<const float>(dd), n, as<float>(dp));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    HIP_TRY(hipMemcpy(pdf_e, dp.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    return LPT_OK;
+}
+
 int lpt_probe_destroy(lpt_probe *p) {
     if (!p) return LPT_OK;
     hipSetDevice(p->dev->ordinal);
@@ -983,6 +1073,7 @@ int lpt_probe_destroy(lpt_probe *p) {
     for (lpt_renderer *r : p->dev->renderers)   // a renderer still bound to it falls back to the 1x1 default probe (renderer.rs:693-696)
         if (r->probe == p) r->probe = nullptr;
     if (p->rgbe) hipFree(p->rgbe);
+    if (p->env_buf) hipFree(p->env_buf);
     delete p;
     return LPT_OK;
 }
@@ -1370,6 +1461,17 @@ int lpt_renderer_set_max_bounces(lpt_renderer *r, uint32_t b) {
     r->max_bounces = b;
     return LPT_OK;
 }
+int lpt_renderer_set_env_sampling(lpt_renderer *r, int flag) {
+    if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_env_sampling: null");
+    FLUSH_OR_RETURN(r);
+    r->env_sampling = flag ? 1 : 0;
+    return LPT_OK;
+}
+int lpt_renderer_get_env_sampling(const lpt_renderer *r, int *flag) {
+    if (!r || !flag) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_get_env_sampling: null");
+    *flag = r->env_sampling;
+    return LPT_OK;
+}
 int lpt_renderer_set_seed(lpt_renderer *r, uint32_t s) {
     if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_seed: null");
     FLUSH_OR_RETURN(r);
@@ -1722,6 +1824,10 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
     }
 
     DProbe probe = r->probe ? r->probe->d : DProbe{(const uint8_t *)r->default_probe, 1u, 1u};
+    // SPEC §18: the ENV kernels while the mode is on and the bound probe has a distribution; otherwise exactly the default launches
+    bool env = false;
+    if (r->env_sampling && r->probe) TRY(probe_env(const_cast<lpt_probe *>(r->probe), env));
+    const DEnv ev = env ? r->probe->env : DEnv{};
     DNoise nz{(const uint8_t *)r->noise, r->noise_w, r->noise_h, (r->use_noise && r->noise) ? 1u : 0u};
     const DScene &sc = r->sg->d;
     if (r->timings) { r->ring_pos++; harvest_slot(r, cur_slot(r)); }
@@ -1832,7 +1938,13 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
                     stage_begin(r, ST_PATH, s, slot);
                     const uint32_t pblocks = std::min<uint32_t>(div_up(n_rays, kTraceBlock), std::max(8u, (cus * r->path_waves_per_cu) & ~7u));
                     const size_t plds = lds + kPathLdsExtra;   // stacks + sRGB table + per-bounce counters
-                    if (denoise) {
+                    if (env) {
+                        if (denoise) {
+                            if (r->stats) hipLaunchKernelGGL((k_path<true, true, true, DEnv>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill, ev);
+                            else hipLaunchKernelGGL((k_path<true, false, true, DEnv>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill, ev);
+                        } else if (r->stats) hipLaunchKernelGGL((k_path<false, true, true, DEnv>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill, ev);
+                        else hipLaunchKernelGGL((k_path<false, false, true, DEnv>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill, ev);
+                    } else if (denoise) {
                         if (r->stats) hipLaunchKernelGGL((k_path<true, true>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill);
                         else hipLaunchKernelGGL((k_path<true, false>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill);
                     } else if (r->stats) hipLaunchKernelGGL((k_path<false, true>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill);
@@ -1844,7 +1956,12 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
                 const uint32_t seed = seed0 + t;     // += 1 per bounce (:453, :487)
                 const Queue qin = w->q[b & 1u], qout = w->q[(b + 1u) & 1u];
                 stage_begin(r, ST_SHADE, s, slot);            // :471-480, :502-508
-                if (denoise && b == 0u)  // PrimaryRayPass: bounce-0 shading + G-buffer + motion (renderer.rs:466-481)
+                if (env) {
+                    if (denoise && b == 0u)
+                        hipLaunchKernelGGL((k_shade<true, true, DEnv>), dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues, ev);
+                    else
+                        hipLaunchKernelGGL((k_shade<false, true, DEnv>), dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues, ev);
+                } else if (denoise && b == 0u)  // PrimaryRayPass: bounce-0 shading + G-buffer + motion (renderer.rs:466-481)
                     hipLaunchKernelGGL(k_shade<true>, dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues);
                 else
                     hipLaunchKernelGGL(k_shade<false>, dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues);

@@ -92,6 +92,9 @@ struct DScene {
 constexpr uint32_t kPairedBit = 0x40000000u;
 
 struct DProbe { const uint8_t *rgbe; uint32_t w, h; };
+// SPEC §18: the probe's sampling distribution (env_dist.cpp), given only to the ENV instantiations of shade_hit / k_shade / k_path.
+// rows[y] = {q, alias bits, -, -} (the marginal over rows); cols[y * w + x] = {q, alias bits, pdf_uv(x, y), pdf_uv(alias, y)}
+struct DEnv { const float4 *rows, *cols; uint32_t w, h; };
 struct DNoise { const uint8_t *rgba; uint32_t w, h, enabled; };
 
 // o.w = pdf of the sampling bounce (<0: camera), d.w = pixel slot bits, T.w = x | y << 13 | sample << 26.
@@ -1453,6 +1456,65 @@ __device__ __forceinline__ f3 env_lookup(const DProbe &pr, f3 d) {
     return r;
 }
 
+// ------------------------------------------------------------------ SPEC §18: environment sampling
+__device__ __forceinline__ DEnv env_arg() { return DEnv{nullptr, nullptr, 1u, 1u}; }   // the default instantiations: never read
+__device__ __forceinline__ DEnv env_arg(const DEnv &e) { return e; }
+constexpr float kTwoPiSq = 19.739208802178716f;   // 2 pi^2: d(omega) = 2 pi^2 sin(theta) du dv
+// A direction drawn from the probe's distribution and its density p_s (solid angle); false: no sample (sin(theta) <= 0).
+// r6..r9 pick the cell through the two alias tables (two dependent loads), r1 / r2 place the point inside it.
+__device__ __forceinline__ bool env_sample(const DEnv &ev, float r6, float r7, float r8, float r9, float r1, float r2, f3 &d, float &ps) {
+    const uint32_t W = ev.w, H = ev.h;
+    const uint32_t ry = min((uint32_t)(r6 * (float)H), H - 1u);
+    const float4 re = ev.rows[ry];
+    const uint32_t row = r7 < re.x ? ry : __float_as_uint(re.y);
+    const uint32_t rx = min((uint32_t)(r8 * (float)W), W - 1u);
+    const float4 ce = ev.cols[(size_t)row * W + rx];
+    const bool keep = r9 < ce.x;
+    const uint32_t col = keep ? rx : __float_as_uint(ce.y);
+    const float pdf_uv = keep ? ce.z : ce.w;
+    const float u = ((float)col + r1) / (float)W, v = ((float)row + r2) / (float)H;
+    float st, ct, sp, cp;
+    sincos2pi(v * 0.5f, st, ct);   // theta = pi v
+    sincos2pi(u, sp, cp);          // phi = 2 pi (u - 1/2): its sine and cosine are those of 2 pi u negated
+    sp = -sp; cp = -cp;
+    d = mk3(st * cp, ct, st * sp);
+    if (!(st > 0.0f)) return false;
+    ps = pdf_uv / (kTwoPiSq * st);
+    return ps > 0.0f;
+}
+// p_e(d): the density of direction d under the distribution, in the cell that env_lookup's (u, v) fall in
+__device__ __forceinline__ float env_pdf(const DEnv &ev, f3 d) {
+    const int W = (int)ev.w, H = (int)ev.h;
+    const float u = atan2_approx(d.z, d.x) * LPT_INV_2PI + 0.5f;
+    const float v = acos_approx(clampf(d.y, -1.0f, 1.0f)) * LPT_INV_PI;
+    int cx = (int)(u * (float)W), cy = (int)(v * (float)H);
+    cx = cx < 0 ? 0 : (cx > W - 1 ? W - 1 : cx);
+    cy = cy < 0 ? 0 : (cy > H - 1 ? H - 1 : cy);
+    const float s = sqrtf(max2(0.0f, 1.0f - d.y * d.y));
+    if (!(s > 0.0f)) return 0.0f;
+    return ev.cols[(size_t)cy * W + cx].z / (kTwoPiSq * s);
+}
+// lpt_probe_sample / lpt_probe_pdf: the functions shade_hit runs, one direction per thread.  u: n x {r6, r7, r8, r9, r1, r2};
+// a draw without a sample gives direction 0, density 0, radiance 0
+__global__ __launch_bounds__(kBlock) void k_env_sample(DProbe probe, DEnv ev, const float *u, uint32_t n, float *dirs, float *pdf_s, float *radiance) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *r = u + 6u * (size_t)i;
+    f3 d;
+    float ps = 0.0f;
+    f3 Le = mk3(0.f, 0.f, 0.f);
+    if (env_sample(ev, r[0], r[1], r[2], r[3], r[4], r[5], d, ps)) Le = env_lookup(probe, d);
+    else { d = mk3(0.f, 0.f, 0.f); ps = 0.0f; }
+    dirs[3u * (size_t)i] = d.x; dirs[3u * (size_t)i + 1u] = d.y; dirs[3u * (size_t)i + 2u] = d.z;
+    pdf_s[i] = ps;
+    radiance[3u * (size_t)i] = Le.x; radiance[3u * (size_t)i + 1u] = Le.y; radiance[3u * (size_t)i + 2u] = Le.z;
+}
+__global__ __launch_bounds__(kBlock) void k_env_pdf(DEnv ev, const float *dirs, uint32_t n, float *pdf_e) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    pdf_e[i] = env_pdf(ev, mk3(dirs[3u * (size_t)i], dirs[3u * (size_t)i + 1u], dirs[3u * (size_t)i + 2u]));
+}
+
 // ------------------------------------------------------------------ SPEC §15 helpers (denoiser path)
 __device__ __forceinline__ uint32_t oct_encode(f3 n) {
     float l1 = (fabsf(n.x) + fabsf(n.y)) + fabsf(n.z);
@@ -1515,9 +1577,9 @@ struct ShadeOut {
 // surface -> shading record, textures, NEE shadow ray and BSDF sample.  Shared by k_shade (one thread per queued ray,
 // radiance deposited into Lsum) and k_path (a lane carries its path through every bounce, radiance kept in registers):
 // `load_o()` returns the ray's (origin, pdf) record — only emitter hits and the G-buffer need it —, `add_l(r, g, b)`
-// adds to the path's radiance.
-template <bool GBUF, typename LoadO, typename AddL>
-__device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe, const DNoise &nz, const FrameParams &p, const float *s_lut,
+// adds to the path's radiance.  ENV (SPEC §18): next-event estimation samples the probe too (distribution `ev`), and a miss is MIS-weighted.
+template <bool GBUF, bool ENV, typename LoadO, typename AddL>
+__device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe, const DEnv &ev, const DNoise &nz, const FrameParams &p, const float *s_lut,
                                           const uint32_t bounce, const bool last_bounce, const uint32_t seed_base, const float inv_nl, const GBufArgs &gb,
                                           const float4 d4, const float4 T4, const float4 h4, LoadO load_o, AddL add_l, ShadeOut &out) {
     out.want_next = false; out.want_shadow = false; out.is_surface = false;
@@ -1533,7 +1595,16 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
         g_P = mk3(fmaf(d.x, h4.x, o4.x), fmaf(d.y, h4.x, o4.y), fmaf(d.z, h4.x, o4.z));
     }
     if (prim == 0xFFFFFFFFu) {
-        const f3 e = env_lookup(probe, d);
+        f3 e = env_lookup(probe, d);
+        if (ENV) {
+            const float pdf_prev = load_o().w;
+            if (pdf_prev >= 0.0f) {   // not a camera ray: the BSDF strategy's MIS weight against the probe's
+                const float pe = (sc.n_lights ? 0.5f : 1.0f) * env_pdf(ev, d);
+                const float pb2 = pdf_prev * pdf_prev;
+                const float w = pb2 / (pb2 + pe * pe);
+                e = mk3(e.x * w, e.y * w, e.z * w);
+            }
+        }
         add_l(T.x * e.x, T.y * e.y, T.z * e.z);
     } else if (prim & LPT_LIGHT_BIT) {
         const float4 *Lt = reinterpret_cast<const float4 *>(sc.lights + (prim & ~LPT_LIGHT_BIT));
@@ -1603,12 +1674,43 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
             float r0 = rng_next(rg), r1 = rng_next(rg), r2 = rng_next(rg);
             float r3 = rng_next(rg), r4 = rng_next(rg), r5 = rng_next(rg);
             noise_shift(nz, x, y, seed_counter, r4, r5);
+            float r6 = 0.0f, r7 = 0.0f, r8 = 0.0f, r9 = 0.0f;
+            if (ENV) { r6 = rng_next(rg); r7 = rng_next(rg); r8 = rng_next(rg); r9 = rng_next(rg); }
+            const float p_env = sc.n_lights ? 0.5f : 1.0f;   // ENV: the probe's share of the light samples
             float am = max2(max2(fabsf(P.x), fabsf(P.y)), fabsf(P.z));
             float eps = 1.0e-4f * (1.0f + am);
             const f3 Po = mk3(P.x + Ng.x * eps, P.y + Ng.y * eps, P.z + Ng.z * eps);
             // next-event estimation
-            if (sc.n_lights) {
-                uint32_t li = (uint32_t)(r0 * (float)sc.n_lights);
+            if (ENV && r0 < p_env) {   // the probe (SPEC §18)
+                f3 wi;
+                float ps;
+                if (env_sample(ev, r6, r7, r8, r9, r1, r2, wi, ps)) {
+                    Hit hl;
+                    hl.t = LPT_T_INF; hl.u = 0.f; hl.v = 0.f; hl.prim = 0xFFFFFFFFu;
+                    intersect_lights(sc, Po, wi, hl);   // a BSDF ray this way would stop at the light's front: not the probe's direction
+                    if (hl.prim == 0xFFFFFFFFu) {
+                        f3 f;
+                        float pb;
+                        bsdf_eval(sf, Ns, Ng, V, NoV, pspec, wi, f, pb);
+                        if (pb > 0.0f) {
+                            const f3 Le = env_lookup(probe, wi);
+                            const float pe = p_env * env_pdf(ev, wi);
+                            const float pe2 = pe * pe;
+                            const float wm = last_bounce ? 1.0f : pe2 / (pe2 + pb * pb);   // the last bounce: no BSDF ray carries the other half
+                            const float NoL = dot(Ns, wi);
+                            const float k = (NoL * wm) / (p_env * ps);
+                            f3 contrib = mk3(((T.x * f.x) * Le.x) * k, ((T.y * f.y) * Le.y) * k, ((T.z * f.z) * Le.z) * k);
+                            if (contrib.x > 0.0f || contrib.y > 0.0f || contrib.z > 0.0f) {
+                                out.want_shadow = true;
+                                out.so4 = make_float4(Po.x, Po.y, Po.z, LPT_T_INF);
+                                out.sd4 = make_float4(wi.x, wi.y, wi.z, d4.w);
+                                out.sc4 = make_float4(contrib.x, contrib.y, contrib.z, 0.f);
+                            }
+                        }
+                    }
+                }
+            } else if (sc.n_lights) {
+                uint32_t li = (uint32_t)((ENV ? (r0 - p_env) / (1.0f - p_env) : r0) * (float)sc.n_lights);
                 if (li > sc.n_lights - 1u) li = sc.n_lights - 1u;
                 const float4 *Lt = reinterpret_cast<const float4 *>(sc.lights + li);
                 const float4 n4 = Lt[0], t4 = Lt[1], b4 = Lt[2], lo4 = Lt[3];
@@ -1669,10 +1771,14 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
     }
 }
 
-template <bool GBUF>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) void k_shade(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue qin, const float4 *hits,
+// ENV (SPEC §18): `env...` is the probe's distribution, one DEnv; the default instantiations take no such argument.  The ENV ones
+// need more than 128 VGPRs and run at 3 waves per SIMD (168), where they do not spill
+template <bool GBUF, bool ENV = false, typename... Env>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ENV ? 3 : 4))) void k_shade(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue qin, const float4 *hits,
                                                   Queue qout, ShadowQueue sq, float4 *Lsum, FrameCounters *ctr, int bounce,
-                                                  uint32_t seed_base, GBufArgs gb, int sorted) {
+                                                  uint32_t seed_base, GBufArgs gb, int sorted, Env... env) {
+    static_assert(sizeof...(Env) == (ENV ? 1u : 0u), "the ENV instantiations take the distribution, the others nothing");
+    const DEnv ev = env_arg(env...);
     __shared__ uint32_t lds[72];
     __shared__ float s_lut[256];
     // ONE RESERVATION FOR TWO ITERATIONS (round 6, log N).  A block reserves its slots in both outgoing queues with one returning atomic — on ONE word for the whole grid:
@@ -1690,7 +1796,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
     const uint32_t rounded = (count + 255u) & ~255u;  // keep whole blocks in the loop for the barriers
     uint32_t n_surface = 0;
     const bool last_bounce = (uint32_t)bounce + 1u >= p.max_bounces;
-    const float inv_nl = sc.n_lights ? 1.0f / (float)sc.n_lights : 0.0f;
+    const float inv_nl = sc.n_lights ? (ENV ? 0.5f : 1.0f) / (float)sc.n_lights : 0.0f;   // ENV: a rectangle light is picked with 1 - p_env = 1/2
     for (uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x; i0 < rounded; i0 += stride) {
         ShadeOut so;
         so.want_next = false; so.want_shadow = false; so.is_surface = false;
@@ -1698,7 +1804,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
         if (i < count) {
             const float4 d4 = ld_nt(qin.d + i), T4 = ld_nt(qin.T + i), h4 = ld_nt(hits + i);
             const uint32_t slot = __float_as_uint(d4.w);
-            shade_hit<GBUF>(sc, probe, nz, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, gb, d4, T4, h4,
+            shade_hit<GBUF, ENV>(sc, probe, ev, nz, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, gb, d4, T4, h4,
                             [&]() { return ld_nt(qin.o + i); },
                             [&](float r, float g, float b) {
                                 float4 L = Lsum[slot];
@@ -1793,13 +1899,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
 // 4 waves per SIMD (128 VGPRs; the allocator wants 150 and spills 15 dwords per lane around the shading batch): measured on a 1 M-ray
 // tile shard, 8 / 12 / 16 waves per CU -> 4.28 / 3.22 / 2.70 ms — the kernel is latency-bound and occupancy is worth more than the spills
 // cost (profiles/r04_experiments_ab.txt)
-#ifndef LPT_PATH_ATTR
-#define LPT_PATH_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
+// The ENV instantiations (SPEC §18: probe sampling in the shading batch) need more registers than that and run at 3 waves per SIMD
+// (168 VGPRs), which they fit without spilling.
+#ifndef LPT_PATH_WAVES
+#define LPT_PATH_WAVES(ENV) ((ENV) ? 3 : 4)
 #endif
 constexpr uint32_t kPathLdsExtra = 1024u + 3u * kMaxBounces * 4u;   // sRGB table + counters: what a wave needs besides its stacks
-template <bool GBUF, bool STATS>
-__global__ __launch_bounds__(kTraceBlock) LPT_PATH_ATTR void k_path(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue q0, const float4 *hits0, float4 *Lsum,
-                                                      FrameCounters *ctr, uint32_t seed0, GBufArgs gb, int refill) {
+template <bool GBUF, bool STATS, bool ENV = false, typename... Env>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(LPT_PATH_WAVES(ENV), LPT_PATH_WAVES(ENV)))) void k_path(
+        DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue q0, const float4 *hits0, float4 *Lsum, FrameCounters *ctr, uint32_t seed0, GBufArgs gb, int refill,
+        Env... env) {
+    static_assert(sizeof...(Env) == (ENV ? 1u : 0u), "the ENV instantiations take the distribution, the others nothing");
+    const DEnv ev = env_arg(env...);
     static_assert(kTraceBlock == 64, "one wave per block: the LDS hand-overs below are ordered by the wave's own program order");
     uint2 *stack = reinterpret_cast<uint2 *>(lds_dyn) + threadIdx.x;
     const uint32_t stack_bytes = sc.stack_entries * kTraceBlock * (uint32_t)sizeof(uint2);
@@ -1814,7 +1925,7 @@ __global__ __launch_bounds__(kTraceBlock) LPT_PATH_ATTR void k_path(DScene sc, D
     ChunkPuller pl;
     puller_init(pl, &ctr->phead[0], QC(ctr, 0));
     const uint32_t nb = p.max_bounces;
-    const float inv_nl = sc.n_lights ? 1.0f / (float)sc.n_lights : 0.0f;
+    const float inv_nl = sc.n_lights ? (ENV ? 0.5f : 1.0f) / (float)sc.n_lights : 0.0f;   // ENV: a rectangle light is picked with 1 - p_env = 1/2
     const int min_batch = 64 - refill;
     uint32_t n_nodes = 0, n_tris = 0, s_nodes = 0, s_tris = 0;
     uint32_t w_steps = 0, w_live = 0, w_node = 0, w_tri = 0;
@@ -1864,7 +1975,7 @@ __global__ __launch_bounds__(kTraceBlock) LPT_PATH_ATTR void k_path(DScene sc, D
                 const float4 d4 = make_float4(rs.d.x, rs.d.y, rs.d.z, __uint_as_float(vslot));
                 const float4 T4 = make_float4(T.x, T.y, T.z, __uint_as_float(pxy));
                 const float4 h4 = make_float4(rs.best.t, rs.best.u, rs.best.v, __uint_as_float(rs.best.prim));
-                shade_hit<GBUF>(sc, probe, nz, p, s_lut, bounce, bounce + 1u >= nb, seed0 + bounce + 1u, inv_nl, gb, d4, T4, h4,
+                shade_hit<GBUF, ENV>(sc, probe, ev, nz, p, s_lut, bounce, bounce + 1u >= nb, seed0 + bounce + 1u, inv_nl, gb, d4, T4, h4,
                                 [&]() { return make_float4(rs.o.x, rs.o.y, rs.o.z, pdf); },
                                 [&](float r, float g, float b) { L.x = L.x + r; L.y = L.y + g; L.z = L.z + b; }, so);
                 if (so.is_surface) atomicAdd(&s_cnt[128u + bounce], 1u);
