@@ -97,6 +97,23 @@ impl Scene {
         check(unsafe { ffi::lpt_scene_add_material(self.h, material, &mut out) })?;
         Ok(out)
     }
+    /// SPEC.md §19: a point / spot / directional light (KHR_lights_punctual); records from `punctual_light`
+    pub fn add_punctual_light(&mut self, light: &ffi::lpt_punctual_light) -> Result<u32, Error> {
+        let mut out = 0u32;
+        check(unsafe { ffi::lpt_scene_add_punctual_light(self.h, light, &mut out) })?;
+        Ok(out)
+    }
+    pub fn set_punctual_light(&mut self, index: u32, light: &ffi::lpt_punctual_light) -> Result<(), Error> {
+        check(unsafe { ffi::lpt_scene_set_punctual_light(self.h, index, light) })
+    }
+    pub fn punctual_lights(&self) -> Result<Vec<ffi::lpt_punctual_light>, Error> {
+        let mut n = 0u32;
+        check(unsafe { ffi::lpt_scene_punctual_count(self.h, &mut n) })?;
+        let zero = ffi::lpt_punctual_light { position: [0.0; 4], direction: [0.0; 4], color: [0.0; 4], cone: [0.0; 4] };
+        let mut out = vec![zero; n as usize];
+        check(unsafe { ffi::lpt_scene_get_punctual_lights(self.h, 0, n, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
     pub fn add_image(&mut self, rgba8: &[u8], width: u32, height: u32) -> Result<u32, Error> {
         assert!(rgba8.len() >= (width as usize) * (height as usize) * 4);
         let mut out = 0u32;
@@ -134,6 +151,31 @@ impl SceneGPU {
         check(unsafe { ffi::lpt_scene_gpu_update_instances(self.h(), scene.h, &mut n) })?;
         Ok(n)
     }
+    /// after `Scene::set_punctual_light`: the punctual lights to the device again, nothing else (same count; frames recorded against the
+    /// old lights are submitted first)
+    pub fn update_punctual(&self, scene: &Scene) -> Result<(), Error> {
+        check(unsafe { ffi::lpt_scene_gpu_update_punctual(self.h(), scene.h) })
+    }
+    /// the shading kernels' punctual-light function on the GPU (SPEC.md §19): points -> (direction to the light, distance, incident term)
+    pub fn sample_punctual(&self, device: &Device, light: u32, points: &[[f32; 3]]) -> Result<(Vec<[f32; 3]>, Vec<f32>, Vec<[f32; 3]>), Error> {
+        let n = points.len();
+        let (mut wi, mut dist, mut e) = (vec![[0f32; 3]; n], vec![0f32; n], vec![[0f32; 3]; n]);
+        check(unsafe {
+            ffi::lpt_scene_gpu_sample_punctual(device.h(), self.h(), light, points.as_ptr() as *const f32, n as u32,
+                                               wi.as_mut_ptr() as *mut f32, dist.as_mut_ptr(), e.as_mut_ptr() as *mut f32)
+        })?;
+        Ok((wi, dist, e))
+    }
+}
+
+/// SPEC.md §19: the record of a KHR_lights_punctual light (`kind`: `ffi::LPT_PUNCTUAL_POINT` / `_SPOT` / `_DIRECTIONAL`); angles in radians
+pub fn punctual_light(kind: u32, position: [f32; 3], direction: [f32; 3], color: [f32; 3], intensity: f32, range: f32, inner_angle: f32,
+                      outer_angle: f32) -> Result<ffi::lpt_punctual_light, Error> {
+    let mut l = ffi::lpt_punctual_light { position: [0.0; 4], direction: [0.0; 4], color: [0.0; 4], cone: [0.0; 4] };
+    check(unsafe {
+        ffi::lpt_punctual_light_make(kind, position.as_ptr(), direction.as_ptr(), color.as_ptr(), intensity, range, inner_angle, outer_angle, &mut l)
+    })?;
+    Ok(l)
 }
 
 /// reference `crates/lib/src/scene.rs:72` `ProbeGPU::new`: RGBE8, equirectangular

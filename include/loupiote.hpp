@@ -75,11 +75,39 @@ class Scene {  // scene.rs:30-54
     uint32_t add_image(const uint8_t *rgba8, uint32_t w, uint32_t h) { uint32_t id = 0; check(lpt_scene_add_image(h_, rgba8, w, h, &id)); return id; }
     uint32_t add_light(const lpt_light &l) { uint32_t id = 0; check(lpt_scene_add_light(h_, &l, &id)); return id; }
     void set_light(uint32_t i, const lpt_light &l) { check(lpt_scene_set_light(h_, i, &l)); }
+    // SPEC.md §19: point / spot / directional lights (KHR_lights_punctual); records from point_light / spot_light / directional_light below
+    uint32_t add_punctual_light(const lpt_punctual_light &l) { uint32_t id = 0; check(lpt_scene_add_punctual_light(h_, &l, &id)); return id; }
+    void set_punctual_light(uint32_t i, const lpt_punctual_light &l) { check(lpt_scene_set_punctual_light(h_, i, &l)); }
+    std::vector<lpt_punctual_light> punctual_lights() const {
+        uint32_t n = 0;
+        check(lpt_scene_punctual_count(h_, &n));
+        std::vector<lpt_punctual_light> out(n);
+        check(lpt_scene_get_punctual_lights(h_, 0, n, out.data()));
+        return out;
+    }
     lpt_scene_counts counts() const { lpt_scene_counts c; check(lpt_scene_counts_get(h_, &c)); return c; }
 
    private:
     lpt_scene *h_ = nullptr;
 };
+
+using Vec3 = std::array<float, 3>;
+inline lpt_punctual_light point_light(const Vec3 &position, const Vec3 &color = {1.f, 1.f, 1.f}, float intensity = 1.f, float range = 0.f) {
+    lpt_punctual_light l;
+    check(lpt_punctual_light_make(LPT_PUNCTUAL_POINT, position.data(), nullptr, color.data(), intensity, range, 0.f, 0.f, &l));
+    return l;
+}
+inline lpt_punctual_light spot_light(const Vec3 &position, const Vec3 &direction, const Vec3 &color = {1.f, 1.f, 1.f}, float intensity = 1.f, float range = 0.f,
+                                     float inner_angle = 0.f, float outer_angle = 0.78539816f) {
+    lpt_punctual_light l;
+    check(lpt_punctual_light_make(LPT_PUNCTUAL_SPOT, position.data(), direction.data(), color.data(), intensity, range, inner_angle, outer_angle, &l));
+    return l;
+}
+inline lpt_punctual_light directional_light(const Vec3 &direction, const Vec3 &color = {1.f, 1.f, 1.f}, float intensity = 1.f) {
+    lpt_punctual_light l;
+    check(lpt_punctual_light_make(LPT_PUNCTUAL_DIRECTIONAL, nullptr, direction.data(), color.data(), intensity, 0.f, 0.f, 0.f, &l));
+    return l;
+}
 
 namespace loaders {  // loaders/gltf.rs:46-161
 inline void load_gltf(const uint8_t *data, size_t size, Scene &scene) { check(lpt_load_gltf(scene.handle(), data, size)); }
@@ -108,6 +136,12 @@ class SceneGPU {  // scene.rs:56-64,151-188
     /// re-bake every instance and rebuild the BVH on the GPU (for edits too large for a refit)
     void rebuild(const Scene &scene) { check(lpt_scene_gpu_rebuild(h_, scene.handle())); }
     uint32_t update_instances(const Scene &scene) { uint32_t n = 0; check(lpt_scene_gpu_update_instances(h_, scene.handle(), &n)); return n; }
+    /// SPEC.md §19: the punctual lights to the device again, nothing else (same count; recorded frames are submitted first and see the old lights)
+    void update_punctual(const Scene &scene) { check(lpt_scene_gpu_update_punctual(h_, scene.handle())); }
+    /// the shading kernels' punctual-light function on the GPU: points[n][3] -> wi[n][3], dist[n], E[n][3]
+    void sample_punctual(const Device &device, uint32_t light, const float *points, uint32_t n, float *wi, float *dist, float *E) const {
+        check(lpt_scene_gpu_sample_punctual(device.inner(), h_, light, points, n, wi, dist, E));
+    }
 
    private:
     SceneGPU() = default;

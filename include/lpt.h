@@ -85,6 +85,19 @@ typedef struct lpt_light {
     float origin[4];    /* xyz centre,         w = radiance (white)         */
 } lpt_light;
 
+/* new (SPEC.md §19; no reference counterpart: the reference's Scene carries rectangle lights only, crates/lib/src/scene.rs:33):
+ * a punctual (delta) light as glTF's KHR_lights_punctual describes it.  64 bytes, four float[4] rows.  Fill it with
+ * lpt_punctual_light_make: `cone` is derived data. */
+#define LPT_PUNCTUAL_POINT 0u
+#define LPT_PUNCTUAL_SPOT 1u
+#define LPT_PUNCTUAL_DIRECTIONAL 2u
+typedef struct lpt_punctual_light {
+    float position[4];  /* xyz world position (point, spot); w = type: 0 point, 1 spot, 2 directional, as a float   */
+    float direction[4]; /* xyz unit direction the light shines ALONG (spot, directional); w = range, 0 = unlimited    */
+    float color[4];     /* rgb = colour x intensity (candela for point / spot, lux for directional); w unused, 0      */
+    float cone[4];      /* x = cos(outer), y = 1 / max(cos(inner) - cos(outer), 1e-6); z, w unused, 0                */
+} lpt_punctual_light;
+
 /* replaces: albedo_rtx::uniforms::Instance as built by BLASArray::add_instance
  * (crates/lib/src/loaders/gltf.rs:141-145) and edited by Instance::set_transform
  * (crates/standalone/src/lib.rs:117-121). */
@@ -233,6 +246,22 @@ int lpt_scene_set_light(lpt_scene *scene, uint32_t index, const lpt_light *l);
 /* replaces: Light::new() (crates/lib/src/scene.rs:50) */
 int lpt_light_default(lpt_light *out);
 
+/* build-only extension (SPEC.md §19; the reference has no punctual lights): the scene's point / spot / directional lights.
+ * Unlike every other scene array there is NO dummy element 0: a fresh scene has none, and a scene without any renders
+ * exactly what it rendered before they existed.  `direction` is normalised on entry.  LPT_ERR_INVALID_ARG (and nothing
+ * appended or changed) for a non-finite field, an unknown type, a zero direction of a spot or directional light, a
+ * negative range or colour. */
+int lpt_scene_add_punctual_light(lpt_scene *scene, const lpt_punctual_light *l, uint32_t *out_index);
+int lpt_scene_set_punctual_light(lpt_scene *scene, uint32_t index, const lpt_punctual_light *l);
+int lpt_scene_punctual_count(const lpt_scene *scene, uint32_t *out);
+int lpt_scene_get_punctual_lights(const lpt_scene *s, uint32_t first, uint32_t count, lpt_punctual_light *dst);
+/* build-only extension: the record of a light of `type` (LPT_PUNCTUAL_*) from what KHR_lights_punctual states: colour (rgb, NULL =
+ * white) x intensity, range (0 = unlimited), the spot's cone angles in radians (0 <= inner < outer <= pi/2; ignored for the other
+ * types), position / direction (3 floats each; NULL = the origin / -Z, glTF's default axis).  Fills the derived `cone` fields (in
+ * double, rounded once).  The same checks as lpt_scene_add_punctual_light, plus the cone angles. */
+int lpt_punctual_light_make(uint32_t type, const float *position, const float *direction, const float *color, float intensity,
+                            float range, float inner_angle, float outer_angle, lpt_punctual_light *out);
+
 /* Read-back of the flat arrays (the reference exposes them as pub Vec fields). */
 int lpt_scene_get_materials(const lpt_scene *s, uint32_t first, uint32_t count, lpt_material *dst);
 int lpt_scene_get_entries(const lpt_scene *s, uint32_t first, uint32_t count, lpt_blas_entry *dst);
@@ -301,6 +330,19 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *scene_gpu, const lpt_scene *sc
  * keeps a topology that no longer fits.  Renderers bound to this lpt_scene_gpu keep working. */
 int lpt_scene_gpu_rebuild(lpt_scene_gpu *scene_gpu, const lpt_scene *scene);
 int lpt_scene_gpu_stats(const lpt_scene_gpu *sg, lpt_accel_stats *out);
+/* build-only extension (SPEC.md §19): after lpt_scene_set_punctual_light on the CPU scene, copies the punctual lights to the device
+ * again and nothing else — no bake, no refit: an animated lamp costs 64 bytes per light.  The scene must hold as many punctual lights
+ * as were uploaded (LPT_ERR_INVALID_ARG otherwise: lpt_scene_gpu_rebuild or a new upload takes a changed count).  Ordering, as for
+ * lpt_scene_gpu_update_instances: raytrace() calls that are recorded but not yet submitted are submitted FIRST and see the lights as
+ * they were when they were recorded; the call then waits for the device before it writes.  Call lpt_renderer_reset_accumulation as
+ * after any scene change. */
+int lpt_scene_gpu_update_punctual(lpt_scene_gpu *scene_gpu, const lpt_scene *scene);
+/* build-only extension (SPEC.md §19), for tests and tools in the manner of lpt_probe_sample: the function the shading kernels run for
+ * punctual light `light_index`, once per point of points[n][3] -> wi[n][3] (unit direction towards the light), dist[n] (the shadow
+ * ray's length before the 0.999 factor; 1e30, the renderer's infinity, for a directional light) and E[n][3] (the incident term:
+ * colour x intensity x 1/d^2 x range window x cone window); all zero where there is no sample (the point IS the light).  Blocking; host arrays. */
+int lpt_scene_gpu_sample_punctual(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t light_index, const float *points, uint32_t n,
+                                  float *wi, float *dist, float *E);
 
 /* replaces: ProbeGPU::new(device, queue, data, width, height)
  * (crates/lib/src/scene.rs:72-121): 4 bytes/pixel RGBE8, equirectangular. */

@@ -36,6 +36,8 @@ MATERIAL_DT = np.dtype([("color", "<f4", 4), ("roughness", "<f4"), ("reflectivit
                         ("albedo_texture", "<u4"), ("mra_texture", "<u4")])
 VERTEX_DT = np.dtype([("position", "<f4", 4), ("normal", "<f4", 4)])
 LIGHT_DT = np.dtype([("normal", "<f4", 4), ("tangent", "<f4", 4), ("bitangent", "<f4", 4), ("origin", "<f4", 4)])
+PUNCTUAL_DT = np.dtype([("position", "<f4", 4), ("direction", "<f4", 4), ("color", "<f4", 4), ("cone", "<f4", 4)])   # lpt_punctual_light (SPEC §19)
+PUNCTUAL_POINT, PUNCTUAL_SPOT, PUNCTUAL_DIRECTIONAL = 0, 1, 2
 INSTANCE_DT = np.dtype([("model_to_world", "<f4", 16), ("blas_index", "<u4"), ("material_index", "<u4"),
                         ("pad", "<u4", 2)])
 ENTRY_DT = np.dtype([("vertex_offset", "<u4"), ("vertex_count", "<u4"), ("index_offset", "<u4"),
@@ -89,6 +91,11 @@ SIGNATURES = {
     "lpt_scene_add_light": (_i, [_vp, _vp, _pu32]),
     "lpt_scene_set_light": (_i, [_vp, _u32, _vp]),
     "lpt_light_default": (_i, [_vp]),
+    "lpt_scene_add_punctual_light": (_i, [_vp, _vp, _pu32]),
+    "lpt_scene_set_punctual_light": (_i, [_vp, _u32, _vp]),
+    "lpt_scene_punctual_count": (_i, [_vp, _pu32]),
+    "lpt_scene_get_punctual_lights": (_i, [_vp, _u32, _u32, _vp]),
+    "lpt_punctual_light_make": (_i, [_u32, _vp, _vp, _vp, _f, _f, _f, _f, _vp]),
     "lpt_scene_get_materials": (_i, [_vp, _u32, _u32, _vp]),
     "lpt_scene_get_entries": (_i, [_vp, _u32, _u32, _vp]),
     "lpt_scene_get_vertices": (_i, [_vp, _u32, _u32, _vp]),
@@ -108,6 +115,8 @@ SIGNATURES = {
     "lpt_scene_gpu_stats": (_i, [_vp, C.POINTER(AccelStats)]),
     "lpt_scene_gpu_rebuild": (_i, [_vp, _vp]),
     "lpt_scene_gpu_update_instances": (_i, [_vp, _vp, C.POINTER(C.c_uint32)]),
+    "lpt_scene_gpu_update_punctual": (_i, [_vp, _vp]),
+    "lpt_scene_gpu_sample_punctual": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
     "lpt_probe_upload": (_i, [_vp, _vp, _u32, _u32, _pvp]),
     "lpt_probe_destroy": (_i, [_vp]),
     "lpt_env_distribution": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),

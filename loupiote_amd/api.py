@@ -182,6 +182,26 @@ class Scene:
         l = np.ascontiguousarray(light, A.LIGHT_DT).reshape(1)
         _check(A.lib().lpt_scene_set_light(self._h, int(index), A.ptr(l)))
 
+    # SPEC §19: point / spot / directional lights (KHR_lights_punctual); records from point_light / spot_light / directional_light
+    def add_punctual_light(self, light):
+        l = np.ascontiguousarray(light, A.PUNCTUAL_DT).reshape(1)
+        out = C.c_uint32()
+        _check(A.lib().lpt_scene_add_punctual_light(self._h, A.ptr(l), C.byref(out)))
+        return out.value
+
+    def set_punctual_light(self, index, light):
+        l = np.ascontiguousarray(light, A.PUNCTUAL_DT).reshape(1)
+        _check(A.lib().lpt_scene_set_punctual_light(self._h, int(index), A.ptr(l)))
+
+    def punctual_count(self):
+        n = C.c_uint32()
+        _check(A.lib().lpt_scene_punctual_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    @property
+    def punctual_lights(self):
+        return self._get(A.lib().lpt_scene_get_punctual_lights, A.PUNCTUAL_DT, self.punctual_count())
+
     def _get(self, fn, dt, count):
         out = np.zeros(count, dt)
         _check(fn(self._h, 0, count, A.ptr(out)))
@@ -226,6 +246,30 @@ def default_light():
     return l
 
 
+def _punctual(kind, position, direction, color, intensity, range, inner_angle, outer_angle):
+    f = lambda v: None if v is None else np.ascontiguousarray(v, np.float32).reshape(3)
+    pos, dr, col = f(position), f(direction), f(color)
+    l = np.zeros(1, A.PUNCTUAL_DT)
+    _check(A.lib().lpt_punctual_light_make(int(kind), A.ptr(pos), A.ptr(dr), A.ptr(col), float(intensity), float(range), float(inner_angle),
+                                           float(outer_angle), A.ptr(l)))
+    return l
+
+
+def point_light(position, color=(1.0, 1.0, 1.0), intensity=1.0, range=0.0):
+    """KHR_lights_punctual `point` (SPEC.md §19): intensity in candela, range 0 = unlimited -> a PUNCTUAL_DT record"""
+    return _punctual(A.PUNCTUAL_POINT, position, None, color, intensity, range, 0.0, 0.0)
+
+
+def spot_light(position, direction, color=(1.0, 1.0, 1.0), intensity=1.0, range=0.0, inner_angle=0.0, outer_angle=np.pi / 4):
+    """KHR_lights_punctual `spot`: shines along `direction`, full inside inner_angle, nothing outside outer_angle (radians)"""
+    return _punctual(A.PUNCTUAL_SPOT, position, direction, color, intensity, range, inner_angle, outer_angle)
+
+
+def directional_light(direction, color=(1.0, 1.0, 1.0), intensity=1.0):
+    """KHR_lights_punctual `directional`: shines along `direction` from infinitely far, intensity in lux"""
+    return _punctual(A.PUNCTUAL_DIRECTIONAL, None, direction, color, intensity, 0.0, 0.0, 0.0)
+
+
 class SceneGPU:
     """scene.rs:151 `SceneGPU::new_from_scene(&Scene, &Device, &Queue)`."""
 
@@ -258,6 +302,20 @@ class SceneGPU:
     def rebuild(self, scene):
         """re-bake every instance and rebuild the BVH on the GPU (for edits too large for a refit)"""
         _check(A.lib().lpt_scene_gpu_rebuild(self._h, scene._h))
+
+    def update_punctual(self, scene):
+        """after `scene.set_punctual_light(...)`: the punctual lights to the device again, nothing else (same count required).
+        Recorded, not yet submitted raytrace() calls are submitted first and see the old lights, as with update_instances."""
+        _check(A.lib().lpt_scene_gpu_update_punctual(self._h, scene._h))
+
+    def sample_punctual(self, light_index, points):
+        """The function the shading kernels run for a punctual light (SPEC.md §19) on the GPU: points[n, 3] -> (wi[n, 3] towards the
+        light, dist[n] (1e30: directional), E[n, 3] the incident term); zeros where there is no sample."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        wi, dist, E = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+        _check(A.lib().lpt_scene_gpu_sample_punctual(self._dev.inner(), self._h, int(light_index), A.ptr(pts), n, A.ptr(wi), A.ptr(dist), A.ptr(E)))
+        return wi, dist, E
 
     def trace_closest(self, origins, dirs):
         o = np.ascontiguousarray(origins, np.float32)

@@ -34,6 +34,7 @@ struct lpt_scene {
     std::vector<lpt_instance> instances;
     std::vector<lpt_light> lights;
     std::vector<lpt::Image> images;
+    std::vector<lpt_punctual_light> punctual;   // SPEC §19: point / spot / directional lights; no dummy element, a fresh scene has none
 };
 
 namespace lpt {

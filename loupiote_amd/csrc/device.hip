@@ -146,6 +146,7 @@ struct lpt_scene_gpu {
     float max_abs = 0.f;            // the scene's largest |coordinate|: d.pad_abs = kScenePad x this (host build: Accel::max_abs; GPU build: the bounds pass; refit: the root box)
     DevTree tree;
     DevMem tri_verts, materials, lights, texels, images, srgb_lut, pair_texels, pair_images;
+    DevMem punctual;                // SPEC §19: lpt_punctual_light records (DScene::punctual)
     TexturePairs pairs;
     lpt_accel_stats stats{};
     // refit bookkeeping (lpt_scene_gpu_update_instances)
@@ -789,6 +790,19 @@ int lpt_scene_gpu_destroy(lpt_scene_gpu *sg) {
     return LPT_OK;
 }
 
+// the scene's punctual lights onto the device (SPEC §19) and into the view the kernels get; the caller has made sure nothing in flight reads the old ones
+static int upload_punctual(lpt_scene_gpu *sg, const lpt_scene &scene) {
+    static_assert(sizeof(lpt_punctual_light) == 4 * sizeof(float4), "a punctual light is four float4 rows");
+    const uint32_t n = (uint32_t)scene.punctual.size();
+    hipStream_t s = sg->dev->stream;
+    if (n != sg->d.n_punctual || !sg->punctual) TRY(dev_alloc(sg->punctual, sizeof(lpt_punctual_light) * std::max<size_t>(n, 1u)));
+    if (n) HIP_TRY(hipMemcpyAsync(sg->punctual.get(), scene.punctual.data(), sizeof(lpt_punctual_light) * (size_t)n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));   // the host vector is the caller's
+    sg->d.punctual = as<const float4>(sg->punctual);
+    sg->d.n_punctual = n;
+    return LPT_OK;
+}
+
 int lpt_scene_upload(lpt_device *dev, const lpt_scene *scene, lpt_scene_gpu **out) { return lpt_scene_upload_ex(dev, scene, LPT_ACCEL_BUILD_HOST_SAH, out); }
 
 int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags, lpt_scene_gpu **out) {
@@ -877,6 +891,7 @@ int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags,
     d.n_materials = (uint32_t)scene->materials.size();
     d.n_lights = (uint32_t)scene->lights.size();
     d.n_images = (uint32_t)scene->images.size();
+    TRY(upload_punctual(sg.get(), *scene));
     sg->stats.triangles = d.n_tris;
     sg->stats.node_bytes = (uint32_t)sizeof(Node8);
     sg->stats.tri_bytes = (uint32_t)sizeof(WoopTri);
@@ -943,10 +958,14 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
     if (!sg || !scene) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_rebuild: null");
     TRY(check_same_layout(sg, *scene, "lpt_scene_gpu_rebuild"));
     const uint32_t n = sg->stats.triangles;
-    if (n < 16u) return lpt_scene_gpu_update_instances(sg, scene, nullptr);
+    if (n < 16u) {
+        TRY(lpt_scene_gpu_update_instances(sg, scene, nullptr));   // (flushes and waits first)
+        return upload_punctual(sg, *scene);
+    }
     HIP_TRY(hipSetDevice(sg->dev->ordinal));
     TRY(flush_device(sg->dev));
     HIP_TRY(hipDeviceSynchronize());  // frames in flight on the renderers' streams still read what is rebuilt here
+    TRY(upload_punctual(sg, *scene));   // lights are scene data: a rebuild carries them too, whatever their number (SPEC §19)
     DevMem woop_prim;
     TRY(dev_alloc(woop_prim, sizeof(WoopTri) * (size_t)n));
     TRY(bake_instances(sg, *scene, every_instance(*scene), woop_prim.get()));
@@ -964,6 +983,40 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
     }
     sg->instances = scene->instances;  // what is baked now
     return st;
+}
+
+// SPEC §19: the punctual lights again, nothing else.  Recorded raytrace() calls are submitted first and see the lights they were recorded with
+// (the rule of lpt_scene_gpu_update_instances); the records are rewritten in place, so every stream of the device is waited for.
+int lpt_scene_gpu_update_punctual(lpt_scene_gpu *sg, const lpt_scene *scene) {
+    if (!sg || !scene) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_update_punctual: null");
+    if (scene->punctual.size() != (size_t)sg->d.n_punctual)
+        return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_update_punctual: the scene has %zu punctual lights, %u were uploaded (lpt_scene_gpu_rebuild or a new upload takes a changed count)",
+                    scene->punctual.size(), sg->d.n_punctual);
+    HIP_TRY(hipSetDevice(sg->dev->ordinal));
+    TRY(flush_device(sg->dev));
+    HIP_TRY(hipDeviceSynchronize());
+    return upload_punctual(sg, *scene);
+}
+
+int lpt_scene_gpu_sample_punctual(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t light_index, const float *points, uint32_t n, float *wi, float *dist, float *E) {
+    if (!dev || !sg || (n && (!points || !wi || !dist || !E))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_punctual: null");
+    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_punctual: the scene belongs to another device");
+    if (light_index >= sg->d.n_punctual) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_punctual: light %u of %u", light_index, sg->d.n_punctual);
+    if (!n) return LPT_OK;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    DevMem dp, dw, dd, de;
+    TRY(dev_alloc(dp, sizeof(float) * 3 * (size_t)n));
+    TRY(dev_alloc(dw, sizeof(float) * 3 * (size_t)n));
+    TRY(dev_alloc(dd, sizeof(float) * (size_t)n));
+    TRY(dev_alloc(de, sizeof(float) * 3 * (size_t)n));
+    HIP_TRY(hipMemcpy(dp.get(), points, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_punctual_sample, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, sg->d, light_index, as<const float>(dp), n, as<float>(dw), as<float>(dd), as<float>(de));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    HIP_TRY(hipMemcpy(wi, dw.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dist, dd.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(E, de.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
+    return LPT_OK;
 }
 
 // ============================================================================ ProbeGPU
@@ -1830,6 +1883,7 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
     const DEnv ev = env ? r->probe->env : DEnv{};
     DNoise nz{(const uint8_t *)r->noise, r->noise_w, r->noise_h, (r->use_noise && r->noise) ? 1u : 0u};
     const DScene &sc = r->sg->d;
+    const bool punct = sc.n_punctual != 0u;   // SPEC §19: the PUNCT kernels while the bound scene has punctual lights; otherwise exactly the default launches
     if (r->timings) { r->ring_pos++; harvest_slot(r, cur_slot(r)); }
 
     tk.stages = 0; tk.run = nullptr;
@@ -1938,17 +1992,19 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
                     stage_begin(r, ST_PATH, s, slot);
                     const uint32_t pblocks = std::min<uint32_t>(div_up(n_rays, kTraceBlock), std::max(8u, (cus * r->path_waves_per_cu) & ~7u));
                     const size_t plds = lds + kPathLdsExtra;   // stacks + sRGB table + per-bounce counters
-                    if (env) {
-                        if (denoise) {
-                            if (r->stats) hipLaunchKernelGGL((k_path<true, true, true, DEnv>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill, ev);
-                            else hipLaunchKernelGGL((k_path<true, false, true, DEnv>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill, ev);
-                        } else if (r->stats) hipLaunchKernelGGL((k_path<false, true, true, DEnv>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill, ev);
-                        else hipLaunchKernelGGL((k_path<false, false, true, DEnv>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill, ev);
-                    } else if (denoise) {
-                        if (r->stats) hipLaunchKernelGGL((k_path<true, true>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill);
-                        else hipLaunchKernelGGL((k_path<true, false>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill);
-                    } else if (r->stats) hipLaunchKernelGGL((k_path<false, true>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill);
-                    else hipLaunchKernelGGL((k_path<false, false>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], packet ? w->hits : (const float4 *)nullptr, w->Lsum, w->ctr, seed0, gb, r->path_refill);
+                    // the instantiation: G-buffer x stats x ENV (SPEC §18) x PUNCT (SPEC §19: the bound scene has punctual lights); without the last two, the kernels of every frame before them
+                    auto launch_path = [&](auto G, auto S, auto P) {
+                        constexpr bool g = decltype(G)::value, st = decltype(S)::value, pu = decltype(P)::value;
+                        const float4 *h0 = packet ? w->hits : (const float4 *)nullptr;
+                        if (env) hipLaunchKernelGGL((k_path<g, st, true, pu, DEnv>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], h0, w->Lsum, w->ctr, seed0, gb, r->path_refill, ev);
+                        else hipLaunchKernelGGL((k_path<g, st, false, pu>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], h0, w->Lsum, w->ctr, seed0, gb, r->path_refill);
+                    };
+                    auto path_gs = [&](auto P) {
+                        if (denoise) { if (r->stats) launch_path(std::true_type{}, std::true_type{}, P); else launch_path(std::true_type{}, std::false_type{}, P); }
+                        else if (r->stats) launch_path(std::false_type{}, std::true_type{}, P);
+                        else launch_path(std::false_type{}, std::false_type{}, P);
+                    };
+                    if (punct) path_gs(std::true_type{}); else path_gs(std::false_type{});
                     stage_end(r, s, slot);
                 }
             } else if (!path) {
@@ -1956,15 +2012,14 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
                 const uint32_t seed = seed0 + t;     // += 1 per bounce (:453, :487)
                 const Queue qin = w->q[b & 1u], qout = w->q[(b + 1u) & 1u];
                 stage_begin(r, ST_SHADE, s, slot);            // :471-480, :502-508
-                if (env) {
-                    if (denoise && b == 0u)
-                        hipLaunchKernelGGL((k_shade<true, true, DEnv>), dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues, ev);
-                    else
-                        hipLaunchKernelGGL((k_shade<false, true, DEnv>), dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues, ev);
-                } else if (denoise && b == 0u)  // PrimaryRayPass: bounce-0 shading + G-buffer + motion (renderer.rs:466-481)
-                    hipLaunchKernelGGL(k_shade<true>, dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues);
-                else
-                    hipLaunchKernelGGL(k_shade<false>, dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues);
+                auto launch_shade = [&](auto G, auto P) {   // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); ENV / PUNCT as for k_path
+                    constexpr bool g = decltype(G)::value, pu = decltype(P)::value;
+                    if (env) hipLaunchKernelGGL((k_shade<g, true, pu, DEnv>), dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues, ev);
+                    else hipLaunchKernelGGL((k_shade<g, false, pu>), dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues);
+                };
+                if (denoise && b == 0u) { if (punct) launch_shade(std::true_type{}, std::true_type{}); else launch_shade(std::true_type{}, std::false_type{}); }
+                else if (punct) launch_shade(std::false_type{}, std::true_type{});
+                else launch_shade(std::false_type{}, std::false_type{});
                 stage_end(r, s, slot);
                 if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
                 trace(b + 1u < nb ? (int)(b + 1u) : -1, (int)b);

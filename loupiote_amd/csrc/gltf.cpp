@@ -313,6 +313,37 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
             lpt_scene_add_instance(&tmp, bvh_offset + (uint32_t)e, m, material, nullptr);
         }
     }
+    // KHR_lights_punctual (SPEC §14(6)): one punctual light per node that names one, placed by the node's own matrix like a mesh
+    const Json &klights = d.js.at("extensions").at("KHR_lights_punctual").at("lights");
+    for (size_t i = 0; i < nodes.size(); ++i) {
+        const Json *jl = nodes[i].at("extensions").at("KHR_lights_punctual").find("light");
+        if (!jl) continue;
+        const size_t li = json_size(*jl, (size_t)-1, "node light");
+        if (li >= klights.size()) bad("KHR_lights_punctual light index out of range");
+        const Json &kl = klights[li];
+        const std::string &ty = kl.at("type").str;
+        uint32_t type;
+        if (ty == "point") type = LPT_PUNCTUAL_POINT;
+        else if (ty == "spot") type = LPT_PUNCTUAL_SPOT;
+        else if (ty == "directional") type = LPT_PUNCTUAL_DIRECTIONAL;
+        else bad("KHR_lights_punctual: unknown light type '" + ty + "'");
+        float color[3] = {1.f, 1.f, 1.f};
+        const Json &jc = kl.at("color");
+        if (!jc.is_null()) {
+            if (jc.size() != 3) bad("KHR_lights_punctual: color must have 3 components");
+            for (int c = 0; c < 3; ++c) color[c] = (float)jc[c].number(1.0);
+        }
+        const float intensity = (float)kl.at("intensity").number(1.0), range = (float)kl.at("range").number(0.0);
+        const Json &spot = kl.at("spot");
+        const float inner = (float)spot.at("innerConeAngle").number(0.0), outer = (float)spot.at("outerConeAngle").number(0.7853981633974483);
+        float m[16];
+        node_matrix(nodes[i], m);
+        const float pos[3] = {m[12], m[13], m[14]}, dir[3] = {-m[8], -m[9], -m[10]};   // the matrix applied to (0, 0, -1) as a direction
+        lpt_punctual_light pl;
+        if (lpt_punctual_light_make(type, pos, dir, color, intensity, range, inner, outer, &pl) != LPT_OK ||
+            lpt_scene_add_punctual_light(&tmp, &pl, nullptr) != LPT_OK)
+            bad(std::string("KHR_lights_punctual light rejected: ") + lpt_last_error());
+    }
     const Json &images = d.js.at("images");
     for (size_t i = 0; i < images.size(); ++i) {
         Image im;

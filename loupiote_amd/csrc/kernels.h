@@ -88,6 +88,10 @@ struct DScene {
     uint32_t n_tris, n_materials, n_lights, n_images, n_pairs;
     float grid_lo[3], grid_step[3];   // the scene grid of the node origins (common.h scene_grid): origin = grid_lo + o * grid_step
     float pad_abs;               // the scene-wide part of the triangle padding (refit / LBVH; bvh.cpp padded_box): kScenePad x the scene's largest |coordinate|
+    // SPEC §19: punctual lights, four float4 per light (lpt_punctual_light verbatim).  Read only by the PUNCT instantiations of shade_hit / k_shade / k_path
+    // (the ones that run while n_punctual != 0) and by k_punctual_sample
+    const float4 *punctual;
+    uint32_t n_punctual;
 };
 constexpr uint32_t kPairedBit = 0x40000000u;
 
@@ -1515,6 +1519,43 @@ __global__ __launch_bounds__(kBlock) void k_env_pdf(DEnv ev, const float *dirs, 
     pdf_e[i] = env_pdf(ev, mk3(dirs[3u * (size_t)i], dirs[3u * (size_t)i + 1u], dirs[3u * (size_t)i + 2u]));
 }
 
+// ------------------------------------------------------------------ punctual lights (SPEC §19)
+// One sample of punctual light `l` seen from Po: the unit direction towards it, the distance (LPT_T_INF: directional) and the incident term E = colour x intensity x
+// 1/d^2 x range window x cone window.  false: no sample (Po is the light's position).  The lanes of a wave pick different lights of different types, so nothing here
+// branches on the type: the record carries the neutral constants of the windows its type does not have (scene.cpp punctual_checked: cone (-2, 1) unless a spot,
+// range 0 for a directional light) and the rest are selects.
+__device__ __forceinline__ bool punctual_sample(const DScene &sc, const uint32_t l, const f3 Po, f3 &wi, float &dist, f3 &E) {
+    const float4 *R = sc.punctual + 4u * (size_t)l;
+    const float4 pos = R[0], dr = R[1], col = R[2], cone = R[3];
+    const bool directional = pos.w == 2.0f;
+    const f3 dir = mk3(dr.x, dr.y, dr.z);
+    const f3 w = mk3(pos.x - Po.x, pos.y - Po.y, pos.z - Po.z);
+    const float d2 = dot(w, w);
+    if (!directional && !(d2 > 0.0f)) return false;
+    const float dd = sqrtf(d2);
+    wi = directional ? neg(dir) : w * (1.0f / dd);
+    dist = directional ? LPT_T_INF : dd;
+    const float att = directional ? 1.0f : 1.0f / d2;
+    const float q = dr.w > 0.0f ? d2 / (dr.w * dr.w) : 0.0f;
+    const float wr = clampf(1.0f - q * q, 0.0f, 1.0f);
+    const float s = clampf((dot(neg(wi), dir) - cone.x) * cone.y, 0.0f, 1.0f);
+    const float g = (att * wr) * (s * s);
+    E = mk3(col.x * g, col.y * g, col.z * g);
+    return true;
+}
+// lpt_scene_gpu_sample_punctual: the function shade_hit runs, one point per thread; a point without a sample gives zeros
+__global__ __launch_bounds__(kBlock) void k_punctual_sample(DScene sc, uint32_t l, const float *points, uint32_t n, float *wi_out, float *dist_out, float *E_out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t j = 3u * (size_t)i;
+    f3 wi, E;
+    float dist;
+    if (!punctual_sample(sc, l, mk3(points[j], points[j + 1u], points[j + 2u]), wi, dist, E)) { wi = mk3(0.f, 0.f, 0.f); E = wi; dist = 0.0f; }
+    wi_out[j] = wi.x; wi_out[j + 1u] = wi.y; wi_out[j + 2u] = wi.z;
+    dist_out[i] = dist;
+    E_out[j] = E.x; E_out[j + 1u] = E.y; E_out[j + 2u] = E.z;
+}
+
 // ------------------------------------------------------------------ SPEC §15 helpers (denoiser path)
 __device__ __forceinline__ uint32_t oct_encode(f3 n) {
     float l1 = (fabsf(n.x) + fabsf(n.y)) + fabsf(n.z);
@@ -1578,9 +1619,24 @@ struct ShadeOut {
 // radiance deposited into Lsum) and k_path (a lane carries its path through every bounce, radiance kept in registers):
 // `load_o()` returns the ray's (origin, pdf) record — only emitter hits and the G-buffer need it —, `add_l(r, g, b)`
 // adds to the path's radiance.  ENV (SPEC §18): next-event estimation samples the probe too (distribution `ev`), and a miss is MIS-weighted.
-template <bool GBUF, bool ENV, typename LoadO, typename AddL>
+// PUNCT (SPEC §19): the scene has punctual lights, which take the share pk.p_p of the non-probe light samples; the other instantiations never read `pk`.
+struct PunctPick { float p_p, p_pick; };   // the punctual share of the non-probe light samples; the probability with which ONE punctual light is picked
+template <bool ENV>
+__device__ __forceinline__ PunctPick punct_pick(const DScene &sc) {
+    PunctPick pk;
+    pk.p_p = (float)sc.n_punctual / (float)(sc.n_punctual + sc.n_lights);
+    pk.p_pick = ((ENV ? 0.5f : 1.0f) * pk.p_p) / (float)sc.n_punctual;
+    return pk;
+}
+// 1 / n of the rectangle lights' pdfs: the probe's half (ENV) and the punctual share (PUNCT) taken off
+template <bool ENV, bool PUNCT>
+__device__ __forceinline__ float rect_inv_nl(const DScene &sc, const PunctPick &pk) {
+    if (PUNCT) return sc.n_lights ? ((ENV ? 0.5f : 1.0f) * (1.0f - pk.p_p)) / (float)sc.n_lights : 0.0f;
+    return sc.n_lights ? (ENV ? 0.5f : 1.0f) / (float)sc.n_lights : 0.0f;   // ENV: a rectangle light is picked with 1 - p_env = 1/2
+}
+template <bool GBUF, bool ENV, bool PUNCT, typename LoadO, typename AddL>
 __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe, const DEnv &ev, const DNoise &nz, const FrameParams &p, const float *s_lut,
-                                          const uint32_t bounce, const bool last_bounce, const uint32_t seed_base, const float inv_nl, const GBufArgs &gb,
+                                          const uint32_t bounce, const bool last_bounce, const uint32_t seed_base, const float inv_nl, const PunctPick &pk, const GBufArgs &gb,
                                           const float4 d4, const float4 T4, const float4 h4, LoadO load_o, AddL add_l, ShadeOut &out) {
     out.want_next = false; out.want_shadow = false; out.is_surface = false;
     const uint32_t pxy = __float_as_uint(T4.w);  // x | y << 13 | sample << 26 (k_raygen)
@@ -1599,7 +1655,7 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
         if (ENV) {
             const float pdf_prev = load_o().w;
             if (pdf_prev >= 0.0f) {   // not a camera ray: the BSDF strategy's MIS weight against the probe's
-                const float pe = (sc.n_lights ? 0.5f : 1.0f) * env_pdf(ev, d);
+                const float pe = ((PUNCT || sc.n_lights) ? 0.5f : 1.0f) * env_pdf(ev, d);
                 const float pb2 = pdf_prev * pdf_prev;
                 const float w = pb2 / (pb2 + pe * pe);
                 e = mk3(e.x * w, e.y * w, e.z * w);
@@ -1676,7 +1732,7 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
             noise_shift(nz, x, y, seed_counter, r4, r5);
             float r6 = 0.0f, r7 = 0.0f, r8 = 0.0f, r9 = 0.0f;
             if (ENV) { r6 = rng_next(rg); r7 = rng_next(rg); r8 = rng_next(rg); r9 = rng_next(rg); }
-            const float p_env = sc.n_lights ? 0.5f : 1.0f;   // ENV: the probe's share of the light samples
+            const float p_env = (PUNCT || sc.n_lights) ? 0.5f : 1.0f;   // ENV: the probe's share of the light samples
             float am = max2(max2(fabsf(P.x), fabsf(P.y)), fabsf(P.z));
             float eps = 1.0e-4f * (1.0f + am);
             const f3 Po = mk3(P.x + Ng.x * eps, P.y + Ng.y * eps, P.z + Ng.z * eps);
@@ -1709,8 +1765,36 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
                         }
                     }
                 }
+            } else if (PUNCT && (ENV ? (r0 - p_env) / (1.0f - p_env) : r0) < pk.p_p) {   // a punctual light (SPEC §19): a delta light, so MIS weight 1 and no draw beyond r0
+                const float rl = ENV ? (r0 - p_env) / (1.0f - p_env) : r0;
+                uint32_t li = (uint32_t)((rl / pk.p_p) * (float)sc.n_punctual);
+                if (li > sc.n_punctual - 1u) li = sc.n_punctual - 1u;
+                f3 wi, E;
+                float dist;
+                if (punctual_sample(sc, li, Po, wi, dist, E)) {
+                    Hit hl;
+                    hl.t = dist; hl.u = 0.f; hl.v = 0.f; hl.prim = 0xFFFFFFFFu;
+                    intersect_lights(sc, Po, wi, hl);   // a rectangle light's front on the segment: shadow rays test triangles only, and it would stop a BSDF ray too
+                    if (hl.prim == 0xFFFFFFFFu) {
+                        f3 f;
+                        float pb;
+                        bsdf_eval(sf, Ns, Ng, V, NoV, pspec, wi, f, pb);
+                        if (pb > 0.0f) {
+                            const float NoL = dot(Ns, wi);
+                            f3 contrib = mk3((T.x * f.x) * ((NoL * E.x) / pk.p_pick), (T.y * f.y) * ((NoL * E.y) / pk.p_pick), (T.z * f.z) * ((NoL * E.z) / pk.p_pick));
+                            if (contrib.x > 0.0f || contrib.y > 0.0f || contrib.z > 0.0f) {
+                                out.want_shadow = true;
+                                out.so4 = make_float4(Po.x, Po.y, Po.z, dist < LPT_T_INF ? dist * 0.999f : LPT_T_INF);
+                                out.sd4 = make_float4(wi.x, wi.y, wi.z, d4.w);
+                                out.sc4 = make_float4(contrib.x, contrib.y, contrib.z, 0.f);
+                            }
+                        }
+                    }
+                }
             } else if (sc.n_lights) {
-                uint32_t li = (uint32_t)((ENV ? (r0 - p_env) / (1.0f - p_env) : r0) * (float)sc.n_lights);
+                float rl = ENV ? (r0 - p_env) / (1.0f - p_env) : r0;
+                if (PUNCT) rl = (rl - pk.p_p) / (1.0f - pk.p_p);
+                uint32_t li = (uint32_t)(rl * (float)sc.n_lights);
                 if (li > sc.n_lights - 1u) li = sc.n_lights - 1u;
                 const float4 *Lt = reinterpret_cast<const float4 *>(sc.lights + li);
                 const float4 n4 = Lt[0], t4 = Lt[1], b4 = Lt[2], lo4 = Lt[3];
@@ -1773,8 +1857,12 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
 
 // ENV (SPEC §18): `env...` is the probe's distribution, one DEnv; the default instantiations take no such argument.  The ENV ones
 // need more than 128 VGPRs and run at 3 waves per SIMD (168), where they do not spill
-template <bool GBUF, bool ENV = false, typename... Env>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ENV ? 3 : 4))) void k_shade(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue qin, const float4 *hits,
+// PUNCT (SPEC §19): the instantiations that run while the scene has punctual lights; LPT_SHADE_WAVES from the compiler's register report
+#ifndef LPT_SHADE_WAVES
+#define LPT_SHADE_WAVES(ENV, PUNCT) (((ENV) || (PUNCT)) ? 3 : 4)
+#endif
+template <bool GBUF, bool ENV = false, bool PUNCT = false, typename... Env>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LPT_SHADE_WAVES(ENV, PUNCT)))) void k_shade(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue qin, const float4 *hits,
                                                   Queue qout, ShadowQueue sq, float4 *Lsum, FrameCounters *ctr, int bounce,
                                                   uint32_t seed_base, GBufArgs gb, int sorted, Env... env) {
     static_assert(sizeof...(Env) == (ENV ? 1u : 0u), "the ENV instantiations take the distribution, the others nothing");
@@ -1796,7 +1884,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ENV ? 3 
     const uint32_t rounded = (count + 255u) & ~255u;  // keep whole blocks in the loop for the barriers
     uint32_t n_surface = 0;
     const bool last_bounce = (uint32_t)bounce + 1u >= p.max_bounces;
-    const float inv_nl = sc.n_lights ? (ENV ? 0.5f : 1.0f) / (float)sc.n_lights : 0.0f;   // ENV: a rectangle light is picked with 1 - p_env = 1/2
+    const PunctPick pk = PUNCT ? punct_pick<ENV>(sc) : PunctPick{0.0f, 0.0f};
+    const float inv_nl = rect_inv_nl<ENV, PUNCT>(sc, pk);
     for (uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x; i0 < rounded; i0 += stride) {
         ShadeOut so;
         so.want_next = false; so.want_shadow = false; so.is_surface = false;
@@ -1804,7 +1893,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ENV ? 3 
         if (i < count) {
             const float4 d4 = ld_nt(qin.d + i), T4 = ld_nt(qin.T + i), h4 = ld_nt(hits + i);
             const uint32_t slot = __float_as_uint(d4.w);
-            shade_hit<GBUF, ENV>(sc, probe, ev, nz, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, gb, d4, T4, h4,
+            shade_hit<GBUF, ENV, PUNCT>(sc, probe, ev, nz, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, gb, d4, T4, h4,
                             [&]() { return ld_nt(qin.o + i); },
                             [&](float r, float g, float b) {
                                 float4 L = Lsum[slot];
@@ -1902,11 +1991,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ENV ? 3 
 // The ENV instantiations (SPEC §18: probe sampling in the shading batch) need more registers than that and run at 3 waves per SIMD
 // (168 VGPRs), which they fit without spilling.
 #ifndef LPT_PATH_WAVES
-#define LPT_PATH_WAVES(ENV) ((ENV) ? 3 : 4)
+#define LPT_PATH_WAVES(ENV, PUNCT) (((ENV) || (PUNCT)) ? 3 : 4)
 #endif
 constexpr uint32_t kPathLdsExtra = 1024u + 3u * kMaxBounces * 4u;   // sRGB table + counters: what a wave needs besides its stacks
-template <bool GBUF, bool STATS, bool ENV = false, typename... Env>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(LPT_PATH_WAVES(ENV), LPT_PATH_WAVES(ENV)))) void k_path(
+template <bool GBUF, bool STATS, bool ENV = false, bool PUNCT = false, typename... Env>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(LPT_PATH_WAVES(ENV, PUNCT), LPT_PATH_WAVES(ENV, PUNCT)))) void k_path(
         DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue q0, const float4 *hits0, float4 *Lsum, FrameCounters *ctr, uint32_t seed0, GBufArgs gb, int refill,
         Env... env) {
     static_assert(sizeof...(Env) == (ENV ? 1u : 0u), "the ENV instantiations take the distribution, the others nothing");
@@ -1925,7 +2014,8 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(LPT
     ChunkPuller pl;
     puller_init(pl, &ctr->phead[0], QC(ctr, 0));
     const uint32_t nb = p.max_bounces;
-    const float inv_nl = sc.n_lights ? (ENV ? 0.5f : 1.0f) / (float)sc.n_lights : 0.0f;   // ENV: a rectangle light is picked with 1 - p_env = 1/2
+    const PunctPick pk = PUNCT ? punct_pick<ENV>(sc) : PunctPick{0.0f, 0.0f};
+    const float inv_nl = rect_inv_nl<ENV, PUNCT>(sc, pk);
     const int min_batch = 64 - refill;
     uint32_t n_nodes = 0, n_tris = 0, s_nodes = 0, s_tris = 0;
     uint32_t w_steps = 0, w_live = 0, w_node = 0, w_tri = 0;
@@ -1975,7 +2065,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(LPT
                 const float4 d4 = make_float4(rs.d.x, rs.d.y, rs.d.z, __uint_as_float(vslot));
                 const float4 T4 = make_float4(T.x, T.y, T.z, __uint_as_float(pxy));
                 const float4 h4 = make_float4(rs.best.t, rs.best.u, rs.best.v, __uint_as_float(rs.best.prim));
-                shade_hit<GBUF, ENV>(sc, probe, ev, nz, p, s_lut, bounce, bounce + 1u >= nb, seed0 + bounce + 1u, inv_nl, gb, d4, T4, h4,
+                shade_hit<GBUF, ENV, PUNCT>(sc, probe, ev, nz, p, s_lut, bounce, bounce + 1u >= nb, seed0 + bounce + 1u, inv_nl, pk, gb, d4, T4, h4,
                                 [&]() { return make_float4(rs.o.x, rs.o.y, rs.o.z, pdf); },
                                 [&](float r, float g, float b) { L.x = L.x + r; L.y = L.y + g; L.z = L.z + b; }, so);
                 if (so.is_surface) atomicAdd(&s_cnt[128u + bounce], 1u);

@@ -199,6 +199,85 @@ int lpt_scene_set_light(lpt_scene *s, uint32_t i, const lpt_light *l) {
     return LPT_OK;
 }
 
+// ---- punctual lights (SPEC §19) -------------------------------------------------
+// the record as the scene keeps it: checked, direction normalised (zero for a point light's unused direction stays zero)
+static int punctual_checked(const lpt_punctual_light *l, lpt_punctual_light &out, const char *fn) {
+    const float *f = l->position;   // the four rows are contiguous: 16 floats
+    for (int i = 0; i < 16; ++i)
+        if (!std::isfinite(f[i])) return fail(LPT_ERR_INVALID_ARG, "%s: field %d is not finite", fn, i);
+    const float type = l->position[3];
+    if (!(type == 0.f || type == 1.f || type == 2.f)) return fail(LPT_ERR_INVALID_ARG, "%s: unknown type %g", fn, (double)type);
+    if (l->direction[3] < 0.f) return fail(LPT_ERR_INVALID_ARG, "%s: negative range", fn);
+    if (l->color[0] < 0.f || l->color[1] < 0.f || l->color[2] < 0.f) return fail(LPT_ERR_INVALID_ARG, "%s: negative colour", fn);
+    if (type == 1.f && !(l->cone[1] > 0.f)) return fail(LPT_ERR_INVALID_ARG, "%s: a spot light's cone[1] = 1 / (cos(inner) - cos(outer)) must be positive", fn);
+    out = *l;
+    normalize3(out.direction);
+    if (type != 0.f && out.direction[0] == 0.f && out.direction[1] == 0.f && out.direction[2] == 0.f)
+        return fail(LPT_ERR_INVALID_ARG, "%s: a spot or directional light needs a direction", fn);
+    // the neutral constants of the windows a type does not have (SPEC §19: the kernel evaluates both for every type): only a spot has a cone —
+    // s = clamp((c + 2) * 1, 0, 1) = 1 for every cosine —, a directional light has no range
+    if (type != 1.f) { out.cone[0] = -2.f; out.cone[1] = 1.f; }
+    if (type == 2.f) out.direction[3] = 0.f;
+    out.color[3] = 0.f; out.cone[2] = 0.f; out.cone[3] = 0.f;
+    return LPT_OK;
+}
+
+int lpt_punctual_light_make(uint32_t type, const float *position, const float *direction, const float *color, float intensity,
+                            float range, float inner_angle, float outer_angle, lpt_punctual_light *out) {
+    if (!out) return fail(LPT_ERR_INVALID_ARG, "lpt_punctual_light_make: null");
+    if (type > LPT_PUNCTUAL_DIRECTIONAL) return fail(LPT_ERR_INVALID_ARG, "lpt_punctual_light_make: unknown type %u", type);
+    if (!std::isfinite(intensity) || intensity < 0.f) return fail(LPT_ERR_INVALID_ARG, "lpt_punctual_light_make: intensity must be finite and >= 0");
+    lpt_punctual_light l;
+    memset(&l, 0, sizeof l);
+    for (int i = 0; i < 3; ++i) {
+        l.position[i] = position ? position[i] : 0.f;
+        l.direction[i] = direction ? direction[i] : (i == 2 ? -1.f : 0.f);
+        l.color[i] = (color ? color[i] : 1.f) * intensity;
+    }
+    l.position[3] = (float)type;
+    l.direction[3] = range;
+    // a point or directional light passes the cone window untouched: s = clamp((c - (-2)) * 1, 0, 1) = 1 for every cosine
+    l.cone[0] = -2.f;
+    l.cone[1] = 1.f;
+    if (type == LPT_PUNCTUAL_SPOT) {
+        if (!(inner_angle >= 0.f) || !(outer_angle > inner_angle) || !(outer_angle <= 1.5707964f))
+            return fail(LPT_ERR_INVALID_ARG, "lpt_punctual_light_make: cone angles must satisfy 0 <= inner < outer <= pi/2");
+        const double co = std::cos((double)outer_angle), ci = std::cos((double)inner_angle);
+        l.cone[0] = (float)co;
+        l.cone[1] = (float)(1.0 / std::fmax(ci - co, 1e-6));
+    }
+    lpt_punctual_light checked;
+    const int st = punctual_checked(&l, checked, "lpt_punctual_light_make");
+    if (st != LPT_OK) return st;
+    *out = checked;
+    return LPT_OK;
+}
+
+int lpt_scene_add_punctual_light(lpt_scene *s, const lpt_punctual_light *l, uint32_t *out_index) {
+    if (!s || !l) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_add_punctual_light: null");
+    lpt_punctual_light c;
+    const int st = punctual_checked(l, c, "lpt_scene_add_punctual_light");
+    if (st != LPT_OK) return st;
+    s->punctual.push_back(c);
+    if (out_index) *out_index = (uint32_t)s->punctual.size() - 1u;
+    return LPT_OK;
+}
+
+int lpt_scene_set_punctual_light(lpt_scene *s, uint32_t i, const lpt_punctual_light *l) {
+    if (!s || !l || i >= s->punctual.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_punctual_light: bad index %u", i);
+    lpt_punctual_light c;
+    const int st = punctual_checked(l, c, "lpt_scene_set_punctual_light");
+    if (st != LPT_OK) return st;
+    s->punctual[i] = c;
+    return LPT_OK;
+}
+
+int lpt_scene_punctual_count(const lpt_scene *s, uint32_t *out) {
+    if (!s || !out) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_punctual_count: null");
+    *out = (uint32_t)s->punctual.size();
+    return LPT_OK;
+}
+
 #define LPT_GETTER(NAME, TYPE, FIELD)                                                            \
     int NAME(const lpt_scene *s, uint32_t first, uint32_t count, TYPE *dst) {                    \
         if (!s || (!dst && count)) return fail(LPT_ERR_INVALID_ARG, #NAME ": null");             \
@@ -213,6 +292,7 @@ LPT_GETTER(lpt_scene_get_vertices, lpt_vertex, vertices)
 LPT_GETTER(lpt_scene_get_indices, uint32_t, indices)
 LPT_GETTER(lpt_scene_get_instances, lpt_instance, instances)
 LPT_GETTER(lpt_scene_get_lights, lpt_light, lights)
+LPT_GETTER(lpt_scene_get_punctual_lights, lpt_punctual_light, punctual)
 
 int lpt_scene_get_image(const lpt_scene *s, uint32_t index, uint32_t *w, uint32_t *h, uint8_t *dst) {
     if (!s || index >= s->images.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_image: bad index %u", index);
