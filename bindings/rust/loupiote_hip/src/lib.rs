@@ -97,6 +97,16 @@ impl Scene {
         check(unsafe { ffi::lpt_scene_add_material(self.h, material, &mut out) })?;
         Ok(out)
     }
+    /// SPEC.md §20: alpha-masked (cutout) materials; `mode` is `ffi::LPT_ALPHA_OPAQUE` / `ffi::LPT_ALPHA_MASK`, `alpha_image` an image index or `ffi::LPT_INVALID_INDEX`
+    pub fn set_material_alpha(&mut self, material: u32, mode: u32, cutoff: f32, alpha_image: u32) -> Result<(), Error> {
+        check(unsafe { ffi::lpt_scene_set_material_alpha(self.h, material, mode, cutoff, alpha_image) })
+    }
+    /// -> (mode, cutoff, alpha_image)
+    pub fn material_alpha(&self, material: u32) -> Result<(u32, f32, u32), Error> {
+        let (mut mode, mut cutoff, mut image) = (0u32, 0f32, 0u32);
+        check(unsafe { ffi::lpt_scene_get_material_alpha(self.h, material, &mut mode, &mut cutoff, &mut image) })?;
+        Ok((mode, cutoff, image))
+    }
     /// SPEC.md §19: a point / spot / directional light (KHR_lights_punctual); records from `punctual_light`
     pub fn add_punctual_light(&mut self, light: &ffi::lpt_punctual_light) -> Result<u32, Error> {
         let mut out = 0u32;

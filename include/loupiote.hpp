@@ -75,6 +75,16 @@ class Scene {  // scene.rs:30-54
     uint32_t add_image(const uint8_t *rgba8, uint32_t w, uint32_t h) { uint32_t id = 0; check(lpt_scene_add_image(h_, rgba8, w, h, &id)); return id; }
     uint32_t add_light(const lpt_light &l) { uint32_t id = 0; check(lpt_scene_add_light(h_, &l, &id)); return id; }
     void set_light(uint32_t i, const lpt_light &l) { check(lpt_scene_set_light(h_, i, &l)); }
+    // SPEC.md §20: alpha-masked (cutout) materials; mode LPT_ALPHA_OPAQUE / LPT_ALPHA_MASK, alpha_image an image index or LPT_INVALID_INDEX
+    struct MaterialAlpha { uint32_t mode; float cutoff; uint32_t alpha_image; };
+    void set_material_alpha(uint32_t material, uint32_t mode, float cutoff = 0.5f, uint32_t alpha_image = LPT_INVALID_INDEX) {
+        check(lpt_scene_set_material_alpha(h_, material, mode, cutoff, alpha_image));
+    }
+    MaterialAlpha material_alpha(uint32_t material) const {
+        MaterialAlpha a{};
+        check(lpt_scene_get_material_alpha(h_, material, &a.mode, &a.cutoff, &a.alpha_image));
+        return a;
+    }
     // SPEC.md §19: point / spot / directional lights (KHR_lights_punctual); records from point_light / spot_light / directional_light below
     uint32_t add_punctual_light(const lpt_punctual_light &l) { uint32_t id = 0; check(lpt_scene_add_punctual_light(h_, &l, &id)); return id; }
     void set_punctual_light(uint32_t i, const lpt_punctual_light &l) { check(lpt_scene_set_punctual_light(h_, i, &l)); }

@@ -262,6 +262,16 @@ int lpt_scene_get_punctual_lights(const lpt_scene *s, uint32_t first, uint32_t c
 int lpt_punctual_light_make(uint32_t type, const float *position, const float *direction, const float *color, float intensity,
                             float range, float inner_angle, float outer_angle, lpt_punctual_light *out);
 
+/* build-only extension (SPEC.md §20; the reference's loader reads no alphaMode): alpha-masked (cutout) materials.  The 32-byte
+ * lpt_material keeps the reference's layout; the alpha state is a side table with one entry per material, opaque by default.
+ * `mode` 0 = opaque, 1 = mask: a triangle hit counts iff color.w (times the bilinear alpha of image `alpha_image`, unless that is
+ * LPT_INVALID_INDEX) >= cutoff — for closest-hit and shadow rays alike.  LPT_ERR_INVALID_ARG, and nothing changed, for a material
+ * or image index out of range, a negative or non-finite cutoff, a mode greater than 1.  Out-pointers of the getter may be NULL. */
+#define LPT_ALPHA_OPAQUE 0u
+#define LPT_ALPHA_MASK 1u
+int lpt_scene_set_material_alpha(lpt_scene *scene, uint32_t material_index, uint32_t mode, float cutoff, uint32_t alpha_image);
+int lpt_scene_get_material_alpha(const lpt_scene *scene, uint32_t material_index, uint32_t *mode, float *cutoff, uint32_t *alpha_image);
+
 /* Read-back of the flat arrays (the reference exposes them as pub Vec fields). */
 int lpt_scene_get_materials(const lpt_scene *s, uint32_t first, uint32_t count, lpt_material *dst);
 int lpt_scene_get_entries(const lpt_scene *s, uint32_t first, uint32_t count, lpt_blas_entry *dst);

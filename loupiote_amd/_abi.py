@@ -38,6 +38,7 @@ VERTEX_DT = np.dtype([("position", "<f4", 4), ("normal", "<f4", 4)])
 LIGHT_DT = np.dtype([("normal", "<f4", 4), ("tangent", "<f4", 4), ("bitangent", "<f4", 4), ("origin", "<f4", 4)])
 PUNCTUAL_DT = np.dtype([("position", "<f4", 4), ("direction", "<f4", 4), ("color", "<f4", 4), ("cone", "<f4", 4)])   # lpt_punctual_light (SPEC §19)
 PUNCTUAL_POINT, PUNCTUAL_SPOT, PUNCTUAL_DIRECTIONAL = 0, 1, 2
+ALPHA_OPAQUE, ALPHA_MASK = 0, 1   # lpt_scene_set_material_alpha's mode (SPEC §20)
 INSTANCE_DT = np.dtype([("model_to_world", "<f4", 16), ("blas_index", "<u4"), ("material_index", "<u4"),
                         ("pad", "<u4", 2)])
 ENTRY_DT = np.dtype([("vertex_offset", "<u4"), ("vertex_count", "<u4"), ("index_offset", "<u4"),
@@ -96,6 +97,8 @@ SIGNATURES = {
     "lpt_scene_punctual_count": (_i, [_vp, _pu32]),
     "lpt_scene_get_punctual_lights": (_i, [_vp, _u32, _u32, _vp]),
     "lpt_punctual_light_make": (_i, [_u32, _vp, _vp, _vp, _f, _f, _f, _f, _vp]),
+    "lpt_scene_set_material_alpha": (_i, [_vp, _u32, _u32, _f, _u32]),
+    "lpt_scene_get_material_alpha": (_i, [_vp, _u32, _pu32, C.POINTER(_f), _pu32]),
     "lpt_scene_get_materials": (_i, [_vp, _u32, _u32, _vp]),
     "lpt_scene_get_entries": (_i, [_vp, _u32, _u32, _vp]),
     "lpt_scene_get_vertices": (_i, [_vp, _u32, _u32, _vp]),

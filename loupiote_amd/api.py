@@ -202,6 +202,20 @@ class Scene:
     def punctual_lights(self):
         return self._get(A.lib().lpt_scene_get_punctual_lights, A.PUNCTUAL_DT, self.punctual_count())
 
+    # SPEC §20: alpha-masked (cutout) materials; a side table of the materials, opaque by default
+    def set_material_alpha(self, material_index, mode, cutoff=0.5, alpha_image=A.INVALID_INDEX):
+        """mode: A.ALPHA_OPAQUE / A.ALPHA_MASK (or "OPAQUE" / "MASK"); a hit on a masked material counts iff color.w (x the bilinear
+        alpha of image `alpha_image`, if any) >= cutoff, for closest-hit and shadow rays alike"""
+        if isinstance(mode, str):
+            mode = {"OPAQUE": A.ALPHA_OPAQUE, "MASK": A.ALPHA_MASK}[mode]
+        _check(A.lib().lpt_scene_set_material_alpha(self._h, int(material_index), int(mode), float(cutoff), int(alpha_image)))
+
+    def material_alpha(self, material_index):
+        """-> (mode, cutoff, alpha_image)"""
+        mode, cutoff, image = C.c_uint32(), C.c_float(), C.c_uint32()
+        _check(A.lib().lpt_scene_get_material_alpha(self._h, int(material_index), C.byref(mode), C.byref(cutoff), C.byref(image)))
+        return int(mode.value), float(cutoff.value), int(image.value)
+
     def _get(self, fn, dt, count):
         out = np.zeros(count, dt)
         _check(fn(self._h, 0, count, A.ptr(out)))

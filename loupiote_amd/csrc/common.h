@@ -20,6 +20,14 @@ int fail(int status, const char *fmt, ...);
 struct Image {
     uint32_t width = 0, height = 0;
     std::vector<uint8_t> rgba8;
+    bool has_alpha = false;   // the file carried an alpha channel that rgba8's fourth byte holds (decode_png; SPEC §20: only then a MASK material reads it)
+};
+
+// SPEC §20: a material's alpha state (the 32-byte lpt_material keeps the reference's layout, so this rides beside it)
+struct MaterialAlpha {
+    uint32_t mode = LPT_ALPHA_OPAQUE;
+    float cutoff = 0.5f;
+    uint32_t image = LPT_INVALID_INDEX;
 };
 
 }  // namespace lpt
@@ -35,6 +43,8 @@ struct lpt_scene {
     std::vector<lpt_light> lights;
     std::vector<lpt::Image> images;
     std::vector<lpt_punctual_light> punctual;   // SPEC §19: point / spot / directional lights; no dummy element, a fresh scene has none
+    std::vector<lpt::MaterialAlpha> alpha;      // SPEC §20: side table of `materials`; a material beyond its end is opaque (material_alpha)
+    lpt::MaterialAlpha material_alpha(size_t i) const { return i < alpha.size() ? alpha[i] : lpt::MaterialAlpha(); }
 };
 
 namespace lpt {

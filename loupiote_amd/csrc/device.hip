@@ -147,6 +147,7 @@ struct lpt_scene_gpu {
     DevTree tree;
     DevMem tri_verts, materials, lights, texels, images, srgb_lut, pair_texels, pair_images;
     DevMem punctual;                // SPEC §19: lpt_punctual_light records (DScene::punctual)
+    DevMem alpha_tri, alpha_recs;   // SPEC §20: the per-triangle table and the records of the masked materials (DScene::alpha_tri / alpha_recs); empty without masks
     TexturePairs pairs;
     lpt_accel_stats stats{};
     // refit bookkeeping (lpt_scene_gpu_update_instances)
@@ -677,6 +678,11 @@ static std::vector<uint64_t> pair_textures(const lpt_scene &scene, bool enable, 
         for (uint32_t id : {m.albedo_texture, m.mra_texture})
             if (id < scene.images.size()) { referenced[id] = 1; if (!paired) alone[id] = 1; }
     }
+    // SPEC §20: the alpha lookup of the traversal reads the plain tiled image, never the paired copy: a mask's image stays in the atlas
+    for (size_t i = 0; i < scene.materials.size(); ++i) {
+        const MaterialAlpha a = scene.material_alpha(i);
+        if (a.mode == LPT_ALPHA_MASK && a.image < scene.images.size()) { referenced[a.image] = 1; alone[a.image] = 1; }
+    }
     p.image_resident.assign(scene.images.size(), 1);
     for (size_t i = 0; i < scene.images.size(); ++i) p.image_resident[i] = (!referenced[i] || alone[i]) ? 1 : 0;
     return texels;
@@ -803,6 +809,50 @@ static int upload_punctual(lpt_scene_gpu *sg, const lpt_scene &scene) {
     return LPT_OK;
 }
 
+// SPEC §20: the alpha tables of the scene as it is now — one record per masked material that an instance with triangles uses, one uint32 per baked triangle (keyed by
+// prim id: a refit leaves it alone).  Derived on the host from the instance layout; both empty for a scene without masks, which then launches what it always launched.
+struct AlphaTables { std::vector<float4> recs; std::vector<uint32_t> tri; };
+static int derive_alpha(const lpt_scene_gpu *sg, const lpt_scene &scene, AlphaTables &out) {
+    std::vector<uint32_t> rec_of(scene.materials.size(), 0u);   // 1 + record index
+    for (size_t i = 0; i < scene.instances.size() && i < sg->inst_count.size(); ++i) {
+        const uint32_t n = sg->inst_count[i];
+        if (!n) continue;
+        const uint32_t mat = scene.instances[i].material_index < scene.materials.size() ? scene.instances[i].material_index : 0u;   // SPEC §2.5
+        const MaterialAlpha a = scene.material_alpha(mat);
+        if (a.mode != LPT_ALPHA_MASK) continue;
+        if (!rec_of[mat]) {
+            uint32_t image = a.image < scene.images.size() ? a.image : LPT_INVALID_INDEX;
+            if (image != LPT_INVALID_INDEX && !(image < sg->pairs.image_resident.size() && sg->pairs.image_resident[image]))
+                return fail(LPT_ERR_INVALID_ARG, "material %u now masks with an image that was uploaded only as half of an (albedo, mra) pair: upload the scene again", mat);
+            float bits;
+            memcpy(&bits, &image, 4);
+            out.recs.push_back(make_float4(a.cutoff, scene.materials[mat].color[3], bits, 0.f));
+            rec_of[mat] = (uint32_t)out.recs.size();
+        }
+        if (out.tri.empty()) out.tri.assign(std::max(sg->d.n_tris, 1u), 0u);
+        if ((size_t)sg->inst_first[i] + n > out.tri.size()) return fail(LPT_ERR_INVALID_ARG, "instance %zu lies beyond the baked triangles", i);
+        std::fill(out.tri.begin() + sg->inst_first[i], out.tri.begin() + sg->inst_first[i] + n, rec_of[mat]);
+    }
+    return LPT_OK;
+}
+// ... onto the device and into the view the kernels get; the caller has made sure nothing in flight reads the old tables
+static int commit_alpha(lpt_scene_gpu *sg, const AlphaTables &at) {
+    DScene &d = sg->d;
+    if (at.recs.empty()) {
+        sg->alpha_tri.reset(); sg->alpha_recs.reset();
+        d.alpha_tri = nullptr; d.alpha_recs = nullptr; d.n_alpha = 0u;
+        return LPT_OK;
+    }
+    hipStream_t s = sg->dev->stream;
+    TRY(upload(sg->alpha_tri, at.tri, s));
+    TRY(upload(sg->alpha_recs, at.recs, s));
+    HIP_TRY(hipStreamSynchronize(s));   // the host vectors are the caller's
+    d.alpha_tri = as<const uint32_t>(sg->alpha_tri);
+    d.alpha_recs = as<const float4>(sg->alpha_recs);
+    d.n_alpha = (uint32_t)at.recs.size();
+    return LPT_OK;
+}
+
 int lpt_scene_upload(lpt_device *dev, const lpt_scene *scene, lpt_scene_gpu **out) { return lpt_scene_upload_ex(dev, scene, LPT_ACCEL_BUILD_HOST_SAH, out); }
 
 int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags, lpt_scene_gpu **out) {
@@ -892,6 +942,11 @@ int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags,
     d.n_lights = (uint32_t)scene->lights.size();
     d.n_images = (uint32_t)scene->images.size();
     TRY(upload_punctual(sg.get(), *scene));
+    {
+        AlphaTables at;
+        TRY(derive_alpha(sg.get(), *scene, at));
+        TRY(commit_alpha(sg.get(), at));
+    }
     sg->stats.triangles = d.n_tris;
     sg->stats.node_bytes = (uint32_t)sizeof(Node8);
     sg->stats.tri_bytes = (uint32_t)sizeof(WoopTri);
@@ -933,6 +988,9 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
     for (size_t i = 0; i < scene->instances.size(); ++i)
         if (memcmp(&scene->instances[i], &sg->instances[i], sizeof(lpt_instance)) != 0) changed.push_back((uint32_t)i);
     if (!changed.empty()) {
+        // SPEC §20: an instance whose material changed may have become masked or opaque; checked before anything is baked
+        AlphaTables at;
+        TRY(derive_alpha(sg, *scene, at));
         // re-bake on the device (the object-space meshes are resident, only the transforms travel); a place-driven scatter then takes the new
         // Woop maps to every place a triangle has in the tree (a split triangle has several)
         DevMem woop_prim;
@@ -945,6 +1003,7 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
             if (sg->inst_count[i]) scatter_woop(sg->tree, woop_prim.get(), sg->inst_first[i], sg->inst_count[i], sg->dev->stream);
         }
         if (st != LPT_OK) return st;
+        TRY(commit_alpha(sg, at));
         if (sg->stats.triangles) TRY(refit(sg));
     }
     if (out_rebaked) *out_rebaked = (uint32_t)changed.size();
@@ -960,12 +1019,20 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
     const uint32_t n = sg->stats.triangles;
     if (n < 16u) {
         TRY(lpt_scene_gpu_update_instances(sg, scene, nullptr));   // (flushes and waits first)
+        AlphaTables at;   // SPEC §20: a rebuild re-derives the alpha tables whether or not an instance changed
+        TRY(derive_alpha(sg, *scene, at));
+        TRY(commit_alpha(sg, at));
         return upload_punctual(sg, *scene);
     }
     HIP_TRY(hipSetDevice(sg->dev->ordinal));
     TRY(flush_device(sg->dev));
     HIP_TRY(hipDeviceSynchronize());  // frames in flight on the renderers' streams still read what is rebuilt here
     TRY(upload_punctual(sg, *scene));   // lights are scene data: a rebuild carries them too, whatever their number (SPEC §19)
+    {
+        AlphaTables at;   // ... and so are the materials' alpha states (SPEC §20)
+        TRY(derive_alpha(sg, *scene, at));
+        TRY(commit_alpha(sg, at));
+    }
     DevMem woop_prim;
     TRY(dev_alloc(woop_prim, sizeof(WoopTri) * (size_t)n));
     TRY(bake_instances(sg, *scene, every_instance(*scene), woop_prim.get()));
@@ -1149,7 +1216,8 @@ int lpt_trace_closest(lpt_device *dev, const lpt_scene_gpu *sg, const float *ori
     if (e == hipSuccess) e = hipMemcpyAsync(dO, o.data(), sizeof(float4) * n, hipMemcpyHostToDevice, dev->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dD, d.data(), sizeof(float4) * n, hipMemcpyHostToDevice, dev->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_query_closest, dim3(div_up(n, kTraceBlock)), dim3(kTraceBlock), stack_bytes(sg->d), dev->stream, sg->d, dO, dD, dH, n);
+        if (sg->d.n_alpha) hipLaunchKernelGGL(k_query_closest<true>, dim3(div_up(n, kTraceBlock)), dim3(kTraceBlock), stack_bytes(sg->d), dev->stream, sg->d, dO, dD, dH, n);   // SPEC §20
+        else hipLaunchKernelGGL(k_query_closest<false>, dim3(div_up(n, kTraceBlock)), dim3(kTraceBlock), stack_bytes(sg->d), dev->stream, sg->d, dO, dD, dH, n);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, dH, sizeof(float4) * n, hipMemcpyDeviceToHost, dev->stream);
@@ -1177,7 +1245,8 @@ int lpt_trace_occluded(lpt_device *dev, const lpt_scene_gpu *sg, const float *or
     if (e == hipSuccess) e = hipMemcpyAsync(dO, o.data(), sizeof(float4) * n, hipMemcpyHostToDevice, dev->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dD, d.data(), sizeof(float4) * n, hipMemcpyHostToDevice, dev->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_query_occluded, dim3(div_up(n, kTraceBlock)), dim3(kTraceBlock), stack_bytes(sg->d), dev->stream, sg->d, dO, dD, dR, n);
+        if (sg->d.n_alpha) hipLaunchKernelGGL(k_query_occluded<true>, dim3(div_up(n, kTraceBlock)), dim3(kTraceBlock), stack_bytes(sg->d), dev->stream, sg->d, dO, dD, dR, n);   // SPEC §20
+        else hipLaunchKernelGGL(k_query_occluded<false>, dim3(div_up(n, kTraceBlock)), dim3(kTraceBlock), stack_bytes(sg->d), dev->stream, sg->d, dO, dD, dR, n);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, dR, n, hipMemcpyDeviceToHost, dev->stream);
@@ -1884,6 +1953,10 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
     DNoise nz{(const uint8_t *)r->noise, r->noise_w, r->noise_h, (r->use_noise && r->noise) ? 1u : 0u};
     const DScene &sc = r->sg->d;
     const bool punct = sc.n_punctual != 0u;   // SPEC §19: the PUNCT kernels while the bound scene has punctual lights; otherwise exactly the default launches
+    // SPEC §20: a scene with alpha-masked materials traces on the plain per-lane step alone (k_trace<STATS, false, false, /*MASK*/true>), whatever the options say — the
+    // only acceptance site that asks the mask.  No packets, no cooperative walks, no path kernel, no tail, no step budget, no occluder probe: each of them accepts hits
+    // on its own.  Otherwise exactly the default launches
+    const bool masked = sc.n_alpha != 0u;
     if (r->timings) { r->ring_pos++; harvest_slot(r, cur_slot(r)); }
 
     tk.stages = 0; tk.run = nullptr;
@@ -1894,7 +1967,7 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
         // the one-round-trip step (kernels.h ray_step_pipe): 72 VGPRs (round 6; 78 before), 6 waves per SIMD used of the 7 that fit, ~3 % more nodes and ~12 % more
         // triangles fetched per ray — and still 1 % less time per frame at 8 M rays, 2 % for a 1 M-ray tile shard
         // (profiles/r03_experiments_ab.txt); LPT_EXP_PIPE_RAYS 0 selects the two-round-trip step
-        const bool pipe = n_rays <= r->pipe_rays;
+        const bool pipe = !masked && n_rays <= r->pipe_rays;
         // persistent waves: about 2.5 primary rays per lane, between 8 waves per CU and all that fit (24 = 6 per SIMD with the one-round-trip step — 28 measured no faster, round 6 —, 32 with the other).  A 1/8
         // tile shard (1 M rays per launch) is best at 24 either way (round 3, span form, two-round-trip step: 8 / 12 / 16 / 24 / 32
         // waves per CU -> 4.41 / 3.89 / 3.62 / 3.51 / 3.54 ms per frame)
@@ -1909,30 +1982,30 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
         // angle, the walk visits several times the nodes, and the packet launch is a third of the frame (0.43 of 1.37 ms; 0.39 ms at 480x270,
         // where the per-ray launch needs 0.13).  LPT_OPT_PACKET_PRIMARY 2 (default): packets up to 1.8 mrad per pixel; 1: always; 0: never.
         const float pixel_rad = 2.0f * th / (float)std::max(r->h, 1u);
-        const bool packet = (r->packet_primary == 1u || (r->packet_primary == 2u && pixel_rad <= kPacketMaxPixelRad));
+        const bool packet = !masked && (r->packet_primary == 1u || (r->packet_primary == 2u && pixel_rad <= kPacketMaxPixelRad));
         tk.packet = packet;
         // Traversal launches: closest-hit rays of bounce b+1 and shadow rays of bounce b, both produced by shade(b), are traced by
         // ONE persistent launch (k_trace) — nb+1 traversal launches per frame instead of 2*nb.
         // the occluder-cache probe rides with the stats kernels only (kernels.h OccProbe); its table belongs to the renderer
         OccProbe occ{nullptr, 0u, 0.0f};
-        if (r->stats && r->occ_table && r->occ_cell > 0.0f) occ = OccProbe{r->occ_table, kOccEntries - 1u, 1.0f / r->occ_cell};
+        if (!masked && r->stats && r->occ_table && r->occ_cell > 0.0f) occ = OccProbe{r->occ_table, kOccEntries - 1u, 1.0f / r->occ_cell};
         // the step budget pays where nothing else fills the tail of a launch: a submission that is ONE wavefront (a tile shard, a small frame).  The
         // pieces of a cut batch overlap on the renderer's lanes and hide each other's tails: 1/2 shard as two wavefronts 6.84 ms without, 6.93 with it
         // (not with the stats kernels: a ray dropped at the budget would be missing from the steps-per-ray histogram and its partial node / triangle counts would be
         // counted again by the cooperative kernel's full re-trace — ADVICE r04)
-        const bool tail_launch = !r->stats && (solo || r->budget_split) && n_rays <= r->budget_rays;
+        const bool tail_launch = !masked && !r->stats && (solo || r->budget_split) && n_rays <= r->budget_rays;
         // ... the tail finished in place (tail_walk) comes first where it is on: nothing is dropped then, so there is nothing to re-trace
         const uint32_t tail = tail_launch ? std::min(std::min(r->tail_lanes, kTailMax), (uint32_t)std::max(r->refill, 0)) : 0u;
         const uint32_t budget = (tail_launch && !tail && r->step_budget) ? r->step_budget : 0u;
         const size_t tail_lds = tail ? sizeof(uint32_t) * tail_lds_words(r->sg->stats.max_depth) : 0u;
         // a TINY wavefront (fewer rays than the chip has wave slots): the per-bounce launches with EVERY ray traced by a whole wave (k_trace_coop over the queues) — a lane per
         // ray leaves the chip empty and the frame is one chain of dependent steps (64x36, 4 spp: k_path 0.72 ms per frame, the per-lane launches 0.83, this 0.39)
-        const bool coop_all = !r->stats && r->coop_rays && n_rays <= r->coop_rays;
+        const bool coop_all = !masked && !r->stats && r->coop_rays && n_rays <= r->coop_rays;
         // The launches in stages, so that the pieces of a cut batch can be enqueued stage by stage across the lanes (flush_pending,
         // LPT_EXP_LANE_PHASE): stage 0 = counters, ray generation and the primary rays (with the path kernel: the whole wavefront),
         // stage b + 1 = shade(b) and the traversal launch behind it.  `ph` orders the stage against the other lanes' (stream events only).
         // The closure holds copies of what the launches read; `r`'s buffers and the scene do not change before the submission is enqueued.
-        const bool path = r->path_rays && n_rays <= r->path_rays && !coop_all;   // the primary hits are there, whichever kernel found them
+        const bool path = !masked && r->path_rays && n_rays <= r->path_rays && !coop_all;   // the primary hits are there, whichever kernel found them
         const int slot = cur_slot(r);
         Wavefront *w = &wf;
         tk.stages = nb + 1u;
@@ -1945,6 +2018,12 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
                 if (coop_all) {
                     const size_t clds = sizeof(uint32_t) * coop_stack_entries(kCoopStack, r->sg->stats.max_depth);
                     hipLaunchKernelGGL(k_trace_coop<false>, dim3(std::min(2u * n_rays, cus * kCoopWavesPerCu)), dim3(kTraceBlock), clds, s, sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, (const uint32_t *)nullptr, launch_no);
+                    stage_end(r, s, slot);
+                    return;
+                }
+                if (masked) {   // SPEC §20 (tail, budget = 0 and no probe table by the decisions above)
+                    if (r->stats) hipLaunchKernelGGL((k_trace<true, false, false, true>), dim3(trace_blocks), dim3(kTraceBlock), lds + 64u, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, 0u, w->strag, launch_no, 0u});
+                    else hipLaunchKernelGGL((k_trace<false, false, false, true>), dim3(trace_blocks), dim3(kTraceBlock), lds, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, 0u, w->strag, launch_no, 0u});
                     stage_end(r, s, slot);
                     return;
                 }

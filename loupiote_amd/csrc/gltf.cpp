@@ -281,6 +281,8 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
         return texture_offset + (uint32_t)si;
     };
     const Json &mats = d.js.at("materials");
+    struct Mask { uint32_t material; float cutoff; uint32_t image; };
+    std::vector<Mask> masks;
     for (size_t i = 0; i < mats.size(); ++i) {
         const Json &pbr = mats[i].at("pbrMetallicRoughness");
         lpt_material m = {{1.f, 1.f, 1.f, 1.f}, 1.f, 1.f, LPT_INVALID_INDEX, LPT_INVALID_INDEX};
@@ -291,6 +293,18 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
         m.albedo_texture = tex_id(pbr.at("baseColorTexture"));
         m.mra_texture = tex_id(pbr.at("metallicRoughnessTexture"));
         tmp.materials.push_back(m);
+        // alphaMode / alphaCutoff (SPEC §20, §14(7)): MASK sets the side table once the images are decoded (below); BLEND loads as opaque.
+        // A file that states neither touches nothing
+        const Json *jmode = mats[i].find("alphaMode"), *jcut = mats[i].find("alphaCutoff");
+        float cutoff = 0.5f;
+        if (jcut) {
+            if (jcut->kind != Json::Num || !std::isfinite(jcut->num) || jcut->num < 0.0 || !std::isfinite((float)jcut->num)) bad("alphaCutoff is not a finite non-negative number");
+            cutoff = (float)jcut->num;
+        }
+        if (jmode) {
+            if (!jmode->is_str() || !(jmode->str == "OPAQUE" || jmode->str == "MASK" || jmode->str == "BLEND")) bad("unknown alphaMode");
+            if (jmode->str == "MASK") masks.push_back(Mask{(uint32_t)tmp.materials.size() - 1u, cutoff, m.albedo_texture});
+        }
     }
     const Json &nodes = d.js.at("nodes");
     for (size_t i = 0; i < nodes.size(); ++i) {
@@ -349,6 +363,12 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
         Image im;
         decode_image(d, images[i], im);
         tmp.images.push_back(std::move(im));
+    }
+    // the alpha image of a MASK material is its base-colour image only if that file carried an alpha channel: §14(5) expands RGB with alpha 0,
+    // which must not cut everything away
+    for (const Mask &k : masks) {
+        const uint32_t image = (k.image < tmp.images.size() && tmp.images[k.image].has_alpha) ? k.image : LPT_INVALID_INDEX;
+        if (lpt_scene_set_material_alpha(&tmp, k.material, LPT_ALPHA_MASK, k.cutoff, image) != LPT_OK) bad(std::string("alphaMode MASK rejected: ") + lpt_last_error());
     }
     *scene = std::move(tmp);
 }

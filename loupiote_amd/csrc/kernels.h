@@ -92,6 +92,11 @@ struct DScene {
     // (the ones that run while n_punctual != 0) and by k_punctual_sample
     const float4 *punctual;
     uint32_t n_punctual;
+    // SPEC §20: alpha-masked materials.  alpha_tri[prim] = 0 for an opaque triangle, else 1 + the index of its record {cutoff, color.w, bits of the PLAIN image index
+    // (LPT_INVALID_INDEX: no alpha image), 0}.  Null / 0 for a scene without masks; read only by the MASK instantiations of the traversal (alpha_rejects)
+    const uint32_t *alpha_tri;
+    const float4 *alpha_recs;
+    uint32_t n_alpha;
 };
 constexpr uint32_t kPairedBit = 0x40000000u;
 
@@ -503,8 +508,47 @@ __device__ __forceinline__ uint2 node_test(const DScene &sc, RayState &rs, const
     }
 }
 
+// SPEC §20: does the alpha mask cut the candidate hit (prim, u, v) away?  Called right behind an accepted Woop test, by the MASK instantiations only.  An opaque
+// triangle costs one 4-byte load; everything else sits behind that branch — divergent and rare —, at a point of the step where the node rows and the triangle's
+// Woop rows are dead, so none of it is live across the child tests (the step's register peak).  The decision is a pure function of (prim, u, v).
+__device__ __forceinline__ int wrap_i(int x, int n);
+__device__ __forceinline__ int wrap_next(int w, int n);
+__device__ __forceinline__ bool alpha_rejects(const DScene &sc, const uint32_t prim, const float hu, const float hv) {
+    const uint32_t e = sc.alpha_tri[prim];
+    if (e == 0u) return false;
+    const float4 rec = sc.alpha_recs[e - 1u];   // cutoff, color.w, image
+    float a = rec.y;
+    const uint32_t image = __float_as_uint(rec.z);
+    if (image < sc.n_images && sc.images[image].width != 0u) {   // (the host keeps a mask's image in the plain atlas: device.hip upload_alpha; a stub descriptor is never indexed)
+        // the texture coordinate exactly as shade_hit interpolates it (uv rides in position.w / normal.w of the shading record)
+        const float *tv = reinterpret_cast<const float *>(sc.tri_verts + kTriRec * (size_t)prim);
+        const float u0 = tv[3], v0 = tv[7], u1 = tv[11], v1 = tv[15], u2 = tv[19], v2 = tv[23];
+        const float bw = (1.0f - hu) - hv;
+        const float tu = (u0 * bw + u1 * hu) + u2 * hv;
+        const float tvv = (v0 * bw + v1 * hu) + v2 * hv;
+        // texture_lookup's taps and weights (SPEC §9), the alpha byte only, through b * (1 / 255): the plain 8x4-tiled image
+        const DImage im = sc.images[image];
+        const int W = (int)im.width, H = (int)im.height;
+        const float fx = tu * (float)W - 0.5f, fy = tvv * (float)H - 0.5f;
+        const float x0f = floorf(fx), y0f = floorf(fy);
+        const float tx = fx - x0f, ty = fy - y0f;
+        const int x0 = wrap_i((int)x0f, W), x1 = wrap_next(x0, W);
+        const int y0 = wrap_i((int)y0f, H), y1 = wrap_next(y0, H);
+        const uint8_t *base = sc.texels + 4u * (size_t)im.offset + 3u;
+        const uint32_t tiles_x = im.pad;
+        const uint32_t r0 = ((uint32_t)y0 >> 2) * tiles_x * 32u + ((uint32_t)y0 & 3u) * 8u, r1 = ((uint32_t)y1 >> 2) * tiles_x * 32u + ((uint32_t)y1 & 3u) * 8u;
+        const uint32_t c0 = ((uint32_t)x0 >> 3) * 32u + ((uint32_t)x0 & 7u), c1 = ((uint32_t)x1 >> 3) * 32u + ((uint32_t)x1 & 7u);
+        const float c00 = (float)base[4u * (size_t)(r0 + c0)] * 0.003921568859368563f, c10 = (float)base[4u * (size_t)(r0 + c1)] * 0.003921568859368563f;
+        const float c01 = (float)base[4u * (size_t)(r1 + c0)] * 0.003921568859368563f, c11 = (float)base[4u * (size_t)(r1 + c1)] * 0.003921568859368563f;
+        const float top = c00 * (1.0f - tx) + c10 * tx, bot = c01 * (1.0f - tx) + c11 * tx;
+        a = a * (top * (1.0f - ty) + bot * ty);
+    }
+    return !(a >= rec.x);
+}
+
 // returns true when the ray is finished (ANY: also as soon as something is hit; best.prim != ~0 then)
-template <bool STATS>
+// MASK (SPEC §20): a hit on a masked triangle whose alpha is below the cutoff is no hit — the only acceptance site that asks (device.hip launches a masked scene on this step only)
+template <bool STATS, bool MASK = false>
 __device__ __forceinline__ bool ray_step_any(const DScene &sc, RayState &rs, uint2 *stack, const bool ANY, uint32_t &n_nodes, uint32_t &n_tris, const uint8_t *lut = nullptr) {
     if (rs.tg.y == 0u) {
         if (!(rs.ng.y & 0xFF000000u)) {
@@ -524,6 +568,7 @@ __device__ __forceinline__ bool ray_step_any(const DScene &sc, RayState &rs, uin
         float t, u, v;
         if (ray_triangle(r0, r1, r2, rs.o, rs.d, rs.best.t, t, u, v)) {
             const uint32_t prim = sc.leaf_prim[ti];
+            if (MASK && alpha_rejects(sc, prim, u, v)) return false;   // as if §7 had rejected the triangle
             if (t < rs.best.t || prim < rs.best.prim) { rs.best.t = t; rs.best.u = u; rs.best.v = v; rs.best.prim = prim; }
             // the occluder's leaf slot, for the occluder-cache probe of the stats kernels (an any-hit ray's v is not read).  Round 5: only ray_step_pipe did this,
             // so `--opt pipe_rays=0` with stats on fed the probe a barycentric's bit pattern as a leaf slot: an out-of-bounds read (a GPU memory fault at bench size)
@@ -592,17 +637,17 @@ __device__ __forceinline__ bool ray_step_pipe(const DScene &sc, RayState &rs, ui
     return false;
 }
 
-template <bool ANY, bool STATS>
+template <bool ANY, bool STATS, bool MASK = false>
 __device__ __forceinline__ bool ray_step(const DScene &sc, RayState &rs, uint2 *stack, uint32_t &n_nodes, uint32_t &n_tris) {
-    return ray_step_any<STATS>(sc, rs, stack, ANY, n_nodes, n_tris);
+    return ray_step_any<STATS, MASK>(sc, rs, stack, ANY, n_nodes, n_tris);
 }
 
 // one ray start to finish (stand-alone queries)
-template <bool ANY, bool STATS>
+template <bool ANY, bool STATS, bool MASK = false>
 __device__ __forceinline__ bool traverse(const DScene &sc, f3 o, f3 d, float tmax, uint2 *stack, Hit &best, uint32_t &n_nodes, uint32_t &n_tris) {
     RayState rs;
     ray_begin(sc, rs, o, d, tmax);
-    while (!ray_step<ANY, STATS>(sc, rs, stack, n_nodes, n_tris)) {}
+    while (!ray_step<ANY, STATS, MASK>(sc, rs, stack, n_nodes, n_tris)) {}
     best = rs.best;
     return best.prim != 0xFFFFFFFFu;
 }
@@ -917,8 +962,10 @@ __device__ __forceinline__ TraceKernargsPtr trace_kernargs() {
 
 // TAIL: the variant whose waves finish their last rays cooperatively (tail_walk); kept to the 6 waves per SIMD of the one-round-trip step (without the attribute the
 // compiler takes the extra code as a licence for 90-100 VGPRs in the loop).  The other variants are compiled as before.
-template <bool STATS, bool PIPE = false, bool TAIL = false>
+// MASK (SPEC §20): the launches of a scene with alpha-masked materials — the plain per-lane step only (ray_step_any asks alpha_rejects), no tail, no step budget
+template <bool STATS, bool PIPE = false, bool TAIL = false, bool MASK = false>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(TAIL ? 6 : (PIPE && !STATS ? 7 : 1)))) void k_trace(const TraceKernargs a) {
+    static_assert(!MASK || (!PIPE && !TAIL), "a masked scene traces on the two-round-trip step: the only acceptance site that evaluates SPEC §20");
     const DScene &sc = a.sc;
     FrameCounters *const ctr = a.ctr;      // (the prologue and the stats epilogue; the loop re-reads it where it needs it)
     const int cb = a.cb, sb = a.sb, refill = a.refill;
@@ -1042,7 +1089,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(TAI
             w_node += (uint32_t)__popcll(__ballot(PIPE ? active && (rs.tg2.y == 0u) && ((rs.ng.y & 0xFF000000u) != 0u || rs.sp != 0) : active && (rs.tg.y == 0u)));
         }
         if ((STATS || budget) && active) my_steps++;
-        if (active && (PIPE ? ray_step_pipe<STATS, PLACE>(sc, rs, stack, shadow, dn, dt, lut) : ray_step_any<STATS>(sc, rs, stack, shadow, dn, dt, lut))) {
+        if (active && (PIPE ? ray_step_pipe<STATS, PLACE>(sc, rs, stack, shadow, dn, dt, lut) : ray_step_any<STATS, MASK>(sc, rs, stack, shadow, dn, dt, lut))) {
             active = false;
             finished = true;
         }
@@ -1334,6 +1381,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8))
 }
 
 // stand-alone closest-hit query (lpt_trace_closest): one ray per lane, no refill
+template <bool MASK = false>
 __global__ __launch_bounds__(kTraceBlock) void k_query_closest(DScene sc, const float4 *o, const float4 *d, float4 *hits, uint32_t n) {
     uint2 *stack = reinterpret_cast<uint2 *>(lds_dyn) + threadIdx.x;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1342,7 +1390,7 @@ __global__ __launch_bounds__(kTraceBlock) void k_query_closest(DScene sc, const 
     const f3 oo = mk3(o4.x, o4.y, o4.z), dd = mk3(d4.x, d4.y, d4.z);
     Hit h;
     uint32_t a = 0, b = 0;
-    traverse<false, false>(sc, oo, dd, LPT_T_INF, stack, h, a, b);
+    traverse<false, false, MASK>(sc, oo, dd, LPT_T_INF, stack, h, a, b);
     intersect_lights(sc, oo, dd, h);
     hits[i] = make_float4(h.t, h.u, h.v, __uint_as_float(h.prim));
 }
@@ -2439,6 +2487,7 @@ __global__ __launch_bounds__(kBlock) void k_tonemap(const float4 *accum, uchar4 
 }
 
 // stand-alone ray queries (lpt_trace_closest / lpt_trace_occluded)
+template <bool MASK = false>
 __global__ __launch_bounds__(kTraceBlock) void k_query_occluded(DScene sc, const float4 *o, const float4 *d, uint8_t *out, uint32_t n) {
     uint2 *stack = reinterpret_cast<uint2 *>(lds_dyn) + threadIdx.x;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2446,7 +2495,7 @@ __global__ __launch_bounds__(kTraceBlock) void k_query_occluded(DScene sc, const
     const float4 o4 = o[i], d4 = d[i];
     Hit h;
     uint32_t a = 0, b = 0;
-    out[i] = traverse<true, false>(sc, mk3(o4.x, o4.y, o4.z), mk3(d4.x, d4.y, d4.z), o4.w, stack, h, a, b) ? 1 : 0;
+    out[i] = traverse<true, false, MASK>(sc, mk3(o4.x, o4.y, o4.z), mk3(d4.x, d4.y, d4.z), o4.w, stack, h, a, b) ? 1 : 0;
 }
 
 

@@ -191,6 +191,7 @@ bool decode_png(const uint8_t *data, size_t size, Image &out) {
         }
     }
     out.width = w; out.height = h;
+    out.has_alpha = ctype == 6;   // SPEC §20: the only layout whose alpha reaches rgba8's fourth byte (grey + alpha lands in r, g by the rule below; tRNS is not read)
     out.rgba8.assign((size_t)w * h * 4, 0);  // gltf.rs:26-38: channels the source lacks stay 0
     const size_t step = depth / 8;
     for (size_t i = 0; i < (size_t)w * h; ++i) {

@@ -176,6 +176,30 @@ int lpt_scene_add_material(lpt_scene *s, const lpt_material *m, uint32_t *out_in
     return LPT_OK;
 }
 
+// ---- alpha-masked materials (SPEC §20): a side table of `materials`, grown on the first write
+int lpt_scene_set_material_alpha(lpt_scene *s, uint32_t material_index, uint32_t mode, float cutoff, uint32_t alpha_image) {
+    if (!s) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_alpha: null");
+    if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_alpha: material %u of %zu", material_index, s->materials.size());
+    if (mode > LPT_ALPHA_MASK) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_alpha: unknown mode %u", mode);
+    if (!std::isfinite(cutoff) || cutoff < 0.f) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_alpha: the cutoff must be finite and >= 0");
+    if (alpha_image != LPT_INVALID_INDEX && alpha_image >= s->images.size())
+        return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_alpha: image %u of %zu", alpha_image, s->images.size());
+    if (s->alpha.size() < s->materials.size()) s->alpha.resize(s->materials.size());
+    MaterialAlpha &a = s->alpha[material_index];
+    a.mode = mode; a.cutoff = cutoff; a.image = alpha_image;
+    return LPT_OK;
+}
+
+int lpt_scene_get_material_alpha(const lpt_scene *s, uint32_t material_index, uint32_t *mode, float *cutoff, uint32_t *alpha_image) {
+    if (!s) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_alpha: null");
+    if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_alpha: material %u of %zu", material_index, s->materials.size());
+    const MaterialAlpha a = s->material_alpha(material_index);
+    if (mode) *mode = a.mode;
+    if (cutoff) *cutoff = a.cutoff;
+    if (alpha_image) *alpha_image = a.image;
+    return LPT_OK;
+}
+
 int lpt_scene_add_image(lpt_scene *s, const uint8_t *rgba8, uint32_t w, uint32_t h, uint32_t *out_index) {
     if (!s || !rgba8 || !w || !h) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_add_image: null or empty");
     Image im;
