@@ -58,6 +58,22 @@ impl Device {
     }
     fn h(&self) -> *mut ffi::lpt_device { self.inner.h }
     pub fn synchronize(&self) -> Result<(), Error> { check(unsafe { ffi::lpt_device_synchronize(self.h()) }) }
+    /// the shading kernels' interface event on the GPU (SPEC.md §21), once per element -> (next direction, weight, kind: 0 reflected / 1 transmitted)
+    #[allow(clippy::too_many_arguments)]
+    pub fn interface_sample(&self, dirs: &[[f32; 3]], ns: &[[f32; 3]], ngf: &[[f32; 3]], entering: &[u32], base: &[[f32; 3]], ior: &[f32], thin: &[u32],
+                            r4: &[f32]) -> Result<(Vec<[f32; 3]>, Vec<[f32; 3]>, Vec<u32>), Error> {
+        let n = dirs.len();
+        if [ns.len(), ngf.len(), entering.len(), base.len(), ior.len(), thin.len(), r4.len()].iter().any(|&l| l != n) {
+            return Err(Error::InvalidArg("interface_sample: the inputs differ in length".into()));
+        }
+        let (mut wi, mut weight, mut kind) = (vec![[0f32; 3]; n], vec![[0f32; 3]; n], vec![0u32; n]);
+        check(unsafe {
+            ffi::lpt_interface_sample(self.h(), n as u32, dirs.as_ptr() as *const f32, ns.as_ptr() as *const f32, ngf.as_ptr() as *const f32, entering.as_ptr(),
+                                      base.as_ptr() as *const f32, ior.as_ptr(), thin.as_ptr(), r4.as_ptr(), wi.as_mut_ptr() as *mut f32,
+                                      weight.as_mut_ptr() as *mut f32, kind.as_mut_ptr())
+        })?;
+        Ok((wi, weight, kind))
+    }
 }
 
 /// reference `crates/lib/src/scene.rs:30-54` `Scene` (`Scene::default()` seeds one dummy element per array)
@@ -106,6 +122,16 @@ impl Scene {
         let (mut mode, mut cutoff, mut image) = (0u32, 0f32, 0u32);
         check(unsafe { ffi::lpt_scene_get_material_alpha(self.h, material, &mut mode, &mut cutoff, &mut image) })?;
         Ok((mode, cutoff, image))
+    }
+    /// SPEC.md §21: transmissive materials (glass); `factor` 0 = opaque, `thin_walled`: a pane without thickness, else the boundary of a closed solid
+    pub fn set_material_transmission(&mut self, material: u32, factor: f32, ior: f32, thin_walled: bool) -> Result<(), Error> {
+        check(unsafe { ffi::lpt_scene_set_material_transmission(self.h, material, factor, ior, thin_walled as u32) })
+    }
+    /// -> (factor, ior, thin_walled)
+    pub fn material_transmission(&self, material: u32) -> Result<(f32, f32, bool), Error> {
+        let (mut factor, mut ior, mut thin) = (0f32, 0f32, 0u32);
+        check(unsafe { ffi::lpt_scene_get_material_transmission(self.h, material, &mut factor, &mut ior, &mut thin) })?;
+        Ok((factor, ior, thin != 0))
     }
     /// SPEC.md §19: a point / spot / directional light (KHR_lights_punctual); records from `punctual_light`
     pub fn add_punctual_light(&mut self, light: &ffi::lpt_punctual_light) -> Result<u32, Error> {

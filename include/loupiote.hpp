@@ -31,6 +31,11 @@ class Device {  // device.rs:72-141
     Device &operator=(const Device &) = delete;
     lpt_device *inner() const { return h_; }
     void synchronize() { check(lpt_device_synchronize(h_)); }
+    /// SPEC.md §21, the shading kernels' interface event on the GPU, once per element (see lpt_interface_sample)
+    void interface_sample(uint32_t n, const float *dirs, const float *ns, const float *ngf, const uint32_t *entering, const float *base, const float *ior,
+                          const uint32_t *thin, const float *r4, float *wi, float *weight, uint32_t *kind) const {
+        check(lpt_interface_sample(h_, n, dirs, ns, ngf, entering, base, ior, thin, r4, wi, weight, kind));
+    }
 
    private:
     lpt_device *h_ = nullptr;
@@ -84,6 +89,18 @@ class Scene {  // scene.rs:30-54
         MaterialAlpha a{};
         check(lpt_scene_get_material_alpha(h_, material, &a.mode, &a.cutoff, &a.alpha_image));
         return a;
+    }
+    // SPEC.md §21: transmissive materials (glass); factor 0 = opaque, thin_walled: a pane without thickness, else the boundary of a closed solid
+    struct MaterialTransmission { float factor; float ior; bool thin_walled; };
+    void set_material_transmission(uint32_t material, float factor, float ior = 1.5f, bool thin_walled = true) {
+        check(lpt_scene_set_material_transmission(h_, material, factor, ior, thin_walled ? 1u : 0u));
+    }
+    MaterialTransmission material_transmission(uint32_t material) const {
+        MaterialTransmission t{};
+        uint32_t thin = 0;
+        check(lpt_scene_get_material_transmission(h_, material, &t.factor, &t.ior, &thin));
+        t.thin_walled = thin != 0;
+        return t;
     }
     // SPEC.md §19: point / spot / directional lights (KHR_lights_punctual); records from point_light / spot_light / directional_light below
     uint32_t add_punctual_light(const lpt_punctual_light &l) { uint32_t id = 0; check(lpt_scene_add_punctual_light(h_, &l, &id)); return id; }

@@ -272,6 +272,15 @@ int lpt_punctual_light_make(uint32_t type, const float *position, const float *d
 int lpt_scene_set_material_alpha(lpt_scene *scene, uint32_t material_index, uint32_t mode, float cutoff, uint32_t alpha_image);
 int lpt_scene_get_material_alpha(const lpt_scene *scene, uint32_t material_index, uint32_t *mode, float *cutoff, uint32_t *alpha_image);
 
+/* build-only extension (SPEC.md §21; the reference's loader reads no KHR_materials_transmission): transmissive materials.  A second
+ * side table beside the 32-byte lpt_material, opaque (factor 0) by default.  With factor tr in (0, 1] a hit on the material is, with
+ * probability tr * (1 - metallic), a smooth dielectric interface of index `ior`: Fresnel reflection or refraction, tinted by the base
+ * colour when transmitted.  `thin_walled` != 0: a pane without thickness (the ray goes straight on); 0: the boundary of a closed
+ * solid with outward winding.  factor 0 returns the material to opaque.  LPT_ERR_INVALID_ARG, and nothing changed, for a material
+ * index out of range, a factor outside [0, 1], an ior below 1, a non-finite number.  Out-pointers of the getter may be NULL. */
+int lpt_scene_set_material_transmission(lpt_scene *scene, uint32_t material_index, float factor, float ior, uint32_t thin_walled);
+int lpt_scene_get_material_transmission(const lpt_scene *scene, uint32_t material_index, float *factor, float *ior, uint32_t *thin_walled);
+
 /* Read-back of the flat arrays (the reference exposes them as pub Vec fields). */
 int lpt_scene_get_materials(const lpt_scene *s, uint32_t first, uint32_t count, lpt_material *dst);
 int lpt_scene_get_entries(const lpt_scene *s, uint32_t first, uint32_t count, lpt_blas_entry *dst);
@@ -353,6 +362,14 @@ int lpt_scene_gpu_update_punctual(lpt_scene_gpu *scene_gpu, const lpt_scene *sce
  * colour x intensity x 1/d^2 x range window x cone window); all zero where there is no sample (the point IS the light).  Blocking; host arrays. */
 int lpt_scene_gpu_sample_punctual(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t light_index, const float *points, uint32_t n,
                                   float *wi, float *dist, float *E);
+
+/* build-only extension (SPEC.md §21), for tests and tools in the manner of lpt_probe_sample: the interface event of the shading kernels
+ * (kernels.h interface_sample), once per element.  Inputs, n of each: dirs[n][3] the ray's unit direction d, ns[n][3] the shading
+ * normal, ngf[n][3] the geometric normal flipped against d, entering[n] (non-zero: the geometric normal was not flipped), base[n][3]
+ * the base colour, ior[n], thin[n] (non-zero: thin-walled), r4[n] the uniform that picks reflection against the Fresnel term.
+ * Outputs: wi[n][3] the next direction, weight[n][3], kind[n] (0 = reflected, 1 = transmitted).  Blocking; host arrays. */
+int lpt_interface_sample(lpt_device *dev, uint32_t n, const float *dirs, const float *ns, const float *ngf, const uint32_t *entering,
+                         const float *base, const float *ior, const uint32_t *thin, const float *r4, float *wi, float *weight, uint32_t *kind);
 
 /* replaces: ProbeGPU::new(device, queue, data, width, height)
  * (crates/lib/src/scene.rs:72-121): 4 bytes/pixel RGBE8, equirectangular. */

@@ -99,6 +99,8 @@ SIGNATURES = {
     "lpt_punctual_light_make": (_i, [_u32, _vp, _vp, _vp, _f, _f, _f, _f, _vp]),
     "lpt_scene_set_material_alpha": (_i, [_vp, _u32, _u32, _f, _u32]),
     "lpt_scene_get_material_alpha": (_i, [_vp, _u32, _pu32, C.POINTER(_f), _pu32]),
+    "lpt_scene_set_material_transmission": (_i, [_vp, _u32, _f, _f, _u32]),
+    "lpt_scene_get_material_transmission": (_i, [_vp, _u32, C.POINTER(_f), C.POINTER(_f), _pu32]),
     "lpt_scene_get_materials": (_i, [_vp, _u32, _u32, _vp]),
     "lpt_scene_get_entries": (_i, [_vp, _u32, _u32, _vp]),
     "lpt_scene_get_vertices": (_i, [_vp, _u32, _u32, _vp]),
@@ -120,6 +122,7 @@ SIGNATURES = {
     "lpt_scene_gpu_update_instances": (_i, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "lpt_scene_gpu_update_punctual": (_i, [_vp, _vp]),
     "lpt_scene_gpu_sample_punctual": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "lpt_interface_sample": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lpt_probe_upload": (_i, [_vp, _vp, _u32, _u32, _pvp]),
     "lpt_probe_destroy": (_i, [_vp]),
     "lpt_env_distribution": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),

@@ -65,6 +65,20 @@ class Device:
     def synchronize(self):
         _check(A.lib().lpt_device_synchronize(self._h))
 
+    def interface_sample(self, dirs, ns, ngf, entering, base, ior, thin, r4):
+        """The interface event of the shading kernels (SPEC.md §21) on the GPU, once per element: dirs / ns / ngf / base [n, 3], entering / ior /
+        thin / r4 [n] -> (wi[n, 3], weight[n, 3], kind[n]: 0 reflected, 1 transmitted)."""
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        n = d.shape[0]
+        v3 = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), (n, 3)))
+        f1 = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), (n,)))
+        u1 = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a).astype(bool).astype(np.uint32), (n,)))
+        ns, ngf, base, ior, r4, entering, thin = v3(ns), v3(ngf), v3(base), f1(ior), f1(r4), u1(entering), u1(thin)
+        wi, weight, kind = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+        _check(A.lib().lpt_interface_sample(self._h, n, A.ptr(d), A.ptr(ns), A.ptr(ngf), A.ptr(entering), A.ptr(base), A.ptr(ior), A.ptr(thin), A.ptr(r4),
+                                            A.ptr(wi), A.ptr(weight), A.ptr(kind)))
+        return wi, weight, kind
+
     def close(self):
         if self._h:
             A.lib().lpt_device_destroy(self._h)
@@ -215,6 +229,18 @@ class Scene:
         mode, cutoff, image = C.c_uint32(), C.c_float(), C.c_uint32()
         _check(A.lib().lpt_scene_get_material_alpha(self._h, int(material_index), C.byref(mode), C.byref(cutoff), C.byref(image)))
         return int(mode.value), float(cutoff.value), int(image.value)
+
+    # SPEC §21: transmissive materials; a second side table of the materials, opaque (factor 0) by default
+    def set_material_transmission(self, material_index, factor, ior=1.5, thin_walled=True):
+        """a hit on the material is, with probability factor x (1 - metallic), a smooth dielectric interface of index `ior` (Fresnel reflection or
+        refraction, tinted by the base colour); thin_walled: a pane without thickness, else the boundary of a closed solid.  factor 0: opaque again"""
+        _check(A.lib().lpt_scene_set_material_transmission(self._h, int(material_index), float(factor), float(ior), 1 if thin_walled else 0))
+
+    def material_transmission(self, material_index):
+        """-> (factor, ior, thin_walled)"""
+        factor, ior, thin = C.c_float(), C.c_float(), C.c_uint32()
+        _check(A.lib().lpt_scene_get_material_transmission(self._h, int(material_index), C.byref(factor), C.byref(ior), C.byref(thin)))
+        return float(factor.value), float(ior.value), bool(thin.value)
 
     def _get(self, fn, dt, count):
         out = np.zeros(count, dt)

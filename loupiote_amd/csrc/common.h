@@ -30,6 +30,13 @@ struct MaterialAlpha {
     uint32_t image = LPT_INVALID_INDEX;
 };
 
+// SPEC §21: a material's transmission state, a second side table; factor 0 = opaque (the default)
+struct MaterialTransmission {
+    float factor = 0.0f;
+    float ior = 1.5f;
+    uint32_t thin_walled = 1u;
+};
+
 }  // namespace lpt
 
 // The CPU-side scene: the flat arrays of the reference's Scene / BLASArray
@@ -45,6 +52,8 @@ struct lpt_scene {
     std::vector<lpt_punctual_light> punctual;   // SPEC §19: point / spot / directional lights; no dummy element, a fresh scene has none
     std::vector<lpt::MaterialAlpha> alpha;      // SPEC §20: side table of `materials`; a material beyond its end is opaque (material_alpha)
     lpt::MaterialAlpha material_alpha(size_t i) const { return i < alpha.size() ? alpha[i] : lpt::MaterialAlpha(); }
+    std::vector<lpt::MaterialTransmission> transmission;   // SPEC §21: side table of `materials`; a material beyond its end is opaque (material_transmission)
+    lpt::MaterialTransmission material_transmission(size_t i) const { return i < transmission.size() ? transmission[i] : lpt::MaterialTransmission(); }
 };
 
 namespace lpt {

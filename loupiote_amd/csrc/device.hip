@@ -147,6 +147,7 @@ struct lpt_scene_gpu {
     DevTree tree;
     DevMem tri_verts, materials, lights, texels, images, srgb_lut, pair_texels, pair_images;
     DevMem punctual;                // SPEC §19: lpt_punctual_light records (DScene::punctual)
+    DevMem trans_tri, trans_recs;   // SPEC §21: the per-triangle table and the records of the transmissive materials (DScene::trans_tri / trans_recs); empty without glass
     DevMem alpha_tri, alpha_recs;   // SPEC §20: the per-triangle table and the records of the masked materials (DScene::alpha_tri / alpha_recs); empty without masks
     TexturePairs pairs;
     lpt_accel_stats stats{};
@@ -853,6 +854,44 @@ static int commit_alpha(lpt_scene_gpu *sg, const AlphaTables &at) {
     return LPT_OK;
 }
 
+// SPEC §21: the transmission tables, derived and committed as the alpha tables are — one record {transmission, ior, thin, 0} per transmissive material that an
+// instance with triangles uses, one uint32 per baked triangle (keyed by prim id).  Both empty for a scene without glass in use, which then launches what it always launched.
+struct TransTables { std::vector<float4> recs; std::vector<uint32_t> tri; };
+static int derive_trans(const lpt_scene_gpu *sg, const lpt_scene &scene, TransTables &out) {
+    std::vector<uint32_t> rec_of(scene.materials.size(), 0u);   // 1 + record index
+    for (size_t i = 0; i < scene.instances.size() && i < sg->inst_count.size(); ++i) {
+        const uint32_t n = sg->inst_count[i];
+        if (!n) continue;
+        const uint32_t mat = scene.instances[i].material_index < scene.materials.size() ? scene.instances[i].material_index : 0u;   // SPEC §2.5
+        const MaterialTransmission t = scene.material_transmission(mat);
+        if (!(t.factor > 0.0f)) continue;
+        if (!rec_of[mat]) {
+            out.recs.push_back(make_float4(t.factor, t.ior, t.thin_walled ? 1.0f : 0.0f, 0.f));
+            rec_of[mat] = (uint32_t)out.recs.size();
+        }
+        if (out.tri.empty()) out.tri.assign(std::max(sg->d.n_tris, 1u), 0u);
+        if ((size_t)sg->inst_first[i] + n > out.tri.size()) return fail(LPT_ERR_INVALID_ARG, "instance %zu lies beyond the baked triangles", i);
+        std::fill(out.tri.begin() + sg->inst_first[i], out.tri.begin() + sg->inst_first[i] + n, rec_of[mat]);
+    }
+    return LPT_OK;
+}
+static int commit_trans(lpt_scene_gpu *sg, const TransTables &tt) {
+    DScene &d = sg->d;
+    if (tt.recs.empty()) {
+        sg->trans_tri.reset(); sg->trans_recs.reset();
+        d.trans_tri = nullptr; d.trans_recs = nullptr; d.n_trans = 0u;
+        return LPT_OK;
+    }
+    hipStream_t s = sg->dev->stream;
+    TRY(upload(sg->trans_tri, tt.tri, s));
+    TRY(upload(sg->trans_recs, tt.recs, s));
+    HIP_TRY(hipStreamSynchronize(s));   // the host vectors are the caller's
+    d.trans_tri = as<const uint32_t>(sg->trans_tri);
+    d.trans_recs = as<const float4>(sg->trans_recs);
+    d.n_trans = (uint32_t)tt.recs.size();
+    return LPT_OK;
+}
+
 int lpt_scene_upload(lpt_device *dev, const lpt_scene *scene, lpt_scene_gpu **out) { return lpt_scene_upload_ex(dev, scene, LPT_ACCEL_BUILD_HOST_SAH, out); }
 
 int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags, lpt_scene_gpu **out) {
@@ -946,6 +985,9 @@ int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags,
         AlphaTables at;
         TRY(derive_alpha(sg.get(), *scene, at));
         TRY(commit_alpha(sg.get(), at));
+        TransTables tt;
+        TRY(derive_trans(sg.get(), *scene, tt));
+        TRY(commit_trans(sg.get(), tt));
     }
     sg->stats.triangles = d.n_tris;
     sg->stats.node_bytes = (uint32_t)sizeof(Node8);
@@ -991,6 +1033,8 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
         // SPEC §20: an instance whose material changed may have become masked or opaque; checked before anything is baked
         AlphaTables at;
         TRY(derive_alpha(sg, *scene, at));
+        TransTables tt;   // ... or transmissive (SPEC §21)
+        TRY(derive_trans(sg, *scene, tt));
         // re-bake on the device (the object-space meshes are resident, only the transforms travel); a place-driven scatter then takes the new
         // Woop maps to every place a triangle has in the tree (a split triangle has several)
         DevMem woop_prim;
@@ -1004,6 +1048,7 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
         }
         if (st != LPT_OK) return st;
         TRY(commit_alpha(sg, at));
+        TRY(commit_trans(sg, tt));
         if (sg->stats.triangles) TRY(refit(sg));
     }
     if (out_rebaked) *out_rebaked = (uint32_t)changed.size();
@@ -1022,6 +1067,9 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
         AlphaTables at;   // SPEC §20: a rebuild re-derives the alpha tables whether or not an instance changed
         TRY(derive_alpha(sg, *scene, at));
         TRY(commit_alpha(sg, at));
+        TransTables tt;   // ... and the transmission tables (SPEC §21)
+        TRY(derive_trans(sg, *scene, tt));
+        TRY(commit_trans(sg, tt));
         return upload_punctual(sg, *scene);
     }
     HIP_TRY(hipSetDevice(sg->dev->ordinal));
@@ -1032,6 +1080,9 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
         AlphaTables at;   // ... and so are the materials' alpha states (SPEC §20)
         TRY(derive_alpha(sg, *scene, at));
         TRY(commit_alpha(sg, at));
+        TransTables tt;   // ... and their transmission states (SPEC §21)
+        TRY(derive_trans(sg, *scene, tt));
+        TRY(commit_trans(sg, tt));
     }
     DevMem woop_prim;
     TRY(dev_alloc(woop_prim, sizeof(WoopTri) * (size_t)n));
@@ -1083,6 +1134,36 @@ int lpt_scene_gpu_sample_punctual(lpt_device *dev, const lpt_scene_gpu *sg, uint
     HIP_TRY(hipMemcpy(wi, dw.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(dist, dd.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(E, de.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
+    return LPT_OK;
+}
+
+// SPEC §21: the interface event of the shading kernels (kernels.h interface_sample), once per element, for tests and tools
+int lpt_interface_sample(lpt_device *dev, uint32_t n, const float *dirs, const float *ns, const float *ngf, const uint32_t *entering, const float *base, const float *ior,
+                         const uint32_t *thin, const float *r4, float *wi, float *weight, uint32_t *kind) {
+    if (!dev || (n && (!dirs || !ns || !ngf || !entering || !base || !ior || !thin || !r4 || !wi || !weight || !kind))) return fail(LPT_ERR_INVALID_ARG, "lpt_interface_sample: null");
+    if (!n) return LPT_OK;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    // one input block: d, Ns, Ngf, base (3 floats each), ior, r4, then entering and thin as uint32 — 16 words per element; one output block: wi, weight, kind — 7 words
+    std::vector<uint32_t> in(16u * (size_t)n, 0u);
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t *e = in.data() + 16u * i;
+        memcpy(e, dirs + 3u * i, 12); memcpy(e + 3, ns + 3u * i, 12); memcpy(e + 6, ngf + 3u * i, 12); memcpy(e + 9, base + 3u * i, 12);
+        memcpy(e + 12, ior + i, 4); memcpy(e + 13, r4 + i, 4);
+        e[14] = entering[i] ? 1u : 0u; e[15] = thin[i] ? 1u : 0u;
+    }
+    DevMem din, dout;
+    TRY(dev_alloc(din, sizeof(uint32_t) * in.size()));
+    TRY(dev_alloc(dout, sizeof(uint32_t) * 7u * (size_t)n));
+    HIP_TRY(hipMemcpy(din.get(), in.data(), sizeof(uint32_t) * in.size(), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_interface_sample, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, as<const uint32_t>(din), n, as<uint32_t>(dout));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    std::vector<uint32_t> res(7u * (size_t)n);
+    HIP_TRY(hipMemcpy(res.data(), dout.get(), sizeof(uint32_t) * res.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(wi + 3u * i, res.data() + 7u * i, 12); memcpy(weight + 3u * i, res.data() + 7u * i + 3u, 12);
+        kind[i] = res[7u * i + 6u];
+    }
     return LPT_OK;
 }
 
@@ -1957,6 +2038,9 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
     // only acceptance site that asks the mask.  No packets, no cooperative walks, no path kernel, no tail, no step budget, no occluder probe: each of them accepts hits
     // on its own.  Otherwise exactly the default launches
     const bool masked = sc.n_alpha != 0u;
+    // SPEC §21: a scene with a transmissive material in use shades with k_shade<..., TRANS> on the per-bounce launches and stays off the path kernel, whose
+    // instantiations therefore do not double.  The traversal — packets, tail, cooperative walks — sees glass as geometry.  Otherwise exactly the default launches
+    const bool trans = sc.n_trans != 0u;
     if (r->timings) { r->ring_pos++; harvest_slot(r, cur_slot(r)); }
 
     tk.stages = 0; tk.run = nullptr;
@@ -2005,7 +2089,7 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
         // LPT_EXP_LANE_PHASE): stage 0 = counters, ray generation and the primary rays (with the path kernel: the whole wavefront),
         // stage b + 1 = shade(b) and the traversal launch behind it.  `ph` orders the stage against the other lanes' (stream events only).
         // The closure holds copies of what the launches read; `r`'s buffers and the scene do not change before the submission is enqueued.
-        const bool path = !masked && r->path_rays && n_rays <= r->path_rays && !coop_all;   // the primary hits are there, whichever kernel found them
+        const bool path = !masked && !trans && r->path_rays && n_rays <= r->path_rays && !coop_all;   // the primary hits are there, whichever kernel found them
         const int slot = cur_slot(r);
         Wavefront *w = &wf;
         tk.stages = nb + 1u;
@@ -2091,11 +2175,12 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
                 const uint32_t seed = seed0 + t;     // += 1 per bounce (:453, :487)
                 const Queue qin = w->q[b & 1u], qout = w->q[(b + 1u) & 1u];
                 stage_begin(r, ST_SHADE, s, slot);            // :471-480, :502-508
-                auto launch_shade = [&](auto G, auto P) {   // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); ENV / PUNCT as for k_path
-                    constexpr bool g = decltype(G)::value, pu = decltype(P)::value;
-                    if (env) hipLaunchKernelGGL((k_shade<g, true, pu, DEnv>), dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues, ev);
-                    else hipLaunchKernelGGL((k_shade<g, false, pu>), dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues);
+                auto launch_shade_t = [&](auto G, auto P, auto Tr) {   // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); ENV / PUNCT as for k_path; TRANS: SPEC §21
+                    constexpr bool g = decltype(G)::value, pu = decltype(P)::value, tr = decltype(Tr)::value;
+                    if (env) hipLaunchKernelGGL((k_shade<g, true, pu, tr, DEnv>), dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues, ev);
+                    else hipLaunchKernelGGL((k_shade<g, false, pu, tr>), dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues);
                 };
+                auto launch_shade = [&](auto G, auto P) { if (trans) launch_shade_t(G, P, std::true_type{}); else launch_shade_t(G, P, std::false_type{}); };
                 if (denoise && b == 0u) { if (punct) launch_shade(std::true_type{}, std::true_type{}); else launch_shade(std::true_type{}, std::false_type{}); }
                 else if (punct) launch_shade(std::false_type{}, std::true_type{});
                 else launch_shade(std::false_type{}, std::false_type{});

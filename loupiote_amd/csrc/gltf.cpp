@@ -283,6 +283,8 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
     const Json &mats = d.js.at("materials");
     struct Mask { uint32_t material; float cutoff; uint32_t image; };
     std::vector<Mask> masks;
+    struct Glass { uint32_t material; float factor, ior; uint32_t thin; };
+    std::vector<Glass> glasses;
     for (size_t i = 0; i < mats.size(); ++i) {
         const Json &pbr = mats[i].at("pbrMetallicRoughness");
         lpt_material m = {{1.f, 1.f, 1.f, 1.f}, 1.f, 1.f, LPT_INVALID_INDEX, LPT_INVALID_INDEX};
@@ -304,6 +306,23 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
         if (jmode) {
             if (!jmode->is_str() || !(jmode->str == "OPAQUE" || jmode->str == "MASK" || jmode->str == "BLEND")) bad("unknown alphaMode");
             if (jmode->str == "MASK") masks.push_back(Mask{(uint32_t)tmp.materials.size() - 1u, cutoff, m.albedo_texture});
+        }
+        // KHR_materials_transmission / _ior / _volume (SPEC §21, §14(8)): a positive transmissionFactor sets the side table; thicknessFactor > 0 makes the
+        // material the boundary of a solid, glTF's own rule.  The numbers are checked whatever the factor; a file without the extensions touches nothing
+        if (const Json *ext = mats[i].find("extensions")) {
+            auto number_of = [&](const char *extension, const char *key, double dflt) -> double {
+                const Json *e = ext->find(extension);
+                const Json *j = e ? e->find(key) : nullptr;
+                if (!j) return dflt;
+                if (j->kind != Json::Num || !std::isfinite(j->num) || !std::isfinite((float)j->num)) bad(std::string(extension) + "." + key + " is not a finite number");
+                return j->num;
+            };
+            const double factor = number_of("KHR_materials_transmission", "transmissionFactor", 0.0);
+            const double ior = number_of("KHR_materials_ior", "ior", 1.5);
+            const double thickness = number_of("KHR_materials_volume", "thicknessFactor", 0.0);
+            if (factor < 0.0 || factor > 1.0) bad("transmissionFactor outside [0, 1]");
+            if (ior < 1.0) bad("ior below 1");
+            if (factor > 0.0) glasses.push_back(Glass{(uint32_t)tmp.materials.size() - 1u, (float)factor, (float)ior, thickness > 0.0 ? 0u : 1u});
         }
     }
     const Json &nodes = d.js.at("nodes");
@@ -370,6 +389,8 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
         const uint32_t image = (k.image < tmp.images.size() && tmp.images[k.image].has_alpha) ? k.image : LPT_INVALID_INDEX;
         if (lpt_scene_set_material_alpha(&tmp, k.material, LPT_ALPHA_MASK, k.cutoff, image) != LPT_OK) bad(std::string("alphaMode MASK rejected: ") + lpt_last_error());
     }
+    for (const Glass &g : glasses)
+        if (lpt_scene_set_material_transmission(&tmp, g.material, g.factor, g.ior, g.thin) != LPT_OK) bad(std::string("KHR_materials_transmission rejected: ") + lpt_last_error());
     *scene = std::move(tmp);
 }
 

@@ -97,6 +97,11 @@ struct DScene {
     const uint32_t *alpha_tri;
     const float4 *alpha_recs;
     uint32_t n_alpha;
+    // SPEC §21: transmissive materials.  trans_tri[prim] = 0 for an opaque triangle, else 1 + the index of its record {transmission, ior, thin (1 / 0), 0}.
+    // Null / 0 for a scene without a transmissive material in use; read only by the TRANS instantiations of shade_hit / k_shade
+    const uint32_t *trans_tri;
+    const float4 *trans_recs;
+    uint32_t n_trans;
 };
 constexpr uint32_t kPairedBit = 0x40000000u;
 
@@ -1604,6 +1609,51 @@ __global__ __launch_bounds__(kBlock) void k_punctual_sample(DScene sc, uint32_t 
     E_out[j] = E.x; E_out[j + 1u] = E.y; E_out[j + 2u] = E.z;
 }
 
+// ------------------------------------------------------------------ transmission (SPEC §21)
+// The smooth dielectric interface event, §21's arithmetic once: d the ray's unit direction, Ns the shading normal, Ngf the geometric normal flipped against d,
+// entering = the geometric normal was not flipped.  Fresnel picks reflection (weight 1) against r4, else the ray refracts — or, thin-walled, goes straight on —
+// with weight `base`.  A result on the wrong side of Ngf is recomputed once with N = Ngf.  Every operation is binary32 with the parentheses of the SPEC.
+struct InterfaceOut { f3 wi, weight; bool transmit; };
+__device__ __forceinline__ bool interface_once(const f3 d, const f3 N, const f3 Ngf, const float eta, const bool thin, const float r4, f3 &wi, bool &transmit) {
+    const float c = min2(dot(neg(d), N), 1.0f);
+    const float s2 = (eta * eta) * max2(0.0f, 1.0f - c * c);
+    float Fr = 1.0f, ct = 0.0f;
+    if (!(s2 >= 1.0f)) {
+        ct = sqrtf(1.0f - s2);
+        const float rs = (eta * c - ct) / (eta * c + ct);
+        const float rp = (c - eta * ct) / (c + eta * ct);
+        Fr = 0.5f * (rs * rs + rp * rp);
+    }
+    if (r4 < Fr) {
+        transmit = false;
+        wi = normalize(N * (2.0f * c) + d);
+        return dot(wi, Ngf) > 0.0f;
+    }
+    transmit = true;
+    wi = thin ? d : normalize(d * eta + N * (eta * c - ct));
+    return dot(wi, Ngf) < 0.0f;
+}
+__device__ __forceinline__ InterfaceOut interface_sample(const f3 d, const f3 Ns, const f3 Ngf, const bool entering, const f3 base, const float ior, const bool thin, const float r4) {
+    InterfaceOut io;
+    const float eta = (thin || entering) ? 1.0f / ior : ior;
+    const f3 N = dot(neg(d), Ns) > 0.0f ? Ns : Ngf;
+    if (!interface_once(d, N, Ngf, eta, thin, r4, io.wi, io.transmit)) interface_once(d, Ngf, Ngf, eta, thin, r4, io.wi, io.transmit);
+    io.weight = io.transmit ? base : mk3(1.0f, 1.0f, 1.0f);
+    return io;
+}
+// lpt_interface_sample: the function shade_hit runs, one element per thread.  in: 16 words per element {d, Ns, Ngf, base, ior, r4, entering, thin}; out: 7 words {wi, weight, kind}
+__global__ __launch_bounds__(kBlock) void k_interface_sample(const uint32_t *in, uint32_t n, uint32_t *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t *e = in + 16u * (size_t)i;
+    auto f = [&](uint32_t k) { return __uint_as_float(e[k]); };
+    const InterfaceOut io = interface_sample(mk3(f(0), f(1), f(2)), mk3(f(3), f(4), f(5)), mk3(f(6), f(7), f(8)), e[14] != 0u, mk3(f(9), f(10), f(11)), f(12), e[15] != 0u, f(13));
+    uint32_t *o = out + 7u * (size_t)i;
+    o[0] = __float_as_uint(io.wi.x); o[1] = __float_as_uint(io.wi.y); o[2] = __float_as_uint(io.wi.z);
+    o[3] = __float_as_uint(io.weight.x); o[4] = __float_as_uint(io.weight.y); o[5] = __float_as_uint(io.weight.z);
+    o[6] = io.transmit ? 1u : 0u;
+}
+
 // ------------------------------------------------------------------ SPEC §15 helpers (denoiser path)
 __device__ __forceinline__ uint32_t oct_encode(f3 n) {
     float l1 = (fabsf(n.x) + fabsf(n.y)) + fabsf(n.z);
@@ -1668,6 +1718,8 @@ struct ShadeOut {
 // `load_o()` returns the ray's (origin, pdf) record — only emitter hits and the G-buffer need it —, `add_l(r, g, b)`
 // adds to the path's radiance.  ENV (SPEC §18): next-event estimation samples the probe too (distribution `ev`), and a miss is MIS-weighted.
 // PUNCT (SPEC §19): the scene has punctual lights, which take the share pk.p_p of the non-probe light samples; the other instantiations never read `pk`.
+// TRANS (SPEC §21): the scene has a transmissive material in use; a hit on such a triangle is an interface event with probability tr (1 - metal) — no next-event
+// estimation, a next ray without a pdf (the camera rays' -1) —, a hit on any other triangle runs the code of the other instantiations with r3 untouched.
 struct PunctPick { float p_p, p_pick; };   // the punctual share of the non-probe light samples; the probability with which ONE punctual light is picked
 template <bool ENV>
 __device__ __forceinline__ PunctPick punct_pick(const DScene &sc) {
@@ -1682,7 +1734,7 @@ __device__ __forceinline__ float rect_inv_nl(const DScene &sc, const PunctPick &
     if (PUNCT) return sc.n_lights ? ((ENV ? 0.5f : 1.0f) * (1.0f - pk.p_p)) / (float)sc.n_lights : 0.0f;
     return sc.n_lights ? (ENV ? 0.5f : 1.0f) / (float)sc.n_lights : 0.0f;   // ENV: a rectangle light is picked with 1 - p_env = 1/2
 }
-template <bool GBUF, bool ENV, bool PUNCT, typename LoadO, typename AddL>
+template <bool GBUF, bool ENV, bool PUNCT, bool TRANS = false, typename LoadO, typename AddL>
 __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe, const DEnv &ev, const DNoise &nz, const FrameParams &p, const float *s_lut,
                                           const uint32_t bounce, const bool last_bounce, const uint32_t seed_base, const float inv_nl, const PunctPick &pk, const GBufArgs &gb,
                                           const float4 d4, const float4 T4, const float4 h4, LoadO load_o, AddL add_l, ShadeOut &out) {
@@ -1742,6 +1794,7 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
             f3 Ns = mk3((N0.x * bw + N1.x * hu) + N2.x * hv, (N0.y * bw + N1.y * hu) + N2.y * hv, (N0.z * bw + N1.z * hu) + N2.z * hv);
             float n2 = dot(Ns, Ns);
             Ns = n2 > 0.0f ? Ns * (1.0f / sqrtf(n2)) : Ng;
+            const bool entering = !(dot(Ng, d) > 0.0f);   // (read by TRANS only)
             if (dot(Ng, d) > 0.0f) Ng = neg(Ng);
             if (dot(Ns, Ng) < 0.0f) Ns = neg(Ns);
             float tu = (P0.w * bw + P1.w * hu) + P2.w * hv;
@@ -1784,8 +1837,33 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
             float am = max2(max2(fabsf(P.x), fabsf(P.y)), fabsf(P.z));
             float eps = 1.0e-4f * (1.0f + am);
             const f3 Po = mk3(P.x + Ng.x * eps, P.y + Ng.y * eps, P.z + Ng.z * eps);
+            bool glass = false;   // TRANS: this hit is an interface event (SPEC §21)
+            if (TRANS) {
+                const uint32_t te = sc.trans_tri[prim];
+                if (te != 0u) {
+                    const float4 tr = sc.trans_recs[te - 1u];   // transmission, ior, thin
+                    const float pt = tr.x * (1.0f - clampf(metal, 0.0f, 1.0f));
+                    if (r3 < pt) {
+                        glass = true;
+                        if (!last_bounce) {
+                            const InterfaceOut io = interface_sample(d, Ns, Ng, entering, base, tr.y, tr.z != 0.0f, r4);
+                            const f3 Tn = mk3(T.x * io.weight.x, T.y * io.weight.y, T.z * io.weight.z);
+                            if (Tn.x > 0.0f || Tn.y > 0.0f || Tn.z > 0.0f) {
+                                const f3 Pn = io.transmit ? mk3(P.x - Ng.x * eps, P.y - Ng.y * eps, P.z - Ng.z * eps) : Po;
+                                out.want_next = true;
+                                out.no4 = make_float4(Pn.x, Pn.y, Pn.z, -1.0f);   // no pdf: what this ray finds is taken with weight 1
+                                out.nd4 = make_float4(io.wi.x, io.wi.y, io.wi.z, d4.w);
+                                out.nT4 = make_float4(Tn.x, Tn.y, Tn.z, T4.w);
+                            }
+                        }
+                    } else {
+                        r3 = (r3 - pt) / (1.0f - pt);
+                    }
+                }
+            }
             // next-event estimation
-            if (ENV && r0 < p_env) {   // the probe (SPEC §18)
+            if (TRANS && glass) {   // none at an interface
+            } else if (ENV && r0 < p_env) {   // the probe (SPEC §18)
                 f3 wi;
                 float ps;
                 if (env_sample(ev, r6, r7, r8, r9, r1, r2, wi, ps)) {
@@ -1878,7 +1956,7 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
                 }
             }
             // BSDF sample -> next ray
-            if (!last_bounce) {
+            if (!last_bounce && !(TRANS && glass)) {
                 f3 Ln, wgt;
                 float pdf;
                 if (bsdf_sample(sf, Ns, Ng, V, NoV, pspec, r3, r4, r5, Ln, wgt, pdf)) {
@@ -1909,8 +1987,12 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
 #ifndef LPT_SHADE_WAVES
 #define LPT_SHADE_WAVES(ENV, PUNCT) (((ENV) || (PUNCT)) ? 3 : 4)
 #endif
-template <bool GBUF, bool ENV = false, bool PUNCT = false, typename... Env>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LPT_SHADE_WAVES(ENV, PUNCT)))) void k_shade(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue qin, const float4 *hits,
+// TRANS (SPEC §21): the instantiations that run while the scene has a transmissive material in use
+#ifndef LPT_SHADE_WAVES_TRANS
+#define LPT_SHADE_WAVES_TRANS(ENV, PUNCT) 3
+#endif
+template <bool GBUF, bool ENV = false, bool PUNCT = false, bool TRANS = false, typename... Env>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TRANS ? LPT_SHADE_WAVES_TRANS(ENV, PUNCT) : LPT_SHADE_WAVES(ENV, PUNCT)))) void k_shade(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue qin, const float4 *hits,
                                                   Queue qout, ShadowQueue sq, float4 *Lsum, FrameCounters *ctr, int bounce,
                                                   uint32_t seed_base, GBufArgs gb, int sorted, Env... env) {
     static_assert(sizeof...(Env) == (ENV ? 1u : 0u), "the ENV instantiations take the distribution, the others nothing");
@@ -1941,7 +2023,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LPT_SHAD
         if (i < count) {
             const float4 d4 = ld_nt(qin.d + i), T4 = ld_nt(qin.T + i), h4 = ld_nt(hits + i);
             const uint32_t slot = __float_as_uint(d4.w);
-            shade_hit<GBUF, ENV, PUNCT>(sc, probe, ev, nz, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, gb, d4, T4, h4,
+            shade_hit<GBUF, ENV, PUNCT, TRANS>(sc, probe, ev, nz, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, gb, d4, T4, h4,
                             [&]() { return ld_nt(qin.o + i); },
                             [&](float r, float g, float b) {
                                 float4 L = Lsum[slot];

@@ -200,6 +200,28 @@ int lpt_scene_get_material_alpha(const lpt_scene *s, uint32_t material_index, ui
     return LPT_OK;
 }
 
+// ---- transmissive materials (SPEC §21): a second side table of `materials`, grown on the first write; factor 0 returns the material to opaque
+int lpt_scene_set_material_transmission(lpt_scene *s, uint32_t material_index, float factor, float ior, uint32_t thin_walled) {
+    if (!s) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_transmission: null");
+    if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_transmission: material %u of %zu", material_index, s->materials.size());
+    if (!std::isfinite(factor) || factor < 0.f || factor > 1.f) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_transmission: the factor must lie in [0, 1]");
+    if (!std::isfinite(ior) || ior < 1.f) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_transmission: the ior must be finite and >= 1");
+    if (s->transmission.size() < s->materials.size()) s->transmission.resize(s->materials.size());
+    MaterialTransmission &t = s->transmission[material_index];
+    t.factor = factor; t.ior = ior; t.thin_walled = thin_walled ? 1u : 0u;
+    return LPT_OK;
+}
+
+int lpt_scene_get_material_transmission(const lpt_scene *s, uint32_t material_index, float *factor, float *ior, uint32_t *thin_walled) {
+    if (!s) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_transmission: null");
+    if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_transmission: material %u of %zu", material_index, s->materials.size());
+    const MaterialTransmission t = s->material_transmission(material_index);
+    if (factor) *factor = t.factor;
+    if (ior) *ior = t.ior;
+    if (thin_walled) *thin_walled = t.thin_walled;
+    return LPT_OK;
+}
+
 int lpt_scene_add_image(lpt_scene *s, const uint8_t *rgba8, uint32_t w, uint32_t h, uint32_t *out_index) {
     if (!s || !rgba8 || !w || !h) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_add_image: null or empty");
     Image im;
