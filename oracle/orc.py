@@ -219,12 +219,17 @@ class Denoiser:
         except Exception:
             pass
 
-    def frame(self, view, mode=1):
+    def frame(self, view, mode=1, vfov=None, use_noise=False):
+        """one raytrace() call; `vfov` (kept for the frames that follow, as `set_vfov` is) and `use_noise` (the scene's noise texture,
+        `use_noise_texture`) may change from frame to frame"""
+        if vfov is not None:
+            self.vfov = vfov
         p = RenderParams()
         p.width, p.height = self.w, self.h
         p.view = (C.c_float * 16)(*[float(x) for x in np.asarray(view, np.float32).reshape(16)])
         p.vfov, p.max_bounces, p.user_seed, p.seed_counter, p.frames = self.vfov, self.bounces, self.user_seed, self.seed_counter, 1
         p.world_size = 1
+        p.use_noise = int(bool(use_noise))
         out = np.zeros((self.h, self.w, 4), np.float32)
         lib().orc_denoise_frame(self.h_, self.scene.h, C.byref(p), int(mode), _p(out))
         self.seed_counter += self.bounces
