@@ -28,6 +28,7 @@
 #include "env_dist.h"
 #include "kernels.h"
 #include "build_kernels.h"
+#include "launch_plan.h"
 #include <hipcub/hipcub.hpp>
 #include <rccl/rccl.h>
 
@@ -195,14 +196,9 @@ struct Wavefront {
     std::vector<hipEvent_t> trav;   // LPT_EXP_LANE_PHASE: trav[t] recorded on the lane's stream behind traversal launch t (0: the primary rays) of the lane's wavefront
 };
 constexpr int kMaxLanes = 4;
-constexpr uint32_t kStepBudget = 48u, kBudgetRays = 3000000u;  // defaults of LPT_EXP_STEP_BUDGET / LPT_EXP_BUDGET_RAYS (measured: profiles/r04_experiments_ab.txt H)
 constexpr float kPacketMaxPixelRad = 1.8e-3f;    // bounce 0 as packets up to this angle per pixel (measured: 1.53 mrad, 960x540: packets 4.46 against 4.51 ms; 2.05 mrad, 720x405: 3.32 against 3.20)
 constexpr uint32_t kOccEntries = 1u << 18;       // occluder-cache probe: 1 MB, L2-resident
-constexpr uint32_t kPathRays = 120000u;           // rays of a wavefront up to which the path kernel is used: the measured cross-over against the per-bounce launches with their tails in place
-                                                  // (whole frames, ms: 113 k rays 0.913 path / 0.932 per bounce, 147 k 1.07 / 0.99, 332 k 1.89 / 1.40; it was 450 000 against the budget pair)
 constexpr uint64_t kSplitRays = 3000000ull;       // a batch above this leaves as at least two wavefronts (LPT_EXP_SPLIT_RAYS)
-constexpr uint32_t kCoopRays = 32000u;            // rays of a wavefront up to which EVERY ray is traced by a whole wave (k_trace_coop over the queues): the measured cross-over (28 k rays:
-                                                  // 0.755 -> 0.652 ms per frame, 37 k: 0.765 -> 0.787; profiles/r05_experiments_ab.txt V)
 constexpr uint32_t kPacketBlocksPerCu = 128u;   // k_trace_packet's grid: one-wave blocks, packets dealt by stride (32 / 64 per CU: the same, round 5)
 constexpr uint32_t kCoopWavesPerCu = 32u;   // k_trace_coop's grid: a wave per straggler, most waves find none and leave (8 / 4 per CU: the same 2.90 ms per 1/8-shard frame, round 5)
 constexpr uint64_t kWavefrontRays = 1ull << 22;   // rays (pixel slots x samples) per wavefront an automatic submission aims at
@@ -230,14 +226,8 @@ struct lpt_renderer {
     struct Pending { float view[16]; uint32_t n = 0, frame_count0 = 1, seed0 = 0; bool acc0 = false; } pend;
     uint32_t max_fused = 0;    // 0 = auto: up to 64 calls wait for the next submission point, which cuts them into wavefronts of about 4 M rays
                                // (spatially: runs of tile rows x all the samples); n >= 1: n calls are ONE wavefront and launch when the n-th is recorded
-    uint32_t packet_primary = 2u;  // bounce 0 by packet traversal (k_trace_packet): 2 = where an 8x8-pixel patch is narrow enough (wavefront_trace), 1 = always, 0 = never (LPT_OPT_PACKET_PRIMARY)
-    uint32_t pipe_rays = 0x7FFFFFFFu;   // wavefronts of at most this many rays trace with the one-round-trip step (k_trace<.., PIPE>): all of them; LPT_EXP_PIPE_RAYS 0: none
+    LaunchTuning tune;         // which kernels a wavefront runs and their grids (launch_plan.h; lpt_renderer_set_option)
     uint64_t wavefront_rays = kWavefrontRays;   // LPT_OPT_WAVEFRONT_RAYS: tests cut small frames into many wavefronts
-    // wavefronts of at most this many rays run every bounce behind the primary hits in ONE launch (k_path: no chip-wide barrier per
-    // bounce); larger ones take the per-bounce launches, whose drains are then a few per cent.  LPT_OPT_PATH_RAYS; 0: never
-    uint32_t path_rays = kPathRays;
-    uint32_t path_waves_per_cu = 16;   // k_path: 4 waves per SIMD (kernels.h LPT_PATH_WAVES)
-    int path_refill = 32;              // k_path: a batch of lanes is shaded (and idle lanes start new paths) when at most this many lanes are tracing
     uint64_t n_recorded = 0, n_wavefronts = 0;   // raytrace() calls recorded / wavefronts submitted so far (lpt_renderer_get_submission_stats)
     int mode = LPT_BLIT_PATHTRACE;
     // build-only knobs
@@ -251,14 +241,7 @@ struct lpt_renderer {
     std::vector<uint32_t> h_offset;  // ... the staging offsets of the ranks (world + 1 entries, any world size) ...
     ShardTable *d_table = nullptr;   // ... and the rule's copy in device memory for the unpack kernels; refreshed by alloc_frame_buffers
     bool use_noise = false, stats = false, timings = false;
-    // traversal tuning (lpt_renderer_set_option, for experiments)
-    int refill = 44;
     int sort_queues = 0;       // k_shade emits both ray queues ordered by direction octant within a block (lpt_renderer_set_sort_queues)
-    // k_shade grid, blocks per CU (LPT_EXP_SHADE_BLOCKS_PER_CU); 0 = by the submission: 4 (what is resident at 4 waves / SIMD; 8: a 1/8 shard 1.89 instead of 1.80 ms) for a
-    // wavefront that has the chip to itself, 3 for the pieces of a cut batch — three 128-VGPR shading waves leave a SIMD room for one 72-VGPR k_trace wave of the piece on the
-    // other lane: the kernel alone is 10 % slower (2.75 -> 3.05 ms per frame), the frame 0.5 % faster (11.27-11.29 -> 11.19-11.24; profiles/r06_experiments_ab.txt O)
-    uint32_t shade_blocks_per_cu = 0;
-    uint32_t trace_waves_per_cu = 0;  // 0 = sized from the frame's ray count (below); LPT_EXP_TRACE_WAVES_PER_CU pins it
     // the pieces of a cut batch against each other (LPT_EXP_LANE_PHASE; flush_pending): 0 free, 1 offset start, 2 alternating traversal.  1: the bench frame
     // 10.44-10.47 ms against 10.52-10.53 free; 2: 11.87 (one traversal grid at a time gives up more than the shading beside it wins; profiles/r08_lane_phase_ab.txt)
     uint32_t lane_phase = 1;
@@ -274,17 +257,8 @@ struct lpt_renderer {
     hipEvent_t xevent = nullptr;
     bool xevent_recorded = false;
     Totals *totals = nullptr;
-    // per-bounce traversal launches: a ray that is not finished after this many steps is handed to k_trace_coop (a whole wave per ray); 0 = off.
-    // Applies to wavefronts of at most `budget_rays` rays: where a launch's longest ray sets its duration
-    uint32_t step_budget = kStepBudget, budget_rays = kBudgetRays;
-    bool budget_split = false;     // the budget also for the pieces of a cut batch (LPT_EXP_BUDGET_SPLIT)
-    // the same launches' tails finished IN PLACE instead (kernels.h tail_park / tail_walk): a wave whose queues are dry and that is down to this many live rays finishes them
-    // cooperatively from where they stand (default); 0: off (then the step budget + k_trace_coop pair applies).  LPT_OPT_TAIL_LANES
-    uint32_t coop_rays = kCoopRays;   // LPT_OPT_COOP_RAYS
-    uint32_t tail_lanes = 4u;      // 1/8 shard of the bench frame: 3, 4, 5 the same (2.74 ms per frame against 2.90 with the budget pair), 2 and 8 slower
     uint64_t split_rays = kSplitRays;   // LPT_EXP_SPLIT_RAYS
     uint32_t *err_host = nullptr, *err_dev = nullptr;   // the device's error word: one page-locked host word the kernels write (a bounded wait that ran out), checked behind every blocking call
-    bool packet_quads = true;      // a packet of bounce 0 = the four samples of a 4x4-pixel quarter (where the queue order allows it) instead of one sample of an 8x8 patch (LPT_EXP_PACKET_QUADS)
     uint32_t *occ_table = nullptr;   // occluder-cache probe (stats only): kOccEntries leaf slots + 1, zero = empty; allocated by enable_stats
     float occ_cell = 0.25f;          // its grid cell (scene units); LPT_EXP_OCC_CELL_MILLI
     void *default_probe = nullptr;
@@ -1781,55 +1755,48 @@ int lpt_renderer_set_sort_queues(lpt_renderer *r, int flag) {
 }
 // Launch tuning that experiments and the variant tests switch (the reference has no counterpart: SURVEY §5 "Config / flags: no").
 // Every value gives the same frame bit for bit; only which kernels run, and how large their grids are, changes.
+// One row per option: how it is read and stored, its range, and what a value outside does — clamped to the range, or (a row with a message) rejected.
+struct OptionRow { int id; uint64_t (*get)(const lpt_renderer *); void (*set)(lpt_renderer *, uint64_t); uint64_t min, max; const char *reject; };
+#define OPT_FIELD(F) [](const lpt_renderer *r) -> uint64_t { return (uint64_t)r->F; }, [](lpt_renderer *r, uint64_t v) { r->F = (decltype(r->F))v; }
+static const OptionRow kOptions[] = {
+    {LPT_OPT_PACKET_PRIMARY, OPT_FIELD(tune.packet_primary), 0u, 2u, "LPT_OPT_PACKET_PRIMARY: 0 (never), 1 (always), 2 (by pixel footprint)"},
+    {LPT_OPT_EXPERIMENT(LPT_EXP_PIPE_RAYS), OPT_FIELD(tune.pipe_rays), 0u, 0x7FFFFFFFu, nullptr},
+    {LPT_OPT_WAVEFRONT_RAYS, OPT_FIELD(wavefront_rays), 64u, UINT64_MAX, nullptr},
+    {LPT_OPT_EXPERIMENT(LPT_EXP_REFILL), OPT_FIELD(tune.refill), 0u, 63u, "LPT_EXP_REFILL: 0..63"},
+    {LPT_OPT_EXPERIMENT(LPT_EXP_TRACE_WAVES_PER_CU), OPT_FIELD(tune.trace_waves_per_cu), 0u, 32u, "LPT_EXP_TRACE_WAVES_PER_CU: 0 (auto) or 1..32"},
+    {LPT_OPT_EXPERIMENT(LPT_EXP_SHADE_BLOCKS_PER_CU), OPT_FIELD(tune.shade_blocks_per_cu), 0u, 64u, "LPT_EXP_SHADE_BLOCKS_PER_CU: 0 (by the submission) or 1..64"},
+    {LPT_OPT_PATH_RAYS, OPT_FIELD(tune.path_rays), 0u, 0x7FFFFFFFu, nullptr},
+    {LPT_OPT_EXPERIMENT(LPT_EXP_PATH_WAVES_PER_CU), OPT_FIELD(tune.path_waves_per_cu), 1u, 32u, "LPT_EXP_PATH_WAVES_PER_CU: 1..32"},
+    {LPT_OPT_EXPERIMENT(LPT_EXP_PATH_REFILL), OPT_FIELD(tune.path_refill), 0u, 63u, "LPT_EXP_PATH_REFILL: 0..63"},
+    {LPT_OPT_EXPERIMENT(LPT_EXP_OCC_CELL_MILLI), [](const lpt_renderer *r) { return (uint64_t)(r->occ_cell * 1000.0f + 0.5f); }, [](lpt_renderer *r, uint64_t v) { r->occ_cell = (float)v * 1.0e-3f; }, 0u, 1000000u, nullptr},
+    {LPT_OPT_EXPERIMENT(LPT_EXP_STEP_BUDGET), OPT_FIELD(tune.step_budget), 0u, 1u << 20, nullptr},
+    {LPT_OPT_EXPERIMENT(LPT_EXP_BUDGET_RAYS), OPT_FIELD(tune.budget_rays), 0u, 0x7FFFFFFFu, nullptr},
+    {LPT_OPT_EXPERIMENT(LPT_EXP_PACKET_QUADS), OPT_FIELD(tune.packet_quads), 0u, 1u, nullptr},
+    {LPT_OPT_EXPERIMENT(LPT_EXP_SPLIT_RAYS), OPT_FIELD(split_rays), 0u, UINT64_MAX, nullptr},
+    {LPT_OPT_EXPERIMENT(LPT_EXP_BUDGET_SPLIT), OPT_FIELD(tune.budget_split), 0u, 1u, nullptr},
+    {LPT_OPT_EXPERIMENT(LPT_EXP_LANE_PHASE), OPT_FIELD(lane_phase), 0u, 2u, "LPT_EXP_LANE_PHASE: 0 (free), 1 (offset start), 2 (alternating traversal)"},
+    {LPT_OPT_TAIL_LANES, OPT_FIELD(tune.tail_lanes), 0u, kTailMax, nullptr},
+    {LPT_OPT_COOP_RAYS, OPT_FIELD(tune.coop_rays), 0u, 0x7FFFFFFFu, nullptr},
+};
+#undef OPT_FIELD
+static const OptionRow *find_option(int option) {
+    for (const OptionRow &o : kOptions) if (o.id == option) return &o;
+    return nullptr;
+}
 int lpt_renderer_set_option(lpt_renderer *r, int option, uint64_t value) {
     if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_option: null");
     FLUSH_OR_RETURN(r);
-    switch (option) {
-    case LPT_OPT_PACKET_PRIMARY: if (value > 2u) return fail(LPT_ERR_INVALID_ARG, "LPT_OPT_PACKET_PRIMARY: 0 (never), 1 (always), 2 (by pixel footprint)"); r->packet_primary = (uint32_t)value; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_PIPE_RAYS): r->pipe_rays = (uint32_t)std::min<uint64_t>(value, 0x7FFFFFFFu); break;
-    case LPT_OPT_WAVEFRONT_RAYS: r->wavefront_rays = std::max<uint64_t>(value, 64u); break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_REFILL): if (value > 63u) return fail(LPT_ERR_INVALID_ARG, "LPT_EXP_REFILL: 0..63"); r->refill = (int)value; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_TRACE_WAVES_PER_CU): if (value > 32u) return fail(LPT_ERR_INVALID_ARG, "LPT_EXP_TRACE_WAVES_PER_CU: 0 (auto) or 1..32"); r->trace_waves_per_cu = (uint32_t)value; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_SHADE_BLOCKS_PER_CU): if (value > 64u) return fail(LPT_ERR_INVALID_ARG, "LPT_EXP_SHADE_BLOCKS_PER_CU: 0 (by the submission) or 1..64"); r->shade_blocks_per_cu = (uint32_t)value; break;
-    case LPT_OPT_PATH_RAYS: r->path_rays = (uint32_t)std::min<uint64_t>(value, 0x7FFFFFFFu); break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_PATH_WAVES_PER_CU): if (value < 1u || value > 32u) return fail(LPT_ERR_INVALID_ARG, "LPT_EXP_PATH_WAVES_PER_CU: 1..32"); r->path_waves_per_cu = (uint32_t)value; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_PATH_REFILL): if (value > 63u) return fail(LPT_ERR_INVALID_ARG, "LPT_EXP_PATH_REFILL: 0..63"); r->path_refill = (int)value; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_OCC_CELL_MILLI): r->occ_cell = (float)std::min<uint64_t>(value, 1000000u) * 1.0e-3f; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_STEP_BUDGET): r->step_budget = (uint32_t)std::min<uint64_t>(value, 1u << 20); break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_BUDGET_RAYS): r->budget_rays = (uint32_t)std::min<uint64_t>(value, 0x7FFFFFFFu); break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_PACKET_QUADS): r->packet_quads = value != 0; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_SPLIT_RAYS): r->split_rays = value; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_BUDGET_SPLIT): r->budget_split = value != 0; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_LANE_PHASE): if (value > 2u) return fail(LPT_ERR_INVALID_ARG, "LPT_EXP_LANE_PHASE: 0 (free), 1 (offset start), 2 (alternating traversal)"); r->lane_phase = (uint32_t)value; break;
-    case LPT_OPT_TAIL_LANES: r->tail_lanes = (uint32_t)std::min<uint64_t>(value, kTailMax); break;
-    case LPT_OPT_COOP_RAYS: r->coop_rays = (uint32_t)std::min<uint64_t>(value, 0x7FFFFFFFu); break;
-    default: return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_option: unknown option %d", option);
-    }
+    const OptionRow *o = find_option(option);
+    if (!o) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_option: unknown option %d", option);
+    if (o->reject && (value < o->min || value > o->max)) return fail(LPT_ERR_INVALID_ARG, "%s", o->reject);
+    o->set(r, std::min(std::max(value, o->min), o->max));
     return LPT_OK;
 }
 int lpt_renderer_get_option(const lpt_renderer *r, int option, uint64_t *value) {
     if (!r || !value) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_get_option: null");
-    switch (option) {
-    case LPT_OPT_PACKET_PRIMARY: *value = r->packet_primary; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_PIPE_RAYS): *value = r->pipe_rays; break;
-    case LPT_OPT_WAVEFRONT_RAYS: *value = r->wavefront_rays; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_REFILL): *value = (uint64_t)r->refill; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_TRACE_WAVES_PER_CU): *value = r->trace_waves_per_cu; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_SHADE_BLOCKS_PER_CU): *value = r->shade_blocks_per_cu; break;
-    case LPT_OPT_PATH_RAYS: *value = r->path_rays; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_PATH_WAVES_PER_CU): *value = r->path_waves_per_cu; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_PATH_REFILL): *value = (uint64_t)r->path_refill; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_OCC_CELL_MILLI): *value = (uint64_t)(r->occ_cell * 1000.0f + 0.5f); break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_STEP_BUDGET): *value = r->step_budget; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_BUDGET_RAYS): *value = r->budget_rays; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_PACKET_QUADS): *value = r->packet_quads; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_SPLIT_RAYS): *value = r->split_rays; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_BUDGET_SPLIT): *value = r->budget_split; break;
-    case LPT_OPT_EXPERIMENT(LPT_EXP_LANE_PHASE): *value = r->lane_phase; break;
-    case LPT_OPT_TAIL_LANES: *value = r->tail_lanes; break;
-    case LPT_OPT_COOP_RAYS: *value = r->coop_rays; break;
-    default: return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_get_option: unknown option %d", option);
-    }
+    const OptionRow *o = find_option(option);
+    if (!o) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_get_option: unknown option %d", option);
+    *value = o->get(r);
     return LPT_OK;
 }
 int lpt_renderer_enable_stats(lpt_renderer *r, int flag) {
@@ -1923,6 +1890,29 @@ static void launch_filter(lpt_renderer *r, hipStream_t s) {
         result = r->den_temp;
     }
     hipLaunchKernelGGL(k_composite, dim3(px_blocks), dim3(kBlock), 0, s, r->den_gbuf[cur], result, r->accum, npx);
+}
+
+// Runtime flags as template arguments: calls f(std::bool_constant<flag>{}...), so every combination of the flags is instantiated.  For kernels whose
+// instantiations are a full cross product (k_shade, k_path); NOT for k_trace, which exists in eight of its sixteen forms (launch_plan.h TraceVariant).
+template <class F> static void with_flags(F &&f) { f(); }
+template <class F, class... Rest> static void with_flags(F &&f, bool flag, Rest... rest) {
+    if (flag) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+// k_trace<STATS, PIPE, TAIL, MASK>: the eight instantiations that exist, by name (launch_plan.h picks one)
+static void launch_k_trace(TraceVariant v, uint32_t blocks, size_t lds, hipStream_t s, const TraceKernargs &ka) {
+    const dim3 grid(blocks), block(kTraceBlock);
+    switch (v) {
+    case TraceVariant::Lane:      hipLaunchKernelGGL((k_trace<false, false>), grid, block, lds, s, ka); break;
+    case TraceVariant::Pipe:      hipLaunchKernelGGL((k_trace<false, true>), grid, block, lds, s, ka); break;
+    case TraceVariant::Stats:     hipLaunchKernelGGL((k_trace<true, false>), grid, block, lds, s, ka); break;
+    case TraceVariant::StatsPipe: hipLaunchKernelGGL((k_trace<true, true>), grid, block, lds, s, ka); break;
+    case TraceVariant::Tail:      hipLaunchKernelGGL((k_trace<false, false, true>), grid, block, lds, s, ka); break;
+    case TraceVariant::PipeTail:  hipLaunchKernelGGL((k_trace<false, true, true>), grid, block, lds, s, ka); break;
+    case TraceVariant::Mask:      hipLaunchKernelGGL((k_trace<false, false, false, true>), grid, block, lds, s, ka); break;
+    case TraceVariant::StatsMask: hipLaunchKernelGGL((k_trace<true, false, false, true>), grid, block, lds, s, ka); break;
+    }
 }
 
 extern "C" {
@@ -2027,102 +2017,51 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
     }
 
     DProbe probe = r->probe ? r->probe->d : DProbe{(const uint8_t *)r->default_probe, 1u, 1u};
-    // SPEC §18: the ENV kernels while the mode is on and the bound probe has a distribution; otherwise exactly the default launches
-    bool env = false;
+    bool env = false;   // SPEC §18: the ENV kernels while the mode is on and the bound probe has a distribution
     if (r->env_sampling && r->probe) TRY(probe_env(const_cast<lpt_probe *>(r->probe), env));
     const DEnv ev = env ? r->probe->env : DEnv{};
     DNoise nz{(const uint8_t *)r->noise, r->noise_w, r->noise_h, (r->use_noise && r->noise) ? 1u : 0u};
     const DScene &sc = r->sg->d;
-    const bool punct = sc.n_punctual != 0u;   // SPEC §19: the PUNCT kernels while the bound scene has punctual lights; otherwise exactly the default launches
-    // SPEC §20: a scene with alpha-masked materials traces on the plain per-lane step alone (k_trace<STATS, false, false, /*MASK*/true>), whatever the options say — the
-    // only acceptance site that asks the mask.  No packets, no cooperative walks, no path kernel, no tail, no step budget, no occluder probe: each of them accepts hits
-    // on its own.  Otherwise exactly the default launches
-    const bool masked = sc.n_alpha != 0u;
-    // SPEC §21: a scene with a transmissive material in use shades with k_shade<..., TRANS> on the per-bounce launches and stays off the path kernel, whose
-    // instantiations therefore do not double.  The traversal — packets, tail, cooperative walks — sees glass as geometry.  Otherwise exactly the default launches
-    const bool trans = sc.n_trans != 0u;
     if (r->timings) { r->ring_pos++; harvest_slot(r, cur_slot(r)); }
 
     tk.stages = 0; tk.run = nullptr;
     if (p.n_slots) {
-        const uint32_t cus = (uint32_t)r->dev->compute_units;
-        const uint32_t stream_blocks = std::min<uint32_t>(div_up(n_rays, kBlock), cus * 8u);
-        const uint32_t shade_blocks = std::min<uint32_t>(div_up(n_rays, kBlock), cus * (r->shade_blocks_per_cu ? r->shade_blocks_per_cu : (solo ? 4u : 3u)));
-        // the one-round-trip step (kernels.h ray_step_pipe): 72 VGPRs (round 6; 78 before), 6 waves per SIMD used of the 7 that fit, ~3 % more nodes and ~12 % more
-        // triangles fetched per ray — and still 1 % less time per frame at 8 M rays, 2 % for a 1 M-ray tile shard
-        // (profiles/r03_experiments_ab.txt); LPT_EXP_PIPE_RAYS 0 selects the two-round-trip step
-        const bool pipe = !masked && n_rays <= r->pipe_rays;
-        // persistent waves: about 2.5 primary rays per lane, between 8 waves per CU and all that fit (24 = 6 per SIMD with the one-round-trip step — 28 measured no faster, round 6 —, 32 with the other).  A 1/8
-        // tile shard (1 M rays per launch) is best at 24 either way (round 3, span form, two-round-trip step: 8 / 12 / 16 / 24 / 32
-        // waves per CU -> 4.41 / 3.89 / 3.62 / 3.51 / 3.54 ms per frame)
-        uint32_t waves = r->trace_waves_per_cu ? cus * r->trace_waves_per_cu : std::min(std::max(n_rays / 160u, cus * 8u), cus * (pipe ? 24u : 32u));
-        waves = std::max(8u, waves & ~7u);  // whole groups of 8: one chunk head per XCD
-        const uint32_t trace_blocks = std::min<uint32_t>(div_up(n_rays, kTraceBlock), waves);
-        const size_t lds = stack_bytes(sc);
-        const bool dense = (r->w % r->tile_w == 0u) && (r->h % r->tile_h == 0u);
-
-        // Bounce 0 by packet traversal (one tree walk per 8x8-pixel patch) pays while the patch is narrow: at 1920x1080 a packet enters 17.9 nodes
-        // for rays that need 14.9 each, and the walk runs at 11.5 Grays/s against 6.2 per ray; at 240x135 the same patch spans eight times the
-        // angle, the walk visits several times the nodes, and the packet launch is a third of the frame (0.43 of 1.37 ms; 0.39 ms at 480x270,
-        // where the per-ray launch needs 0.13).  LPT_OPT_PACKET_PRIMARY 2 (default): packets up to 1.8 mrad per pixel; 1: always; 0: never.
-        const float pixel_rad = 2.0f * th / (float)std::max(r->h, 1u);
-        const bool packet = !masked && (r->packet_primary == 1u || (r->packet_primary == 2u && pixel_rad <= kPacketMaxPixelRad));
-        tk.packet = packet;
-        // Traversal launches: closest-hit rays of bounce b+1 and shadow rays of bounce b, both produced by shade(b), are traced by
-        // ONE persistent launch (k_trace) — nb+1 traversal launches per frame instead of 2*nb.
-        // the occluder-cache probe rides with the stats kernels only (kernels.h OccProbe); its table belongs to the renderer
-        OccProbe occ{nullptr, 0u, 0.0f};
-        if (!masked && r->stats && r->occ_table && r->occ_cell > 0.0f) occ = OccProbe{r->occ_table, kOccEntries - 1u, 1.0f / r->occ_cell};
-        // the step budget pays where nothing else fills the tail of a launch: a submission that is ONE wavefront (a tile shard, a small frame).  The
-        // pieces of a cut batch overlap on the renderer's lanes and hide each other's tails: 1/2 shard as two wavefronts 6.84 ms without, 6.93 with it
-        // (not with the stats kernels: a ray dropped at the budget would be missing from the steps-per-ray histogram and its partial node / triangle counts would be
-        // counted again by the cooperative kernel's full re-trace — ADVICE r04)
-        const bool tail_launch = !masked && !r->stats && (solo || r->budget_split) && n_rays <= r->budget_rays;
-        // ... the tail finished in place (tail_walk) comes first where it is on: nothing is dropped then, so there is nothing to re-trace
-        const uint32_t tail = tail_launch ? std::min(std::min(r->tail_lanes, kTailMax), (uint32_t)std::max(r->refill, 0)) : 0u;
-        const uint32_t budget = (tail_launch && !tail && r->step_budget) ? r->step_budget : 0u;
-        const size_t tail_lds = tail ? sizeof(uint32_t) * tail_lds_words(r->sg->stats.max_depth) : 0u;
-        // a TINY wavefront (fewer rays than the chip has wave slots): the per-bounce launches with EVERY ray traced by a whole wave (k_trace_coop over the queues) — a lane per
-        // ray leaves the chip empty and the frame is one chain of dependent steps (64x36, 4 spp: k_path 0.72 ms per frame, the per-lane launches 0.83, this 0.39)
-        const bool coop_all = !masked && !r->stats && r->coop_rays && n_rays <= r->coop_rays;
+        // what the launches depend on, and the decision (launch_plan.h: the rules are stated there)
+        WavefrontFacts f;
+        f.n_rays = n_rays; f.n_slots = p.n_slots; f.slot0 = p.slot0; f.n_samples = n_samples; f.cus = (uint32_t)r->dev->compute_units;
+        f.solo = solo; f.stats = r->stats; f.denoise = denoise; f.env = env;
+        f.masked = sc.n_alpha != 0u; f.trans = sc.n_trans != 0u; f.punct = sc.n_punctual != 0u; f.max_depth = r->sg->stats.max_depth; f.stack_entries = sc.stack_entries;
+        f.pixel_rad = 2.0f * th / (float)std::max(r->h, 1u); f.dense = (r->w % r->tile_w == 0u) && (r->h % r->tile_h == 0u); f.block8 = p.block8 != 0u;
+        f.lim = KernelLimits{kBlock, kTraceBlock, kTailMax, kCoopWavesPerCu, kPacketBlocksPerCu, kPacketMaxPixelRad};
+        const LaunchTuning tune = r->tune;
+        const LaunchPlan pl = plan_wavefront(tune, f);
+        tk.packet = pl.packet;
+        OccProbe occ{nullptr, 0u, 0.0f};   // its table belongs to the renderer
+        if (pl.occ_probe && r->occ_table && r->occ_cell > 0.0f) occ = OccProbe{r->occ_table, kOccEntries - 1u, 1.0f / r->occ_cell};
+        const size_t trace_lds = pl.stack_lds + (pl.tail ? sizeof(uint32_t) * tail_lds_words(f.max_depth) : 0u) + (pl.stats_lds_pad ? 64u : 0u);
+        const size_t coop_lds = sizeof(uint32_t) * coop_stack_entries(kCoopStack, f.max_depth);
+        const int sort_queues = r->sort_queues;
         // The launches in stages, so that the pieces of a cut batch can be enqueued stage by stage across the lanes (flush_pending,
         // LPT_EXP_LANE_PHASE): stage 0 = counters, ray generation and the primary rays (with the path kernel: the whole wavefront),
         // stage b + 1 = shade(b) and the traversal launch behind it.  `ph` orders the stage against the other lanes' (stream events only).
         // The closure holds copies of what the launches read; `r`'s buffers and the scene do not change before the submission is enqueued.
-        const bool path = !masked && !trans && r->path_rays && n_rays <= r->path_rays && !coop_all;   // the primary hits are there, whichever kernel found them
         const int slot = cur_slot(r);
         Wavefront *w = &wf;
         tk.stages = nb + 1u;
         tk.run = [=](uint32_t t, const PhaseHooks &ph) -> int {
             if (ph.wait_start) HIP_TRY(hipStreamWaitEvent(s, ph.wait_start, 0));
+            // Traversal launches: closest-hit rays of bounce b+1 and shadow rays of bounce b, both produced by shade(b), are traced by
+            // ONE persistent launch (k_trace) — nb+1 traversal launches per frame instead of 2*nb.
             auto trace = [&](int cb, int sb) {
                 stage_begin(r, cb >= 0 ? ST_INTERSECT : ST_SHADOW, s, slot);  // :457-464, :493-498
                 const Queue qin = w->q[(uint32_t)(cb < 0 ? 0 : cb) & 1u];
                 const int launch_no = cb >= 0 ? cb : (int)nb;   // which strag_count[] this launch fills
-                if (coop_all) {
-                    const size_t clds = sizeof(uint32_t) * coop_stack_entries(kCoopStack, r->sg->stats.max_depth);
-                    hipLaunchKernelGGL(k_trace_coop<false>, dim3(std::min(2u * n_rays, cus * kCoopWavesPerCu)), dim3(kTraceBlock), clds, s, sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, (const uint32_t *)nullptr, launch_no);
-                    stage_end(r, s, slot);
-                    return;
-                }
-                if (masked) {   // SPEC §20 (tail, budget = 0 and no probe table by the decisions above)
-                    if (r->stats) hipLaunchKernelGGL((k_trace<true, false, false, true>), dim3(trace_blocks), dim3(kTraceBlock), lds + 64u, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, 0u, w->strag, launch_no, 0u});
-                    else hipLaunchKernelGGL((k_trace<false, false, false, true>), dim3(trace_blocks), dim3(kTraceBlock), lds, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, 0u, w->strag, launch_no, 0u});
-                    stage_end(r, s, slot);
-                    return;
-                }
-                if (tail) {
-                    if (pipe) hipLaunchKernelGGL((k_trace<false, true, true>), dim3(trace_blocks), dim3(kTraceBlock), lds + tail_lds, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, 0u, w->strag, launch_no, tail});
-                    else hipLaunchKernelGGL((k_trace<false, false, true>), dim3(trace_blocks), dim3(kTraceBlock), lds + tail_lds, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, 0u, w->strag, launch_no, tail});
-                } else if (pipe) {
-                    if (r->stats) hipLaunchKernelGGL((k_trace<true, true>), dim3(trace_blocks), dim3(kTraceBlock), lds + 64u, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, budget, w->strag, launch_no, 0u});
-                    else hipLaunchKernelGGL((k_trace<false, true>), dim3(trace_blocks), dim3(kTraceBlock), lds, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, budget, w->strag, launch_no, 0u});
-                } else if (r->stats) hipLaunchKernelGGL((k_trace<true, false>), dim3(trace_blocks), dim3(kTraceBlock), lds + 64u, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, budget, w->strag, launch_no, 0u});
-                else hipLaunchKernelGGL((k_trace<false, false>), dim3(trace_blocks), dim3(kTraceBlock), lds, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, r->refill, occ, budget, w->strag, launch_no, 0u});
-                if (budget) {   // the launch's stragglers, a whole wave each (most waves of this grid find none and leave at once)
-                    const size_t clds = sizeof(uint32_t) * coop_stack_entries(kCoopStack, r->sg->stats.max_depth);
-                    if (r->stats) hipLaunchKernelGGL(k_trace_coop<true>, dim3(cus * kCoopWavesPerCu), dim3(kTraceBlock), clds, s, sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, w->strag, launch_no);
-                    else hipLaunchKernelGGL(k_trace_coop<false>, dim3(cus * kCoopWavesPerCu), dim3(kTraceBlock), clds, s, sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, w->strag, launch_no);
+                // every ray of both queues (coop-all), or the stragglers a budgeted launch left in w->strag: a whole wave each
+                auto coop = [&](const uint32_t *strag) { with_flags([&](auto S) { hipLaunchKernelGGL(k_trace_coop<decltype(S)::value>, dim3(pl.coop_blocks), dim3(kTraceBlock), coop_lds, s, sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, strag, launch_no); }, f.stats); };
+                if (pl.coop_all) coop(nullptr);
+                else {
+                    launch_k_trace(pl.variant, pl.trace_blocks, trace_lds, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, tune.refill, occ, pl.budget, w->strag, launch_no, pl.tail});
+                    if (pl.budget) coop(w->strag);
                 }
                 stage_end(r, s, slot);
             };
@@ -2130,60 +2069,37 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
                 HIP_TRY(hipMemsetAsync(w->ctr, 0, sizeof(FrameCounters), s));
                 // "ray generation" (:444-448)
                 stage_begin(r, ST_RAYGEN, s, slot);
-                if (dense) {
-                    hipLaunchKernelGGL(k_raygen<true>, dim3(stream_blocks), dim3(kBlock), 0, s, p, nz, w->q[0], w->Lsum, w->ctr);
-                } else {
-                    hipLaunchKernelGGL(k_raygen<false>, dim3(stream_blocks), dim3(kBlock), 0, s, p, nz, w->q[0], w->Lsum, w->ctr);
-                }
+                with_flags([&](auto D) { hipLaunchKernelGGL(k_raygen<decltype(D)::value>, dim3(pl.stream_blocks), dim3(kBlock), 0, s, p, nz, w->q[0], w->Lsum, w->ctr); }, f.dense);
                 stage_end(r, s, slot);
                 if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
-                if (packet) {
+                if (pl.packet) {
                     // the primary rays: 64 consecutive queue entries are an 8x8-pixel patch of one sample — packet traversal (k_trace_packet)
                     stage_begin(r, ST_PRIMARY, s, slot);
-                    const uint32_t packets = div_up(n_rays, 64u);
-                    const size_t plds = (size_t)(48u + 7u * r->sg->stats.max_depth + 8u) * sizeof(uint32_t);   // 48 planes + the stack
-                    // 4 samples of a 4x4-pixel quarter per packet instead of one sample of an 8x8 patch, where the queue order allows it: a dense frame
-                    // (queue index = sample * slots + slot), 8x8 pixel blocks inside the tiles, whole blocks, a multiple of four samples
-                    const uint32_t quad_slots = (r->packet_quads && dense && p.block8 && p.n_slots % 64u == 0u && p.slot0 % 64u == 0u && n_samples % 4u == 0u) ? p.n_slots : 0u;
-                    if (r->stats) hipLaunchKernelGGL(k_trace_packet<true>, dim3(std::min(packets, cus * kPacketBlocksPerCu)), dim3(kTraceBlock), plds, s, sc, w->q[0], w->hits, w->ctr, 0, quad_slots);
-                    else hipLaunchKernelGGL(k_trace_packet<false>, dim3(std::min(packets, cus * kPacketBlocksPerCu)), dim3(kTraceBlock), plds, s, sc, w->q[0], w->hits, w->ctr, 0, quad_slots);
+                    with_flags([&](auto S) { hipLaunchKernelGGL(k_trace_packet<decltype(S)::value>, dim3(pl.packet_blocks), dim3(kTraceBlock), pl.packet_lds, s, sc, w->q[0], w->hits, w->ctr, 0, pl.quad_slots); }, f.stats);
                     stage_end(r, s, slot);
-                } else if (coop_all || !path) trace(0, -1);   // a path-kernel wavefront traces its primary rays itself
-                // A small wavefront (the tile shard of a multi-GPU frame): every bounce behind the primary hits in ONE persistent launch — the
-                // passes of renderer.rs:484-509 without a chip-wide barrier between them (kernels.h k_path); same frame, same counters
-                if (path) {
+                } else if (pl.coop_all || !pl.path) trace(0, -1);   // a path-kernel wavefront traces its primary rays itself
+                // every bounce behind the primary hits in ONE persistent launch — the passes of renderer.rs:484-509 without a chip-wide barrier between them (kernels.h k_path); same frame, same counters
+                if (pl.path) {
                     stage_begin(r, ST_PATH, s, slot);
-                    const uint32_t pblocks = std::min<uint32_t>(div_up(n_rays, kTraceBlock), std::max(8u, (cus * r->path_waves_per_cu) & ~7u));
-                    const size_t plds = lds + kPathLdsExtra;   // stacks + sRGB table + per-bounce counters
-                    // the instantiation: G-buffer x stats x ENV (SPEC §18) x PUNCT (SPEC §19: the bound scene has punctual lights); without the last two, the kernels of every frame before them
-                    auto launch_path = [&](auto G, auto S, auto P) {
-                        constexpr bool g = decltype(G)::value, st = decltype(S)::value, pu = decltype(P)::value;
-                        const float4 *h0 = packet ? w->hits : (const float4 *)nullptr;
-                        if (env) hipLaunchKernelGGL((k_path<g, st, true, pu, DEnv>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], h0, w->Lsum, w->ctr, seed0, gb, r->path_refill, ev);
-                        else hipLaunchKernelGGL((k_path<g, st, false, pu>), dim3(pblocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], h0, w->Lsum, w->ctr, seed0, gb, r->path_refill);
-                    };
-                    auto path_gs = [&](auto P) {
-                        if (denoise) { if (r->stats) launch_path(std::true_type{}, std::true_type{}, P); else launch_path(std::true_type{}, std::false_type{}, P); }
-                        else if (r->stats) launch_path(std::false_type{}, std::true_type{}, P);
-                        else launch_path(std::false_type{}, std::false_type{}, P);
-                    };
-                    if (punct) path_gs(std::true_type{}); else path_gs(std::false_type{});
+                    const size_t plds = pl.stack_lds + kPathLdsExtra;   // stacks + sRGB table + per-bounce counters
+                    const float4 *h0 = pl.packet ? w->hits : (const float4 *)nullptr;
+                    // the instantiation: G-buffer x stats x PUNCT (SPEC §19) x ENV (SPEC §18: `e` is the probe's distribution, or nothing)
+                    with_flags([&](auto G, auto S, auto P) {
+                        auto launch = [&](auto... e) { hipLaunchKernelGGL((k_path<decltype(G)::value, decltype(S)::value, sizeof...(e) != 0, decltype(P)::value, decltype(e)...>), dim3(pl.path_blocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], h0, w->Lsum, w->ctr, seed0, gb, tune.path_refill, e...); };
+                        if (f.env) launch(ev); else launch();
+                    }, f.denoise, f.stats, f.punct);
                     stage_end(r, s, slot);
                 }
-            } else if (!path) {
+            } else if (!pl.path) {
                 const uint32_t b = t - 1u;
                 const uint32_t seed = seed0 + t;     // += 1 per bounce (:453, :487)
                 const Queue qin = w->q[b & 1u], qout = w->q[(b + 1u) & 1u];
                 stage_begin(r, ST_SHADE, s, slot);            // :471-480, :502-508
-                auto launch_shade_t = [&](auto G, auto P, auto Tr) {   // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); ENV / PUNCT as for k_path; TRANS: SPEC §21
-                    constexpr bool g = decltype(G)::value, pu = decltype(P)::value, tr = decltype(Tr)::value;
-                    if (env) hipLaunchKernelGGL((k_shade<g, true, pu, tr, DEnv>), dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues, ev);
-                    else hipLaunchKernelGGL((k_shade<g, false, pu, tr>), dim3(shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, r->sort_queues);
-                };
-                auto launch_shade = [&](auto G, auto P) { if (trans) launch_shade_t(G, P, std::true_type{}); else launch_shade_t(G, P, std::false_type{}); };
-                if (denoise && b == 0u) { if (punct) launch_shade(std::true_type{}, std::true_type{}); else launch_shade(std::true_type{}, std::false_type{}); }
-                else if (punct) launch_shade(std::false_type{}, std::true_type{});
-                else launch_shade(std::false_type{}, std::false_type{});
+                // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); PUNCT / ENV as for k_path; TRANS: SPEC §21
+                with_flags([&](auto G, auto P, auto Tr) {
+                    auto launch = [&](auto... e) { hipLaunchKernelGGL((k_shade<decltype(G)::value, sizeof...(e) != 0, decltype(P)::value, decltype(Tr)::value, decltype(e)...>), dim3(pl.shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, sort_queues, e...); };
+                    if (f.env) launch(ev); else launch();
+                }, f.denoise && b == 0u, f.punct, f.trans);
                 stage_end(r, s, slot);
                 if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
                 trace(b + 1u < nb ? (int)(b + 1u) : -1, (int)b);
