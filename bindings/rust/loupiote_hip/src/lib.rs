@@ -133,6 +133,16 @@ impl Scene {
         check(unsafe { ffi::lpt_scene_get_material_transmission(self.h, material, &mut factor, &mut ior, &mut thin) })?;
         Ok((factor, ior, thin != 0))
     }
+    /// SPEC.md §22: emissive materials; `Le = factor x strength` per channel, times the sRGB emissive `image` where one is given; a product of 0: non-emissive again
+    pub fn set_material_emission(&mut self, material: u32, factor: [f32; 3], strength: f32, image: Option<u32>) -> Result<(), Error> {
+        check(unsafe { ffi::lpt_scene_set_material_emission(self.h, material, factor.as_ptr(), strength, image.unwrap_or(ffi::LPT_INVALID_INDEX)) })
+    }
+    /// -> (Le, image)
+    pub fn material_emission(&self, material: u32) -> Result<([f32; 3], Option<u32>), Error> {
+        let (mut le, mut image) = ([0f32; 3], 0u32);
+        check(unsafe { ffi::lpt_scene_get_material_emission(self.h, material, le.as_mut_ptr(), &mut image) })?;
+        Ok((le, if image == ffi::LPT_INVALID_INDEX { None } else { Some(image) }))
+    }
     /// SPEC.md §19: a point / spot / directional light (KHR_lights_punctual); records from `punctual_light`
     pub fn add_punctual_light(&mut self, light: &ffi::lpt_punctual_light) -> Result<u32, Error> {
         let mut out = 0u32;

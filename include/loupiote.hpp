@@ -102,6 +102,16 @@ class Scene {  // scene.rs:30-54
         t.thin_walled = thin != 0;
         return t;
     }
+    // SPEC.md §22: emissive materials; Le = factor x strength per channel, times the sRGB emissive image where one is given; a product of 0: non-emissive again
+    struct MaterialEmission { float le[3]; uint32_t image; };
+    void set_material_emission(uint32_t material, const float factor[3], float strength = 1.0f, uint32_t image = LPT_INVALID_INDEX) {
+        check(lpt_scene_set_material_emission(h_, material, factor, strength, image));
+    }
+    MaterialEmission material_emission(uint32_t material) const {
+        MaterialEmission e{};
+        check(lpt_scene_get_material_emission(h_, material, e.le, &e.image));
+        return e;
+    }
     // SPEC.md §19: point / spot / directional lights (KHR_lights_punctual); records from point_light / spot_light / directional_light below
     uint32_t add_punctual_light(const lpt_punctual_light &l) { uint32_t id = 0; check(lpt_scene_add_punctual_light(h_, &l, &id)); return id; }
     void set_punctual_light(uint32_t i, const lpt_punctual_light &l) { check(lpt_scene_set_punctual_light(h_, i, &l)); }

@@ -281,6 +281,16 @@ int lpt_scene_get_material_alpha(const lpt_scene *scene, uint32_t material_index
 int lpt_scene_set_material_transmission(lpt_scene *scene, uint32_t material_index, float factor, float ior, uint32_t thin_walled);
 int lpt_scene_get_material_transmission(const lpt_scene *scene, uint32_t material_index, float *factor, float *ior, uint32_t *thin_walled);
 
+/* build-only extension (SPEC.md §22; the reference's loader reads no emissiveFactor): emissive materials.  A third side table beside
+ * the 32-byte lpt_material, non-emissive by default.  Le_c = factor[c] * strength (one float product per channel, made here); a path
+ * that hits a triangle of the material, from either side and on any bounce, picks up Le — times the sRGB-decoded rgb of `image` at the
+ * hit's texture coordinate when `image` is not LPT_INVALID_INDEX — with weight 1.  No light sample is drawn toward such triangles.
+ * Le = 0 in all channels returns the material to non-emissive and drops the record (the getter then reports no image).
+ * LPT_ERR_INVALID_ARG, and nothing changed, for a material index out of range, a negative or non-finite number or product, an image
+ * index out of range.  The getter returns Le (the products), not the factor and the strength; its out-pointers may be NULL. */
+int lpt_scene_set_material_emission(lpt_scene *scene, uint32_t material_index, const float factor[3], float strength, uint32_t image);
+int lpt_scene_get_material_emission(const lpt_scene *scene, uint32_t material_index, float le[3], uint32_t *image);
+
 /* Read-back of the flat arrays (the reference exposes them as pub Vec fields). */
 int lpt_scene_get_materials(const lpt_scene *s, uint32_t first, uint32_t count, lpt_material *dst);
 int lpt_scene_get_entries(const lpt_scene *s, uint32_t first, uint32_t count, lpt_blas_entry *dst);

@@ -101,6 +101,8 @@ SIGNATURES = {
     "lpt_scene_get_material_alpha": (_i, [_vp, _u32, _pu32, C.POINTER(_f), _pu32]),
     "lpt_scene_set_material_transmission": (_i, [_vp, _u32, _f, _f, _u32]),
     "lpt_scene_get_material_transmission": (_i, [_vp, _u32, C.POINTER(_f), C.POINTER(_f), _pu32]),
+    "lpt_scene_set_material_emission": (_i, [_vp, _u32, _vp, _f, _u32]),
+    "lpt_scene_get_material_emission": (_i, [_vp, _u32, _vp, _pu32]),
     "lpt_scene_get_materials": (_i, [_vp, _u32, _u32, _vp]),
     "lpt_scene_get_entries": (_i, [_vp, _u32, _u32, _vp]),
     "lpt_scene_get_vertices": (_i, [_vp, _u32, _u32, _vp]),

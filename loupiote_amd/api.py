@@ -242,6 +242,19 @@ class Scene:
         _check(A.lib().lpt_scene_get_material_transmission(self._h, int(material_index), C.byref(factor), C.byref(ior), C.byref(thin)))
         return float(factor.value), float(ior.value), bool(thin.value)
 
+    # SPEC §22: emissive materials; a third side table of the materials, non-emissive by default
+    def set_material_emission(self, material_index, factor, strength=1.0, image=None):
+        """a path that hits a triangle of the material, from either side and on any bounce, picks up Le = factor x strength (x the sRGB-decoded rgb of
+        `image` at the hit, if one is given) with weight 1; no light sample is drawn toward it.  A product of 0 in all channels: non-emissive again"""
+        f = np.ascontiguousarray(np.broadcast_to(np.asarray(factor, np.float32), (3,)))
+        _check(A.lib().lpt_scene_set_material_emission(self._h, int(material_index), A.ptr(f), float(strength), A.INVALID_INDEX if image is None else int(image)))
+
+    def material_emission(self, material_index):
+        """-> (Le: float32[3], the products factor x strength; image index or None)"""
+        le, image = np.zeros(3, np.float32), C.c_uint32()
+        _check(A.lib().lpt_scene_get_material_emission(self._h, int(material_index), A.ptr(le), C.byref(image)))
+        return le, (None if image.value == A.INVALID_INDEX else int(image.value))
+
     def _get(self, fn, dt, count):
         out = np.zeros(count, dt)
         _check(fn(self._h, 0, count, A.ptr(out)))

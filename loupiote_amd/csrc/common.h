@@ -37,6 +37,13 @@ struct MaterialTransmission {
     uint32_t thin_walled = 1u;
 };
 
+// SPEC §22: a material's emission, a third side table; Le = 0 in all channels = non-emissive (the default, and no record is kept)
+struct MaterialEmission {
+    float le[3] = {0.0f, 0.0f, 0.0f};       // float32(factor_c) * float32(strength), one binary32 product per channel
+    uint32_t image = LPT_INVALID_INDEX;     // the emissive image (sRGB), or none
+    bool emissive() const { return le[0] != 0.0f || le[1] != 0.0f || le[2] != 0.0f; }
+};
+
 }  // namespace lpt
 
 // The CPU-side scene: the flat arrays of the reference's Scene / BLASArray
@@ -54,6 +61,8 @@ struct lpt_scene {
     lpt::MaterialAlpha material_alpha(size_t i) const { return i < alpha.size() ? alpha[i] : lpt::MaterialAlpha(); }
     std::vector<lpt::MaterialTransmission> transmission;   // SPEC §21: side table of `materials`; a material beyond its end is opaque (material_transmission)
     lpt::MaterialTransmission material_transmission(size_t i) const { return i < transmission.size() ? transmission[i] : lpt::MaterialTransmission(); }
+    std::vector<lpt::MaterialEmission> emission;   // SPEC §22: side table of `materials`; a material beyond its end is non-emissive (material_emission)
+    lpt::MaterialEmission material_emission(size_t i) const { return i < emission.size() ? emission[i] : lpt::MaterialEmission(); }
 };
 
 namespace lpt {

@@ -149,6 +149,7 @@ struct lpt_scene_gpu {
     DevMem tri_verts, materials, lights, texels, images, srgb_lut, pair_texels, pair_images;
     DevMem punctual;                // SPEC §19: lpt_punctual_light records (DScene::punctual)
     DevMem trans_tri, trans_recs;   // SPEC §21: the per-triangle table and the records of the transmissive materials (DScene::trans_tri / trans_recs); empty without glass
+    DevMem emis_tri, emis_recs;     // SPEC §22: the per-triangle table and the records of the emissive materials (DScene::emis_tri / emis_recs); empty without emitters
     DevMem alpha_tri, alpha_recs;   // SPEC §20: the per-triangle table and the records of the masked materials (DScene::alpha_tri / alpha_recs); empty without masks
     TexturePairs pairs;
     lpt_accel_stats stats{};
@@ -658,6 +659,11 @@ static std::vector<uint64_t> pair_textures(const lpt_scene &scene, bool enable, 
         const MaterialAlpha a = scene.material_alpha(i);
         if (a.mode == LPT_ALPHA_MASK && a.image < scene.images.size()) { referenced[a.image] = 1; alone[a.image] = 1; }
     }
+    // SPEC §22: so does an emissive image — shade_hit<.., EMIS> looks it up on its own, whatever pair it is also half of
+    for (size_t i = 0; i < scene.materials.size(); ++i) {
+        const MaterialEmission e = scene.material_emission(i);
+        if (e.emissive() && e.image < scene.images.size()) { referenced[e.image] = 1; alone[e.image] = 1; }
+    }
     p.image_resident.assign(scene.images.size(), 1);
     for (size_t i = 0; i < scene.images.size(); ++i) p.image_resident[i] = (!referenced[i] || alone[i]) ? 1 : 0;
     return texels;
@@ -866,6 +872,49 @@ static int commit_trans(lpt_scene_gpu *sg, const TransTables &tt) {
     return LPT_OK;
 }
 
+// SPEC §22: the emission tables, derived and committed as the alpha tables are — one record {Le.r, Le.g, Le.b, bits of the plain image index} per emissive material
+// that an instance with triangles uses, one uint32 per baked triangle (keyed by prim id).  Both empty for a scene without an emitter in use, which then launches what it always launched.
+struct EmisTables { std::vector<float4> recs; std::vector<uint32_t> tri; };
+static int derive_emis(const lpt_scene_gpu *sg, const lpt_scene &scene, EmisTables &out) {
+    std::vector<uint32_t> rec_of(scene.materials.size(), 0u);   // 1 + record index
+    for (size_t i = 0; i < scene.instances.size() && i < sg->inst_count.size(); ++i) {
+        const uint32_t n = sg->inst_count[i];
+        if (!n) continue;
+        const uint32_t mat = scene.instances[i].material_index < scene.materials.size() ? scene.instances[i].material_index : 0u;   // SPEC §2.5
+        const MaterialEmission e = scene.material_emission(mat);
+        if (!e.emissive()) continue;
+        if (!rec_of[mat]) {
+            const uint32_t image = e.image < scene.images.size() ? e.image : LPT_INVALID_INDEX;
+            if (image != LPT_INVALID_INDEX && !(image < sg->pairs.image_resident.size() && sg->pairs.image_resident[image]))
+                return fail(LPT_ERR_INVALID_ARG, "material %u now emits with an image that was uploaded only as half of an (albedo, mra) pair: upload the scene again", mat);
+            float bits;
+            memcpy(&bits, &image, 4);
+            out.recs.push_back(make_float4(e.le[0], e.le[1], e.le[2], bits));
+            rec_of[mat] = (uint32_t)out.recs.size();
+        }
+        if (out.tri.empty()) out.tri.assign(std::max(sg->d.n_tris, 1u), 0u);
+        if ((size_t)sg->inst_first[i] + n > out.tri.size()) return fail(LPT_ERR_INVALID_ARG, "instance %zu lies beyond the baked triangles", i);
+        std::fill(out.tri.begin() + sg->inst_first[i], out.tri.begin() + sg->inst_first[i] + n, rec_of[mat]);
+    }
+    return LPT_OK;
+}
+static int commit_emis(lpt_scene_gpu *sg, const EmisTables &et) {
+    DScene &d = sg->d;
+    if (et.recs.empty()) {
+        sg->emis_tri.reset(); sg->emis_recs.reset();
+        d.emis_tri = nullptr; d.emis_recs = nullptr; d.n_emis = 0u;
+        return LPT_OK;
+    }
+    hipStream_t s = sg->dev->stream;
+    TRY(upload(sg->emis_tri, et.tri, s));
+    TRY(upload(sg->emis_recs, et.recs, s));
+    HIP_TRY(hipStreamSynchronize(s));   // the host vectors are the caller's
+    d.emis_tri = as<const uint32_t>(sg->emis_tri);
+    d.emis_recs = as<const float4>(sg->emis_recs);
+    d.n_emis = (uint32_t)et.recs.size();
+    return LPT_OK;
+}
+
 int lpt_scene_upload(lpt_device *dev, const lpt_scene *scene, lpt_scene_gpu **out) { return lpt_scene_upload_ex(dev, scene, LPT_ACCEL_BUILD_HOST_SAH, out); }
 
 int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags, lpt_scene_gpu **out) {
@@ -962,6 +1011,9 @@ int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags,
         TransTables tt;
         TRY(derive_trans(sg.get(), *scene, tt));
         TRY(commit_trans(sg.get(), tt));
+        EmisTables et;
+        TRY(derive_emis(sg.get(), *scene, et));
+        TRY(commit_emis(sg.get(), et));
     }
     sg->stats.triangles = d.n_tris;
     sg->stats.node_bytes = (uint32_t)sizeof(Node8);
@@ -1009,6 +1061,8 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
         TRY(derive_alpha(sg, *scene, at));
         TransTables tt;   // ... or transmissive (SPEC §21)
         TRY(derive_trans(sg, *scene, tt));
+        EmisTables et;    // ... or emissive (SPEC §22)
+        TRY(derive_emis(sg, *scene, et));
         // re-bake on the device (the object-space meshes are resident, only the transforms travel); a place-driven scatter then takes the new
         // Woop maps to every place a triangle has in the tree (a split triangle has several)
         DevMem woop_prim;
@@ -1023,6 +1077,7 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
         if (st != LPT_OK) return st;
         TRY(commit_alpha(sg, at));
         TRY(commit_trans(sg, tt));
+        TRY(commit_emis(sg, et));
         if (sg->stats.triangles) TRY(refit(sg));
     }
     if (out_rebaked) *out_rebaked = (uint32_t)changed.size();
@@ -1044,6 +1099,9 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
         TransTables tt;   // ... and the transmission tables (SPEC §21)
         TRY(derive_trans(sg, *scene, tt));
         TRY(commit_trans(sg, tt));
+        EmisTables et;    // ... and the emission tables (SPEC §22)
+        TRY(derive_emis(sg, *scene, et));
+        TRY(commit_emis(sg, et));
         return upload_punctual(sg, *scene);
     }
     HIP_TRY(hipSetDevice(sg->dev->ordinal));
@@ -1057,6 +1115,9 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
         TransTables tt;   // ... and their transmission states (SPEC §21)
         TRY(derive_trans(sg, *scene, tt));
         TRY(commit_trans(sg, tt));
+        EmisTables et;    // ... and their emission (SPEC §22)
+        TRY(derive_emis(sg, *scene, et));
+        TRY(commit_emis(sg, et));
     }
     DevMem woop_prim;
     TRY(dev_alloc(woop_prim, sizeof(WoopTri) * (size_t)n));
@@ -2030,7 +2091,7 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
         WavefrontFacts f;
         f.n_rays = n_rays; f.n_slots = p.n_slots; f.slot0 = p.slot0; f.n_samples = n_samples; f.cus = (uint32_t)r->dev->compute_units;
         f.solo = solo; f.stats = r->stats; f.denoise = denoise; f.env = env;
-        f.masked = sc.n_alpha != 0u; f.trans = sc.n_trans != 0u; f.punct = sc.n_punctual != 0u; f.max_depth = r->sg->stats.max_depth; f.stack_entries = sc.stack_entries;
+        f.masked = sc.n_alpha != 0u; f.trans = sc.n_trans != 0u; f.emis = sc.n_emis != 0u; f.punct = sc.n_punctual != 0u; f.max_depth = r->sg->stats.max_depth; f.stack_entries = sc.stack_entries;
         f.pixel_rad = 2.0f * th / (float)std::max(r->h, 1u); f.dense = (r->w % r->tile_w == 0u) && (r->h % r->tile_h == 0u); f.block8 = p.block8 != 0u;
         f.lim = KernelLimits{kBlock, kTraceBlock, kTailMax, kCoopWavesPerCu, kPacketBlocksPerCu, kPacketMaxPixelRad};
         const LaunchTuning tune = r->tune;
@@ -2095,11 +2156,11 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
                 const uint32_t seed = seed0 + t;     // += 1 per bounce (:453, :487)
                 const Queue qin = w->q[b & 1u], qout = w->q[(b + 1u) & 1u];
                 stage_begin(r, ST_SHADE, s, slot);            // :471-480, :502-508
-                // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); PUNCT / ENV as for k_path; TRANS: SPEC §21
-                with_flags([&](auto G, auto P, auto Tr) {
-                    auto launch = [&](auto... e) { hipLaunchKernelGGL((k_shade<decltype(G)::value, sizeof...(e) != 0, decltype(P)::value, decltype(Tr)::value, decltype(e)...>), dim3(pl.shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, sort_queues, e...); };
+                // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); PUNCT / ENV as for k_path; TRANS: SPEC §21; EMIS: SPEC §22
+                with_flags([&](auto G, auto P, auto Tr, auto Em) {
+                    auto launch = [&](auto... e) { hipLaunchKernelGGL((k_shade<decltype(G)::value, sizeof...(e) != 0, decltype(P)::value, decltype(Tr)::value, decltype(Em)::value, decltype(e)...>), dim3(pl.shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, sort_queues, e...); };
                     if (f.env) launch(ev); else launch();
-                }, f.denoise && b == 0u, f.punct, f.trans);
+                }, f.denoise && b == 0u, f.punct, f.trans, f.emis);
                 stage_end(r, s, slot);
                 if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
                 trace(b + 1u < nb ? (int)(b + 1u) : -1, (int)b);

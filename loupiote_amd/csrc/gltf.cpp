@@ -285,6 +285,8 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
     std::vector<Mask> masks;
     struct Glass { uint32_t material; float factor, ior; uint32_t thin; };
     std::vector<Glass> glasses;
+    struct Emitter { uint32_t material; float factor[3], strength; uint32_t image; };
+    std::vector<Emitter> emitters;
     for (size_t i = 0; i < mats.size(); ++i) {
         const Json &pbr = mats[i].at("pbrMetallicRoughness");
         lpt_material m = {{1.f, 1.f, 1.f, 1.f}, 1.f, 1.f, LPT_INVALID_INDEX, LPT_INVALID_INDEX};
@@ -323,6 +325,27 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
             if (factor < 0.0 || factor > 1.0) bad("transmissionFactor outside [0, 1]");
             if (ior < 1.0) bad("ior below 1");
             if (factor > 0.0) glasses.push_back(Glass{(uint32_t)tmp.materials.size() - 1u, (float)factor, (float)ior, thickness > 0.0 ? 0u : 1u});
+        }
+        // emissiveFactor / emissiveTexture / KHR_materials_emissive_strength (SPEC §22, §14(9)): a non-zero product sets the side table once the images are
+        // decoded (below).  What is stated is checked whatever the product; a file that states none of the three touches nothing
+        {
+            const Json *jf = mats[i].find("emissiveFactor"), *jt = mats[i].find("emissiveTexture");
+            const Json *jx = mats[i].at("extensions").at("KHR_materials_emissive_strength").find("emissiveStrength");
+            Emitter e{(uint32_t)tmp.materials.size() - 1u, {0.f, 0.f, 0.f}, 1.f, LPT_INVALID_INDEX};
+            if (jf) {
+                if (!jf->is_arr() || jf->size() != 3) bad("emissiveFactor is not three numbers");
+                for (size_t c = 0; c < 3; ++c) {
+                    const Json &n = (*jf)[c];
+                    if (!n.is_num() || !std::isfinite(n.num) || n.num < 0.0 || n.num > 1.0) bad("emissiveFactor outside [0, 1]");
+                    e.factor[c] = (float)n.num;
+                }
+            }
+            if (jx) {
+                if (!jx->is_num() || !std::isfinite(jx->num) || jx->num < 0.0 || !std::isfinite((float)jx->num)) bad("emissiveStrength is not a finite non-negative number");
+                e.strength = (float)jx->num;
+            }
+            if (jt) e.image = tex_id(*jt);
+            if (e.factor[0] * e.strength != 0.f || e.factor[1] * e.strength != 0.f || e.factor[2] * e.strength != 0.f) emitters.push_back(e);
         }
     }
     const Json &nodes = d.js.at("nodes");
@@ -391,6 +414,8 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
     }
     for (const Glass &g : glasses)
         if (lpt_scene_set_material_transmission(&tmp, g.material, g.factor, g.ior, g.thin) != LPT_OK) bad(std::string("KHR_materials_transmission rejected: ") + lpt_last_error());
+    for (const Emitter &e : emitters)
+        if (lpt_scene_set_material_emission(&tmp, e.material, e.factor, e.strength, e.image) != LPT_OK) bad(std::string("emissive material rejected: ") + lpt_last_error());
     *scene = std::move(tmp);
 }
 

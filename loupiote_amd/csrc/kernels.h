@@ -102,6 +102,11 @@ struct DScene {
     const uint32_t *trans_tri;
     const float4 *trans_recs;
     uint32_t n_trans;
+    // SPEC §22: emissive materials.  emis_tri[prim] = 0 for a non-emissive triangle, else 1 + the index of its record {Le.r, Le.g, Le.b, bits of the PLAIN image index
+    // (LPT_INVALID_INDEX: no emissive image)}.  Null / 0 for a scene without an emissive material in use; read only by the EMIS instantiations of shade_hit / k_shade
+    const uint32_t *emis_tri;
+    const float4 *emis_recs;
+    uint32_t n_emis;
 };
 constexpr uint32_t kPairedBit = 0x40000000u;
 
@@ -1720,6 +1725,8 @@ struct ShadeOut {
 // PUNCT (SPEC §19): the scene has punctual lights, which take the share pk.p_p of the non-probe light samples; the other instantiations never read `pk`.
 // TRANS (SPEC §21): the scene has a transmissive material in use; a hit on such a triangle is an interface event with probability tr (1 - metal) — no next-event
 // estimation, a next ray without a pdf (the camera rays' -1) —, a hit on any other triangle runs the code of the other instantiations with r3 untouched.
+// EMIS (SPEC §22): the scene has an emissive material in use; a surface hit on such a triangle adds T x Le (x the emissive image) with weight 1, from either side, on
+// every bounce, before the hit's own light sample — and changes nothing else of the hit.
 struct PunctPick { float p_p, p_pick; };   // the punctual share of the non-probe light samples; the probability with which ONE punctual light is picked
 template <bool ENV>
 __device__ __forceinline__ PunctPick punct_pick(const DScene &sc) {
@@ -1734,7 +1741,7 @@ __device__ __forceinline__ float rect_inv_nl(const DScene &sc, const PunctPick &
     if (PUNCT) return sc.n_lights ? ((ENV ? 0.5f : 1.0f) * (1.0f - pk.p_p)) / (float)sc.n_lights : 0.0f;
     return sc.n_lights ? (ENV ? 0.5f : 1.0f) / (float)sc.n_lights : 0.0f;   // ENV: a rectangle light is picked with 1 - p_env = 1/2
 }
-template <bool GBUF, bool ENV, bool PUNCT, bool TRANS = false, typename LoadO, typename AddL>
+template <bool GBUF, bool ENV, bool PUNCT, bool TRANS = false, bool EMIS = false, typename LoadO, typename AddL>
 __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe, const DEnv &ev, const DNoise &nz, const FrameParams &p, const float *s_lut,
                                           const uint32_t bounce, const bool last_bounce, const uint32_t seed_base, const float inv_nl, const PunctPick &pk, const GBufArgs &gb,
                                           const float4 d4, const float4 T4, const float4 h4, LoadO load_o, AddL add_l, ShadeOut &out) {
@@ -1783,6 +1790,8 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
         const float4 *tv = sc.tri_verts + kTriRec * (size_t)prim;
         const float4 P0 = tv[0], N0 = tv[1], P1 = tv[2], N1 = tv[3], P2 = tv[4], N2 = tv[5];
         const float4 mc = tv[6], mp = tv[7];
+        uint32_t em = 0u;   // EMIS: 0, or 1 + the triangle's emission record.  The word depends on `prim` alone, so its load goes out with the record's, not behind the texture taps
+        if (EMIS) em = sc.emis_tri[prim];
         float bw = (1.0f - hu) - hv;
         const f3 p0 = mk3(P0.x, P0.y, P0.z), p1 = mk3(P1.x, P1.y, P1.z), p2 = mk3(P2.x, P2.y, P2.z);
         f3 P = mk3((p0.x * bw + p1.x * hu) + p2.x * hv, (p0.y * bw + p1.y * hu) + p2.y * hv, (p0.z * bw + p1.z * hu) + p2.z * hv);
@@ -1817,6 +1826,16 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
                     const float4 tex = texture_lookup(sc, s_lut, mtex, tu, tvv, false);
                     rough *= tex.y; metal *= tex.z;
                 }
+            }
+            if (EMIS && em != 0u) {   // SPEC §22: weight 1 whatever the ray's pdf, both sides (the flipped Ng plays no part), the last bounce included
+                const float4 er = sc.emis_recs[em - 1u];
+                f3 E = mk3(er.x, er.y, er.z);
+                const uint32_t etex = __float_as_uint(er.w);
+                if (etex < sc.n_images) {
+                    const float4 tex = texture_lookup(sc, s_lut, etex, tu, tvv, true);
+                    E.x *= tex.x; E.y *= tex.y; E.z *= tex.z;
+                }
+                add_l(T.x * E.x, T.y * E.y, T.z * E.z);
             }
             g_n = Ns; g_P = P;
             g_alb = mk3(clampf(base.x, 0.0f, 1.0f), clampf(base.y, 0.0f, 1.0f), clampf(base.z, 0.0f, 1.0f));
@@ -1991,8 +2010,12 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
 #ifndef LPT_SHADE_WAVES_TRANS
 #define LPT_SHADE_WAVES_TRANS(ENV, PUNCT) 3
 #endif
-template <bool GBUF, bool ENV = false, bool PUNCT = false, bool TRANS = false, typename... Env>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TRANS ? LPT_SHADE_WAVES_TRANS(ENV, PUNCT) : LPT_SHADE_WAVES(ENV, PUNCT)))) void k_shade(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue qin, const float4 *hits,
+// EMIS (SPEC §22): the instantiations that run while the scene has an emissive material in use
+#ifndef LPT_SHADE_WAVES_EMIS
+#define LPT_SHADE_WAVES_EMIS(ENV, PUNCT, TRANS) 3
+#endif
+template <bool GBUF, bool ENV = false, bool PUNCT = false, bool TRANS = false, bool EMIS = false, typename... Env>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(EMIS ? LPT_SHADE_WAVES_EMIS(ENV, PUNCT, TRANS) : TRANS ? LPT_SHADE_WAVES_TRANS(ENV, PUNCT) : LPT_SHADE_WAVES(ENV, PUNCT)))) void k_shade(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue qin, const float4 *hits,
                                                   Queue qout, ShadowQueue sq, float4 *Lsum, FrameCounters *ctr, int bounce,
                                                   uint32_t seed_base, GBufArgs gb, int sorted, Env... env) {
     static_assert(sizeof...(Env) == (ENV ? 1u : 0u), "the ENV instantiations take the distribution, the others nothing");
@@ -2023,7 +2046,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TRANS ? 
         if (i < count) {
             const float4 d4 = ld_nt(qin.d + i), T4 = ld_nt(qin.T + i), h4 = ld_nt(hits + i);
             const uint32_t slot = __float_as_uint(d4.w);
-            shade_hit<GBUF, ENV, PUNCT, TRANS>(sc, probe, ev, nz, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, gb, d4, T4, h4,
+            shade_hit<GBUF, ENV, PUNCT, TRANS, EMIS>(sc, probe, ev, nz, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, gb, d4, T4, h4,
                             [&]() { return ld_nt(qin.o + i); },
                             [&](float r, float g, float b) {
                                 float4 L = Lsum[slot];

@@ -222,6 +222,38 @@ int lpt_scene_get_material_transmission(const lpt_scene *s, uint32_t material_in
     return LPT_OK;
 }
 
+// ---- emissive materials (SPEC §22): a third side table of `materials`, grown on the first write; Le = 0 in all channels drops the record
+int lpt_scene_set_material_emission(lpt_scene *s, uint32_t material_index, const float factor[3], float strength, uint32_t image) {
+    if (!s || !factor) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_emission: null");
+    if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_emission: material %u of %zu", material_index, s->materials.size());
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(factor[c]) || factor[c] < 0.f) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_emission: the factor must be finite and >= 0");
+    if (!std::isfinite(strength) || strength < 0.f) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_emission: the strength must be finite and >= 0");
+    if (image != LPT_INVALID_INDEX && image >= s->images.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_emission: image %u of %zu", image, s->images.size());
+    MaterialEmission e;
+    for (int c = 0; c < 3; ++c) {
+        e.le[c] = factor[c] * strength;
+        if (!std::isfinite(e.le[c])) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_emission: factor x strength is not finite");
+    }
+    e.image = image;
+    if (!e.emissive()) {   // non-emissive again: the record is dropped, whatever the image says
+        if (material_index < s->emission.size()) s->emission[material_index] = MaterialEmission();
+        return LPT_OK;
+    }
+    if (s->emission.size() < s->materials.size()) s->emission.resize(s->materials.size());
+    s->emission[material_index] = e;
+    return LPT_OK;
+}
+
+int lpt_scene_get_material_emission(const lpt_scene *s, uint32_t material_index, float le[3], uint32_t *image) {
+    if (!s) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_emission: null");
+    if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_emission: material %u of %zu", material_index, s->materials.size());
+    const MaterialEmission e = s->material_emission(material_index);
+    if (le) for (int c = 0; c < 3; ++c) le[c] = e.le[c];
+    if (image) *image = e.image;
+    return LPT_OK;
+}
+
 int lpt_scene_add_image(lpt_scene *s, const uint8_t *rgba8, uint32_t w, uint32_t h, uint32_t *out_index) {
     if (!s || !rgba8 || !w || !h) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_add_image: null or empty");
     Image im;
