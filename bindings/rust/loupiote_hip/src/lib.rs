@@ -143,6 +143,15 @@ impl Scene {
         check(unsafe { ffi::lpt_scene_get_material_emission(self.h, material, le.as_mut_ptr(), &mut image) })?;
         Ok((le, if image == ffi::LPT_INVALID_INDEX { None } else { Some(image) }))
     }
+    /// SPEC.md §23 on the host: the emissive triangles' alias table -> (q, alias, prim, prim_alias, sum_w); empty = no distribution
+    pub fn emitter_distribution(&self) -> Result<(Vec<f32>, Vec<u32>, Vec<u32>, Vec<u32>, f64), Error> {
+        let (mut n, mut total) = (0u32, 0f64);
+        check(unsafe { ffi::lpt_scene_emitter_distribution(self.h, 0, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), &mut n, &mut total) })?;
+        let cap = n as usize;
+        let (mut q, mut alias, mut prim, mut prim_alias) = (vec![0f32; cap], vec![0u32; cap], vec![0u32; cap], vec![0u32; cap]);
+        check(unsafe { ffi::lpt_scene_emitter_distribution(self.h, n, q.as_mut_ptr(), alias.as_mut_ptr(), prim.as_mut_ptr(), prim_alias.as_mut_ptr(), &mut n, &mut total) })?;
+        Ok((q, alias, prim, prim_alias, total))
+    }
     /// SPEC.md §19: a point / spot / directional light (KHR_lights_punctual); records from `punctual_light`
     pub fn add_punctual_light(&mut self, light: &ffi::lpt_punctual_light) -> Result<u32, Error> {
         let mut out = 0u32;
@@ -342,6 +351,13 @@ impl Renderer {
     pub fn set_seed(&mut self, seed: u32) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_seed(self.h, seed) }) }
     /// `SPEC.md` §18: next-event estimation samples the environment probe too (off by default; frames change with it)
     pub fn set_env_sampling(&mut self, on: bool) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_env_sampling(self.h, on as i32) }) }
+    /// SPEC.md §23: next-event estimation samples the emissive triangles too; off by default
+    pub fn set_emissive_sampling(&mut self, on: bool) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_emissive_sampling(self.h, on as i32) }) }
+    pub fn emissive_sampling(&self) -> Result<bool, Error> {
+        let mut f = 0i32;
+        check(unsafe { ffi::lpt_renderer_get_emissive_sampling(self.h, &mut f) })?;
+        Ok(f != 0)
+    }
     /// launch tuning (the `LPT_OPT_` constants of `ffi`): never changes a frame
     pub fn set_option(&mut self, option: i32, value: u64) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_option(self.h, option, value) }) }
     /// tile-sharded frames: bind a communicator (implies `set_shard(rank, world, 32, 8)`), then `exchange` after the frame's `raytrace` calls

@@ -112,6 +112,12 @@ class Scene {  // scene.rs:30-54
         check(lpt_scene_get_material_emission(h_, material, e.le, &e.image));
         return e;
     }
+    // SPEC.md §23: the emissive triangles' sampling distribution, on the host; returns the number of entries (up to `cap` of them are written)
+    uint32_t emitter_distribution(uint32_t cap, float *q, uint32_t *alias, uint32_t *prim_self, uint32_t *prim_alias, double *sum_w = nullptr) const {
+        uint32_t n = 0;
+        check(lpt_scene_emitter_distribution(h_, cap, q, alias, prim_self, prim_alias, &n, sum_w));
+        return n;
+    }
     // SPEC.md §19: point / spot / directional lights (KHR_lights_punctual); records from point_light / spot_light / directional_light below
     uint32_t add_punctual_light(const lpt_punctual_light &l) { uint32_t id = 0; check(lpt_scene_add_punctual_light(h_, &l, &id)); return id; }
     void set_punctual_light(uint32_t i, const lpt_punctual_light &l) { check(lpt_scene_set_punctual_light(h_, i, &l)); }
@@ -179,6 +185,11 @@ class SceneGPU {  // scene.rs:56-64,151-188
     void sample_punctual(const Device &device, uint32_t light, const float *points, uint32_t n, float *wi, float *dist, float *E) const {
         check(lpt_scene_gpu_sample_punctual(device.inner(), h_, light, points, n, wi, dist, E));
     }
+    // SPEC.md §23: the shading kernels' emitter sample, rands[n][4] = {ra, rb, r1, r2} per point
+    void sample_emitter(const Device &device, uint32_t n, const float *points, const float *rands, uint32_t *prim, uint32_t *sampled, float *y, float *wi, float *dist, float *cl,
+                        float *p_a, float *E) const {
+        check(lpt_scene_gpu_sample_emitter(device.inner(), h_, n, points, rands, prim, sampled, y, wi, dist, cl, p_a, E));
+    }
 
    private:
     SceneGPU() = default;
@@ -244,6 +255,9 @@ class Renderer {  // renderer.rs:169-811
     /// SPEC.md §18: next-event estimation samples the environment probe too (off by default; frames change with it)
     void set_env_sampling(bool on) { check(lpt_renderer_set_env_sampling(h_, on ? 1 : 0)); }
     bool env_sampling() const { int f = 0; check(lpt_renderer_get_env_sampling(h_, &f)); return f != 0; }
+    // SPEC.md §23: next-event estimation samples the emissive triangles too; off by default
+    void set_emissive_sampling(bool on) { check(lpt_renderer_set_emissive_sampling(h_, on ? 1 : 0)); }
+    bool emissive_sampling() const { int f = 0; check(lpt_renderer_get_emissive_sampling(h_, &f)); return f != 0; }
     void set_seed(uint32_t s) { check(lpt_renderer_set_seed(h_, s)); }
     void set_vfov(float radians) { check(lpt_renderer_set_vfov(h_, radians)); }
     /// `weights` (one small integer per rank, the same on every rank; nullptr = equal shares): unequal tile shares, e.g. fewer tiles for the rank that also assembles the frame

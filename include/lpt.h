@@ -373,6 +373,22 @@ int lpt_scene_gpu_update_punctual(lpt_scene_gpu *scene_gpu, const lpt_scene *sce
 int lpt_scene_gpu_sample_punctual(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t light_index, const float *points, uint32_t n,
                                   float *wi, float *dist, float *E);
 
+/* build-only extension (SPEC.md §23; no reference counterpart): the sampling distribution of the scene's emissive triangles, pure host
+ * arithmetic (no GPU): the instances of emissive materials are baked on the host (SPEC.md §2.5) and every baked triangle with a non-zero
+ * binary32 cross product becomes an entry, in prim-id order, with the weight area x lum(Le).  Writes min(*n_e, cap) entries of the
+ * alias table — q (the probability of keeping the slot), alias (the other slot), prim_self and prim_alias (the baked triangle ids of
+ * the slot and of its alias) —, *n_e (the number of entries, which may exceed cap) and *sum_w (the sum of the weights; 0 with
+ * *n_e = 0: the scene has no distribution).  NULL outputs other than n_e are skipped. */
+int lpt_scene_emitter_distribution(const lpt_scene *scene, uint32_t cap, float *q, uint32_t *alias, uint32_t *prim_self, uint32_t *prim_alias,
+                                   uint32_t *n_e, double *sum_w);
+/* build-only extension (SPEC.md §23), for tests and tools in the manner of lpt_scene_gpu_sample_punctual: the emitter sample of the
+ * shading kernels (kernels.h emitter_sample), once per point of points[n][3] with the draws rands[n][4] = {ra, rb, r1, r2} ->
+ * prim[n] (the picked baked triangle), sampled[n] (0: no sample, the other outputs are then zero), y[n][3] (the point on the emitter),
+ * wi[n][3] (unit direction towards it), dist[n], cl[n] (the cosine at the emitter), p_a[n] (the area density lum(Le) / sum_w) and
+ * E[n][3] (Le x the emissive image).  LPT_ERR_INVALID_ARG for a scene without a distribution.  Blocking; host arrays. */
+int lpt_scene_gpu_sample_emitter(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const float *points, const float *rands, uint32_t *prim,
+                                 uint32_t *sampled, float *y, float *wi, float *dist, float *cl, float *p_a, float *E);
+
 /* build-only extension (SPEC.md §21), for tests and tools in the manner of lpt_probe_sample: the interface event of the shading kernels
  * (kernels.h interface_sample), once per element.  Inputs, n of each: dirs[n][3] the ray's unit direction d, ns[n][3] the shading
  * normal, ngf[n][3] the geometric normal flipped against d, entering[n] (non-zero: the geometric normal was not flipped), base[n][3]
@@ -544,6 +560,12 @@ int lpt_renderer_set_max_bounces(lpt_renderer *r, uint32_t bounces);
  * a call of its own.  Active while the bound probe has a distribution (not black); recorded calls are submitted first. */
 int lpt_renderer_set_env_sampling(lpt_renderer *r, int flag);
 int lpt_renderer_get_env_sampling(const lpt_renderer *r, int *flag);
+/* new (SPEC.md §23): next-event estimation samples the emissive triangles too (multiple importance sampling against the BSDF rays
+ * that hit them).  Off (0) by default; off, every frame is what it was (SPEC.md §22).  On, the expectation of a frame is unchanged and
+ * its variance drops; the frame's numbers change, so call lpt_renderer_reset_accumulation after a toggle.  Active while the bound
+ * scene has an emitter distribution (an emissive material in use on a triangle with an area); recorded calls are submitted first. */
+int lpt_renderer_set_emissive_sampling(lpt_renderer *r, int flag);
+int lpt_renderer_get_emissive_sampling(const lpt_renderer *r, int *flag);
 int lpt_renderer_set_seed(lpt_renderer *r, uint32_t user_seed);
 /* vertical field of view in radians (reference: Camera::default inside albedo) */
 int lpt_renderer_set_vfov(lpt_renderer *r, float radians);

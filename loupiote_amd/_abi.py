@@ -124,6 +124,8 @@ SIGNATURES = {
     "lpt_scene_gpu_update_instances": (_i, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "lpt_scene_gpu_update_punctual": (_i, [_vp, _vp]),
     "lpt_scene_gpu_sample_punctual": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "lpt_scene_emitter_distribution": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _pu32, C.POINTER(C.c_double)]),
+    "lpt_scene_gpu_sample_emitter": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lpt_interface_sample": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lpt_probe_upload": (_i, [_vp, _vp, _u32, _u32, _pvp]),
     "lpt_probe_destroy": (_i, [_vp]),
@@ -170,6 +172,8 @@ SIGNATURES = {
     "lpt_renderer_set_max_bounces": (_i, [_vp, _u32]),
     "lpt_renderer_set_env_sampling": (_i, [_vp, _i]),
     "lpt_renderer_get_env_sampling": (_i, [_vp, C.POINTER(_i)]),
+    "lpt_renderer_set_emissive_sampling": (_i, [_vp, _i]),
+    "lpt_renderer_get_emissive_sampling": (_i, [_vp, C.POINTER(_i)]),
     "lpt_renderer_set_seed": (_i, [_vp, _u32]),
     "lpt_renderer_set_vfov": (_i, [_vp, _f]),
     "lpt_renderer_set_shard": (_i, [_vp, _u32, _u32, _u32, _u32]),

@@ -255,6 +255,18 @@ class Scene:
         _check(A.lib().lpt_scene_get_material_emission(self._h, int(material_index), A.ptr(le), C.byref(image)))
         return le, (None if image.value == A.INVALID_INDEX else int(image.value))
 
+    def emitter_distribution(self):
+        """SPEC.md §23 on the host (no GPU): the sampling distribution of the scene's emissive triangles.  Returns a dict of q [n_e], alias [n_e],
+        prim [n_e] (baked triangle ids, ascending), prim_alias [n_e] and sum_w (the sum of the weights area x lum(Le); 0 and no entry = no distribution)."""
+        n, total = C.c_uint32(), C.c_double()
+        _check(A.lib().lpt_scene_emitter_distribution(self._h, 0, None, None, None, None, C.byref(n), C.byref(total)))
+        cap = int(n.value)
+        out = {"q": np.zeros(cap, np.float32), "alias": np.zeros(cap, np.uint32), "prim": np.zeros(cap, np.uint32), "prim_alias": np.zeros(cap, np.uint32)}
+        if cap:
+            _check(A.lib().lpt_scene_emitter_distribution(self._h, cap, A.ptr(out["q"]), A.ptr(out["alias"]), A.ptr(out["prim"]), A.ptr(out["prim_alias"]), C.byref(n), C.byref(total)))
+        out["sum_w"] = total.value
+        return out
+
     def _get(self, fn, dt, count):
         out = np.zeros(count, dt)
         _check(fn(self._h, 0, count, A.ptr(out)))
@@ -369,6 +381,21 @@ class SceneGPU:
         wi, dist, E = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
         _check(A.lib().lpt_scene_gpu_sample_punctual(self._dev.inner(), self._h, int(light_index), A.ptr(pts), n, A.ptr(wi), A.ptr(dist), A.ptr(E)))
         return wi, dist, E
+
+    def sample_emitter(self, points, rands):
+        """The emitter sample the shading kernels run (SPEC.md §23) on the GPU: points[n, 3], rands[n, 4] = (ra, rb, r1, r2) -> a dict of prim[n],
+        sampled[n] (bool), y[n, 3], wi[n, 3], dist[n], cl[n], p_a[n], E[n, 3]; zeros where there is no sample (prim is still the pick)."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        rs = np.ascontiguousarray(rands, np.float32).reshape(-1, 4)
+        n = pts.shape[0]
+        if rs.shape[0] != n:
+            raise Error(A.LPT_ERR_INVALID_ARG, "sample_emitter: one (ra, rb, r1, r2) per point")
+        o = {"prim": np.zeros(n, np.uint32), "sampled": np.zeros(n, np.uint32), "y": np.zeros((n, 3), np.float32), "wi": np.zeros((n, 3), np.float32),
+             "dist": np.zeros(n, np.float32), "cl": np.zeros(n, np.float32), "p_a": np.zeros(n, np.float32), "E": np.zeros((n, 3), np.float32)}
+        _check(A.lib().lpt_scene_gpu_sample_emitter(self._dev.inner(), self._h, n, A.ptr(pts), A.ptr(rs), A.ptr(o["prim"]), A.ptr(o["sampled"]), A.ptr(o["y"]),
+                                                    A.ptr(o["wi"]), A.ptr(o["dist"]), A.ptr(o["cl"]), A.ptr(o["p_a"]), A.ptr(o["E"])))
+        o["sampled"] = o["sampled"] != 0
+        return o
 
     def trace_closest(self, origins, dirs):
         o = np.ascontiguousarray(origins, np.float32)
@@ -587,6 +614,15 @@ class Renderer:
     def get_env_sampling(self):
         f = C.c_int()
         _check(A.lib().lpt_renderer_get_env_sampling(self._h, C.byref(f)))
+        return bool(f.value)
+
+    def set_emissive_sampling(self, flag):
+        """SPEC.md §23: next-event estimation samples the emissive triangles too (off by default; the expectation of a frame stays, its noise drops)"""
+        _check(A.lib().lpt_renderer_set_emissive_sampling(self._h, 1 if flag else 0))
+
+    def get_emissive_sampling(self):
+        f = C.c_int()
+        _check(A.lib().lpt_renderer_get_emissive_sampling(self._h, C.byref(f)))
         return bool(f.value)
 
     def set_seed(self, s):

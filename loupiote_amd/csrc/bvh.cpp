@@ -288,8 +288,10 @@ inline void normalize3(float v[3]) {
     v[0] *= inv; v[1] *= inv; v[2] *= inv;
 }
 
-// SPEC §2.5: one instance -> world-space triangles (appended to `verts`, 3 per triangle); returns the material
-uint32_t bake_one(const lpt_scene &s, size_t ii, std::vector<lpt_vertex> &verts) {
+}  // namespace
+
+// SPEC §2.5: one instance -> world-space triangles (appended to `verts`, 3 per triangle); returns the material.  Also emit_dist.cpp's bake (common.h)
+uint32_t bake_instance(const lpt_scene &s, size_t ii, std::vector<lpt_vertex> &verts) {
     const lpt_instance &inst = s.instances[ii];
     uint32_t mi = inst.material_index;
     if (mi >= s.materials.size()) mi = 0;
@@ -320,6 +322,8 @@ uint32_t bake_one(const lpt_scene &s, size_t ii, std::vector<lpt_vertex> &verts)
     return mi;
 }
 
+namespace {
+
 // SPEC §2.5: instances -> world-space soup
 void bake(const lpt_scene &s, Accel &out) {
     out.tri_verts.clear();
@@ -328,7 +332,7 @@ void bake(const lpt_scene &s, Accel &out) {
     out.inst_count.assign(s.instances.size(), 0u);
     for (size_t ii = 0; ii < s.instances.size(); ++ii) {
         const size_t before = out.tri_verts.size() / 3;
-        const uint32_t mi = bake_one(s, ii, out.tri_verts);
+        const uint32_t mi = bake_instance(s, ii, out.tri_verts);
         const size_t ntri = out.tri_verts.size() / 3 - before;
         out.inst_first[ii] = (uint32_t)before;
         out.inst_count[ii] = (uint32_t)ntri;

@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "env_dist.h"
+#include "emit_dist.h"
 #include "kernels.h"
 #include "build_kernels.h"
 #include "launch_plan.h"
@@ -149,6 +150,7 @@ struct lpt_scene_gpu {
     DevMem tri_verts, materials, lights, texels, images, srgb_lut, pair_texels, pair_images;
     DevMem punctual;                // SPEC §19: lpt_punctual_light records (DScene::punctual)
     DevMem trans_tri, trans_recs;   // SPEC §21: the per-triangle table and the records of the transmissive materials (DScene::trans_tri / trans_recs); empty without glass
+    DevMem emit_tab;                // SPEC §23: the emitter distribution's entries (DScene::emit_tab); empty without a distribution
     DevMem emis_tri, emis_recs;     // SPEC §22: the per-triangle table and the records of the emissive materials (DScene::emis_tri / emis_recs); empty without emitters
     DevMem alpha_tri, alpha_recs;   // SPEC §20: the per-triangle table and the records of the masked materials (DScene::alpha_tri / alpha_recs); empty without masks
     TexturePairs pairs;
@@ -233,6 +235,7 @@ struct lpt_renderer {
     int mode = LPT_BLIT_PATHTRACE;
     // build-only knobs
     uint32_t max_bounces = 3, user_seed = 0;
+    int emissive_sampling = 0; // SPEC §23 (lpt_renderer_set_emissive_sampling): the ESAMP kernels while the bound scene has an emitter distribution
     int env_sampling = 0;      // SPEC §18 (lpt_renderer_set_env_sampling): the ENV kernels while the bound probe has a distribution
     float vfov = 0.78539816339744830962f;
     uint32_t rank = 0, world = 1, tile_w = 32, tile_h = 8;
@@ -556,7 +559,7 @@ static int bake_instances(lpt_scene_gpu *sg, const lpt_scene &scene, const std::
         memcpy(a.m, now.model_to_world, sizeof a.m);
         const float *m = a.m;
         const float a00 = m[0], a10 = m[1], a20 = m[2], a01 = m[4], a11 = m[5], a21 = m[6], a02 = m[8], a12 = m[9], a22 = m[10];
-        a.c[0] = a11 * a22 - a12 * a21; a.c[1] = a12 * a20 - a10 * a22; a.c[2] = a10 * a21 - a11 * a20;   // bvh.cpp bake_one
+        a.c[0] = a11 * a22 - a12 * a21; a.c[1] = a12 * a20 - a10 * a22; a.c[2] = a10 * a21 - a11 * a20;   // bvh.cpp bake_instance
         a.c[3] = a02 * a21 - a01 * a22; a.c[4] = a00 * a22 - a02 * a20; a.c[5] = a01 * a20 - a00 * a21;
         a.c[6] = a01 * a12 - a02 * a11; a.c[7] = a02 * a10 - a00 * a12; a.c[8] = a00 * a11 - a01 * a10;
         a.vertex_offset = e.vertex_offset; a.index_offset = e.index_offset; a.first_tri = sg->inst_first[i]; a.n_tris = n;
@@ -915,6 +918,39 @@ static int commit_emis(lpt_scene_gpu *sg, const EmisTables &et) {
     return LPT_OK;
 }
 
+// SPEC §23: the emitter distribution of the scene as it is now (emit_dist.cpp: the emissive instances baked on the host, so nothing is read back), derived and
+// committed beside the emission tables — at upload, rebuild and every instance update, since the weights are world-space areas.  The cost is a host bake of every
+// emissive instance (bake_instance: normals too, which the distribution does not read) on every update, also one that moves no emitter: linear in the emissive
+// triangles, meant for lamps of a few thousand triangles, not for a scene that is mostly emissive.
+static inline float bits_as_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
+struct EmitTable { std::vector<float4> tab; float inv_W = 0.0f; };
+static int derive_emit(const lpt_scene_gpu *sg, const lpt_scene &scene, EmitTable &out) {
+    EmitDist dist;
+    emitter_distribution(scene, dist);
+    out = EmitTable();
+    for (size_t i = 0; i < dist.prim.size(); ++i) {
+        if (dist.prim[i] >= sg->d.n_tris) return fail(LPT_ERR_INVALID_ARG, "emissive triangle %u lies beyond the %u baked triangles", dist.prim[i], sg->d.n_tris);
+        out.tab.push_back(make_float4(dist.q[i], bits_as_float(dist.alias[i]), bits_as_float(dist.prim[i]), bits_as_float(dist.prim[dist.alias[i]])));
+    }
+    if (!out.tab.empty()) out.inv_W = (float)(1.0 / dist.sum_w);
+    return LPT_OK;
+}
+static int commit_emit(lpt_scene_gpu *sg, const EmitTable &et) {
+    DScene &d = sg->d;
+    if (et.tab.empty() || !d.n_emis) {
+        sg->emit_tab.reset();
+        d.emit_tab = nullptr; d.n_emit = 0u; d.emit_inv_W = 0.0f;
+        return LPT_OK;
+    }
+    hipStream_t s = sg->dev->stream;
+    TRY(upload(sg->emit_tab, et.tab, s));
+    HIP_TRY(hipStreamSynchronize(s));   // the host vector is the caller's
+    d.emit_tab = as<const float4>(sg->emit_tab);
+    d.n_emit = (uint32_t)et.tab.size();
+    d.emit_inv_W = et.inv_W;
+    return LPT_OK;
+}
+
 int lpt_scene_upload(lpt_device *dev, const lpt_scene *scene, lpt_scene_gpu **out) { return lpt_scene_upload_ex(dev, scene, LPT_ACCEL_BUILD_HOST_SAH, out); }
 
 int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags, lpt_scene_gpu **out) {
@@ -1014,6 +1050,9 @@ int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags,
         EmisTables et;
         TRY(derive_emis(sg.get(), *scene, et));
         TRY(commit_emis(sg.get(), et));
+        EmitTable em;   // SPEC §23
+        TRY(derive_emit(sg.get(), *scene, em));
+        TRY(commit_emit(sg.get(), em));
     }
     sg->stats.triangles = d.n_tris;
     sg->stats.node_bytes = (uint32_t)sizeof(Node8);
@@ -1063,6 +1102,8 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
         TRY(derive_trans(sg, *scene, tt));
         EmisTables et;    // ... or emissive (SPEC §22)
         TRY(derive_emis(sg, *scene, et));
+        EmitTable em;   // ... and with it the emitter distribution (SPEC §23: world-space areas)
+        TRY(derive_emit(sg, *scene, em));
         // re-bake on the device (the object-space meshes are resident, only the transforms travel); a place-driven scatter then takes the new
         // Woop maps to every place a triangle has in the tree (a split triangle has several)
         DevMem woop_prim;
@@ -1078,6 +1119,7 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
         TRY(commit_alpha(sg, at));
         TRY(commit_trans(sg, tt));
         TRY(commit_emis(sg, et));
+        TRY(commit_emit(sg, em));
         if (sg->stats.triangles) TRY(refit(sg));
     }
     if (out_rebaked) *out_rebaked = (uint32_t)changed.size();
@@ -1102,6 +1144,9 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
         EmisTables et;    // ... and the emission tables (SPEC §22)
         TRY(derive_emis(sg, *scene, et));
         TRY(commit_emis(sg, et));
+        EmitTable em;   // SPEC §23
+        TRY(derive_emit(sg, *scene, em));
+        TRY(commit_emit(sg, em));
         return upload_punctual(sg, *scene);
     }
     HIP_TRY(hipSetDevice(sg->dev->ordinal));
@@ -1118,6 +1163,9 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
         EmisTables et;    // ... and their emission (SPEC §22)
         TRY(derive_emis(sg, *scene, et));
         TRY(commit_emis(sg, et));
+        EmitTable em;   // ... and the emitter distribution (SPEC §23)
+        TRY(derive_emit(sg, *scene, em));
+        TRY(commit_emit(sg, em));
     }
     DevMem woop_prim;
     TRY(dev_alloc(woop_prim, sizeof(WoopTri) * (size_t)n));
@@ -1172,6 +1220,35 @@ int lpt_scene_gpu_sample_punctual(lpt_device *dev, const lpt_scene_gpu *sg, uint
     return LPT_OK;
 }
 
+// SPEC §23: the emitter sample of the shading kernels (kernels.h emitter_sample), once per point, for tests and tools
+int lpt_scene_gpu_sample_emitter(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const float *points, const float *rands, uint32_t *prim, uint32_t *sampled, float *y,
+                                 float *wi, float *dist, float *cl, float *p_a, float *E) {
+    if (!dev || !sg || (n && (!points || !rands || !prim || !sampled || !y || !wi || !dist || !cl || !p_a || !E))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_emitter: null");
+    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_emitter: the scene belongs to another device");
+    if (!sg->d.n_emit) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_emitter: the scene has no emitter distribution");
+    if (!n) return LPT_OK;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    DevMem dp, dr, dout;
+    TRY(dev_alloc(dp, sizeof(float) * 3 * (size_t)n));
+    TRY(dev_alloc(dr, sizeof(float) * 4 * (size_t)n));
+    TRY(dev_alloc(dout, sizeof(uint32_t) * 16 * (size_t)n));
+    HIP_TRY(hipMemcpy(dp.get(), points, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dr.get(), rands, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_emitter_sample, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, sg->d, as<const float>(dp), as<const float>(dr), n, as<uint32_t>(dout));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    std::vector<uint32_t> o(16u * (size_t)n);
+    HIP_TRY(hipMemcpy(o.data(), dout.get(), sizeof(uint32_t) * o.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t *e = o.data() + 16u * i;
+        prim[i] = e[0]; sampled[i] = e[1];
+        memcpy(y + 3u * i, e + 2, 12); memcpy(wi + 3u * i, e + 5, 12);
+        memcpy(dist + i, e + 8, 4); memcpy(cl + i, e + 9, 4); memcpy(p_a + i, e + 10, 4);
+        memcpy(E + 3u * i, e + 11, 12);
+    }
+    return LPT_OK;
+}
+
 // SPEC §21: the interface event of the shading kernels (kernels.h interface_sample), once per element, for tests and tools
 int lpt_interface_sample(lpt_device *dev, uint32_t n, const float *dirs, const float *ns, const float *ngf, const uint32_t *entering, const float *base, const float *ior,
                          const uint32_t *thin, const float *r4, float *wi, float *weight, uint32_t *kind) {
@@ -1217,7 +1294,6 @@ int lpt_probe_upload(lpt_device *dev, const uint8_t *rgbe8, uint32_t w, uint32_t
     return LPT_OK;
 }
 
-static inline float bits_as_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 // The probe's distribution (SPEC §18; env_dist.cpp) on the device, built the first time it is asked for; false: the probe has none.
 // The texels come back from the device, so that a probe keeps no host copy for a mode it may never be used with.
 static int probe_env(lpt_probe *p, bool &has) {
@@ -1710,6 +1786,17 @@ int lpt_renderer_get_env_sampling(const lpt_renderer *r, int *flag) {
     *flag = r->env_sampling;
     return LPT_OK;
 }
+int lpt_renderer_set_emissive_sampling(lpt_renderer *r, int flag) {
+    if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_emissive_sampling: null");
+    FLUSH_OR_RETURN(r);
+    r->emissive_sampling = flag ? 1 : 0;
+    return LPT_OK;
+}
+int lpt_renderer_get_emissive_sampling(const lpt_renderer *r, int *flag) {
+    if (!r || !flag) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_get_emissive_sampling: null");
+    *flag = r->emissive_sampling;
+    return LPT_OK;
+}
 int lpt_renderer_set_seed(lpt_renderer *r, uint32_t s) {
     if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_seed: null");
     FLUSH_OR_RETURN(r);
@@ -2102,6 +2189,7 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
         const size_t trace_lds = pl.stack_lds + (pl.tail ? sizeof(uint32_t) * tail_lds_words(f.max_depth) : 0u) + (pl.stats_lds_pad ? 64u : 0u);
         const size_t coop_lds = sizeof(uint32_t) * coop_stack_entries(kCoopStack, f.max_depth);
         const int sort_queues = r->sort_queues;
+        const bool esamp = r->emissive_sampling && f.emis && sc.n_emit != 0u;   // SPEC §23: the ESAMP forms of k_shade while the mode is on and the scene has an emitter distribution
         // The launches in stages, so that the pieces of a cut batch can be enqueued stage by stage across the lanes (flush_pending,
         // LPT_EXP_LANE_PHASE): stage 0 = counters, ray generation and the primary rays (with the path kernel: the whole wavefront),
         // stage b + 1 = shade(b) and the traversal launch behind it.  `ph` orders the stage against the other lanes' (stream events only).
@@ -2156,11 +2244,11 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
                 const uint32_t seed = seed0 + t;     // += 1 per bounce (:453, :487)
                 const Queue qin = w->q[b & 1u], qout = w->q[(b + 1u) & 1u];
                 stage_begin(r, ST_SHADE, s, slot);            // :471-480, :502-508
-                // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); PUNCT / ENV as for k_path; TRANS: SPEC §21; EMIS: SPEC §22
-                with_flags([&](auto G, auto P, auto Tr, auto Em) {
-                    auto launch = [&](auto... e) { hipLaunchKernelGGL((k_shade<decltype(G)::value, sizeof...(e) != 0, decltype(P)::value, decltype(Tr)::value, decltype(Em)::value, decltype(e)...>), dim3(pl.shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, sort_queues, e...); };
+                // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); PUNCT / ENV as for k_path; TRANS: SPEC §21; EMIS: SPEC §22; ESAMP: SPEC §23, only with EMIS
+                with_flags([&](auto G, auto P, auto Tr, auto Em, auto Es) {
+                    auto launch = [&](auto... e) { hipLaunchKernelGGL((k_shade<decltype(G)::value, sizeof...(e) != 0, decltype(P)::value, decltype(Tr)::value, decltype(Em)::value, decltype(Em)::value && decltype(Es)::value, decltype(e)...>), dim3(pl.shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, sort_queues, e...); };
                     if (f.env) launch(ev); else launch();
-                }, f.denoise && b == 0u, f.punct, f.trans, f.emis);
+                }, f.denoise && b == 0u, f.punct, f.trans, f.emis, esamp);
                 stage_end(r, s, slot);
                 if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
                 trace(b + 1u < nb ? (int)(b + 1u) : -1, (int)b);

@@ -18,7 +18,9 @@ double texel_lum(const uint8_t *t) {
     return (0.2126 * (t[0] * s) + 0.7152 * (t[1] * s)) + 0.0722 * (t[2] * s);
 }
 
-// Vose's alias method over p[0..n): q[i] = the probability of keeping i, alias[i] = the other outcome of its column
+}  // namespace
+
+// Vose's alias method over p[0..n): q[i] = the probability of keeping i, alias[i] = the other outcome of its column (env_dist.h: SPEC §23's emitters use it too)
 void alias_table(const double *p, uint32_t n, float *q, uint32_t *alias) {
     double total = 0.0;
     for (uint32_t i = 0; i < n; ++i) total += p[i];
@@ -38,8 +40,6 @@ void alias_table(const double *p, uint32_t n, float *q, uint32_t *alias) {
     for (uint32_t i : large) { q[i] = 1.0f; alias[i] = i; }
     for (uint32_t i : small) { q[i] = 1.0f; alias[i] = i; }   // rounding leftovers: their share is 1 within the double's precision
 }
-
-}  // namespace
 
 double env_distribution(const uint8_t *rgbe8, uint32_t W, uint32_t H, EnvDist &out) {
     const size_t n = (size_t)W * H;

@@ -93,7 +93,8 @@ struct DScene {
     const float4 *punctual;
     uint32_t n_punctual;
     // SPEC §20: alpha-masked materials.  alpha_tri[prim] = 0 for an opaque triangle, else 1 + the index of its record {cutoff, color.w, bits of the PLAIN image index
-    // (LPT_INVALID_INDEX: no alpha image), 0}.  Null / 0 for a scene without masks; read only by the MASK instantiations of the traversal (alpha_rejects)
+    // (LPT_INVALID_INDEX: no alpha image), 0}.  Null / 0 for a scene without masks; read only by the MASK instantiations of the traversal (alpha_rejects) and, behind
+    // n_alpha != 0, by emitter_sample (SPEC §23)
     const uint32_t *alpha_tri;
     const float4 *alpha_recs;
     uint32_t n_alpha;
@@ -107,6 +108,12 @@ struct DScene {
     const uint32_t *emis_tri;
     const float4 *emis_recs;
     uint32_t n_emis;
+    // SPEC §23: the emitter distribution, one entry per emissive triangle of non-zero area in prim-id order: {q, bits of the alias slot, bits of the slot's own prim,
+    // bits of the alias slot's prim} — the column of a Vose alias table with both outcomes' triangles in it, so a pick is ONE dependent load.  emit_inv_W = float(1 / sum of
+    // the weights area x lum(Le)).  Null / 0 without a distribution; read only by the ESAMP instantiations of shade_hit / k_shade and by k_emitter_sample
+    const float4 *emit_tab;
+    uint32_t n_emit;
+    float emit_inv_W;
 };
 constexpr uint32_t kPairedBit = 0x40000000u;
 
@@ -1614,6 +1621,75 @@ __global__ __launch_bounds__(kBlock) void k_punctual_sample(DScene sc, uint32_t 
     E_out[j] = E.x; E_out[j + 1u] = E.y; E_out[j + 2u] = E.z;
 }
 
+// ------------------------------------------------------------------ emitter sampling (SPEC §23)
+// One sample on the emissive triangles seen from Po, §23's arithmetic once: (ra, rb) pick the triangle through the alias table (one dependent load, issued first),
+// (r1, r2) place the point on it.  Out: the triangle, the point, the unit direction towards it, the distance, the cosine at the emitter (both sides emit), the area
+// density p_A = lum(Le) x emit_inv_W of the triangle's material and E = Le (x the sRGB emissive image at the point).  false: no sample (`prim` is still the pick) —
+// also where the triangle's alpha mask (SPEC §20) rejects the point.
+struct EmitterSample { uint32_t prim; f3 y, wi, E; float d2, dist, cl, pA; };
+__device__ __forceinline__ bool emitter_sample(const DScene &sc, const float *s_lut, const float ra, const float rb, const float r1, const float r2, const f3 Po, EmitterSample &es) {
+    uint32_t slot = (uint32_t)(ra * (float)sc.n_emit);
+    if (slot > sc.n_emit - 1u) slot = sc.n_emit - 1u;
+    const float4 e = sc.emit_tab[slot];
+    const uint32_t j = rb < e.x ? __float_as_uint(e.z) : __float_as_uint(e.w);
+    es.prim = j;
+    const float4 *tv = sc.tri_verts + kTriRec * (size_t)j;
+    const float4 P0 = tv[0], N0 = tv[1], P1 = tv[2], N1 = tv[3], P2 = tv[4], N2 = tv[5];
+    const uint32_t em = sc.emis_tri[j];
+    if (em == 0u) return false;   // not an emitter: the table never names one
+    const float4 er = sc.emis_recs[em - 1u];
+    const float su = sqrtf(r1);
+    const float u = su * (1.0f - r2), v = su * r2;
+    const float bw = (1.0f - u) - v;
+    // SPEC §20 at the sampled point: a point the emitter's own alpha mask cuts away is no surface — a BSDF ray passes through it —, so it gives no sample
+    // (the shadow ray stops short of the emitter and would never ask).  The area density stays p_A: the share of the cut parts is wasted, as on a black image
+    if (sc.n_alpha != 0u && alpha_rejects(sc, j, u, v)) return false;
+    const f3 p0 = mk3(P0.x, P0.y, P0.z), p1 = mk3(P1.x, P1.y, P1.z), p2 = mk3(P2.x, P2.y, P2.z);
+    es.y = mk3((p0.x * bw + p1.x * u) + p2.x * v, (p0.y * bw + p1.y * u) + p2.y * v, (p0.z * bw + p1.z * u) + p2.z * v);
+    const f3 Ng = cross(p1 - p0, p2 - p0);
+    const float l2 = dot(Ng, Ng);
+    if (!(l2 > 0.0f)) return false;
+    const f3 w = es.y - Po;
+    const float d2 = dot(w, w);
+    if (!(d2 > 0.0f)) return false;
+    es.d2 = d2;
+    es.dist = sqrtf(d2);
+    es.wi = w * (1.0f / es.dist);
+    es.cl = fabsf(dot(Ng, es.wi)) * (1.0f / sqrtf(l2));
+    if (!(es.cl > 0.0f)) return false;
+    es.pA = lum(mk3(er.x, er.y, er.z)) * sc.emit_inv_W;
+    es.E = mk3(er.x, er.y, er.z);
+    const uint32_t etex = __float_as_uint(er.w);
+    if (etex < sc.n_images) {
+        const float tu = (P0.w * bw + P1.w * u) + P2.w * v;
+        const float tvv = (N0.w * bw + N1.w * u) + N2.w * v;
+        const float4 tex = texture_lookup(sc, s_lut, etex, tu, tvv, true);
+        es.E.x *= tex.x; es.E.y *= tex.y; es.E.z *= tex.z;
+    }
+    return true;
+}
+// lpt_scene_gpu_sample_emitter: the function shade_hit runs, one point per thread.  rands: (ra, rb, r1, r2) per point; out: 16 words per point
+// {prim, sampled (1 / 0), y, wi, dist, cl, p_A, E, 0}; a point without a sample keeps its prim and gives zeros
+__global__ __launch_bounds__(kBlock) void k_emitter_sample(DScene sc, const float *points, const float *rands, uint32_t n, uint32_t *out) {
+    __shared__ float s_lut[256];
+    s_lut[threadIdx.x] = sc.srgb_lut[threadIdx.x];  // kBlock == 256
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *pt = points + 3u * (size_t)i, *r = rands + 4u * (size_t)i;
+    EmitterSample es;
+    const bool ok = emitter_sample(sc, s_lut, r[0], r[1], r[2], r[3], mk3(pt[0], pt[1], pt[2]), es);
+    uint32_t *o = out + 16u * (size_t)i;
+    for (uint32_t k = 0; k < 16u; ++k) o[k] = 0u;
+    o[0] = es.prim; o[1] = ok ? 1u : 0u;
+    if (ok) {
+        o[2] = __float_as_uint(es.y.x); o[3] = __float_as_uint(es.y.y); o[4] = __float_as_uint(es.y.z);
+        o[5] = __float_as_uint(es.wi.x); o[6] = __float_as_uint(es.wi.y); o[7] = __float_as_uint(es.wi.z);
+        o[8] = __float_as_uint(es.dist); o[9] = __float_as_uint(es.cl); o[10] = __float_as_uint(es.pA);
+        o[11] = __float_as_uint(es.E.x); o[12] = __float_as_uint(es.E.y); o[13] = __float_as_uint(es.E.z);
+    }
+}
+
 // ------------------------------------------------------------------ transmission (SPEC §21)
 // The smooth dielectric interface event, §21's arithmetic once: d the ray's unit direction, Ns the shading normal, Ngf the geometric normal flipped against d,
 // entering = the geometric normal was not flipped.  Fresnel picks reflection (weight 1) against r4, else the ray refracts — or, thin-walled, goes straight on —
@@ -1728,20 +1804,30 @@ struct ShadeOut {
 // EMIS (SPEC §22): the scene has an emissive material in use; a surface hit on such a triangle adds T x Le (x the emissive image) with weight 1, from either side, on
 // every bounce, before the hit's own light sample — and changes nothing else of the hit.
 struct PunctPick { float p_p, p_pick; };   // the punctual share of the non-probe light samples; the probability with which ONE punctual light is picked
-template <bool ENV>
+// ESAMP (SPEC §23): the emitter set takes p_m = 1/2 of the non-probe light samples from the punctual and rectangle lights, whose pdfs gain the factor 1 - p_m = 1/2
+template <bool ENV, bool ESAMP = false>
 __device__ __forceinline__ PunctPick punct_pick(const DScene &sc) {
     PunctPick pk;
     pk.p_p = (float)sc.n_punctual / (float)(sc.n_punctual + sc.n_lights);
-    pk.p_pick = ((ENV ? 0.5f : 1.0f) * pk.p_p) / (float)sc.n_punctual;
+    pk.p_pick = (((ENV ? 0.5f : 1.0f) * (ESAMP ? 0.5f : 1.0f)) * pk.p_p) / (float)sc.n_punctual;
     return pk;
 }
 // 1 / n of the rectangle lights' pdfs: the probe's half (ENV) and the punctual share (PUNCT) taken off
-template <bool ENV, bool PUNCT>
+template <bool ENV, bool PUNCT, bool ESAMP = false>
 __device__ __forceinline__ float rect_inv_nl(const DScene &sc, const PunctPick &pk) {
-    if (PUNCT) return sc.n_lights ? ((ENV ? 0.5f : 1.0f) * (1.0f - pk.p_p)) / (float)sc.n_lights : 0.0f;
-    return sc.n_lights ? (ENV ? 0.5f : 1.0f) / (float)sc.n_lights : 0.0f;   // ENV: a rectangle light is picked with 1 - p_env = 1/2
+    if (PUNCT) return sc.n_lights ? (((ENV ? 0.5f : 1.0f) * (ESAMP ? 0.5f : 1.0f)) * (1.0f - pk.p_p)) / (float)sc.n_lights : 0.0f;
+    return sc.n_lights ? ((ENV ? 0.5f : 1.0f) * (ESAMP ? 0.5f : 1.0f)) / (float)sc.n_lights : 0.0f;   // ENV: a rectangle light is picked with 1 - p_env = 1/2
 }
-template <bool GBUF, bool ENV, bool PUNCT, bool TRANS = false, bool EMIS = false, typename LoadO, typename AddL>
+// ESAMP (SPEC §23; only with EMIS): emitter sampling is on and the scene has an emitter distribution; next-event estimation also draws on the emissive triangles (two more
+// draws, the share p_m of the non-probe light samples) and an emissive triangle hit by a BSDF ray is MIS-weighted against that strategy.
+// the light pick's number behind the probe's share (§19's rl) and, ESAMP, behind the emitters' share
+template <bool ENV, bool ESAMP>
+__device__ __forceinline__ float light_rl(const float r0, const float p_env, const float p_m) {
+    float rl = ENV ? (r0 - p_env) / (1.0f - p_env) : r0;
+    if (ESAMP) rl = (rl - p_m) / (1.0f - p_m);
+    return rl;
+}
+template <bool GBUF, bool ENV, bool PUNCT, bool TRANS = false, bool EMIS = false, bool ESAMP = false, typename LoadO, typename AddL>
 __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe, const DEnv &ev, const DNoise &nz, const FrameParams &p, const float *s_lut,
                                           const uint32_t bounce, const bool last_bounce, const uint32_t seed_base, const float inv_nl, const PunctPick &pk, const GBufArgs &gb,
                                           const float4 d4, const float4 T4, const float4 h4, LoadO load_o, AddL add_l, ShadeOut &out) {
@@ -1762,7 +1848,7 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
         if (ENV) {
             const float pdf_prev = load_o().w;
             if (pdf_prev >= 0.0f) {   // not a camera ray: the BSDF strategy's MIS weight against the probe's
-                const float pe = ((PUNCT || sc.n_lights) ? 0.5f : 1.0f) * env_pdf(ev, d);
+                const float pe = ((PUNCT || ESAMP || sc.n_lights) ? 0.5f : 1.0f) * env_pdf(ev, d);
                 const float pb2 = pdf_prev * pdf_prev;
                 const float w = pb2 / (pb2 + pe * pe);
                 e = mk3(e.x * w, e.y * w, e.z * w);
@@ -1835,6 +1921,18 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
                     const float4 tex = texture_lookup(sc, s_lut, etex, tu, tvv, true);
                     E.x *= tex.x; E.y *= tex.y; E.z *= tex.z;
                 }
+                if (ESAMP) {   // SPEC §23: the BSDF strategy's weight against the emitter sample that could have found this point; a ray without a pdf keeps weight 1
+                    const float pdf_prev = load_o().w;
+                    if (pdf_prev >= 0.0f) {
+                        const float cl = fabsf(dot(Ng, d));
+                        const float pA = lum(mk3(er.x, er.y, er.z)) * sc.emit_inv_W;
+                        const float p_sel = (ENV ? 0.5f : 1.0f) * ((PUNCT || sc.n_lights) ? 0.5f : 1.0f);
+                        const float pl = (((h4.x * h4.x) / cl) * pA) * p_sel;
+                        const float pb2 = pdf_prev * pdf_prev;
+                        const float w = pb2 / (pb2 + pl * pl);
+                        E = mk3(E.x * w, E.y * w, E.z * w);
+                    }
+                }
                 add_l(T.x * E.x, T.y * E.y, T.z * E.z);
             }
             g_n = Ns; g_P = P;
@@ -1852,7 +1950,10 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
             noise_shift(nz, x, y, seed_counter, r4, r5);
             float r6 = 0.0f, r7 = 0.0f, r8 = 0.0f, r9 = 0.0f;
             if (ENV) { r6 = rng_next(rg); r7 = rng_next(rg); r8 = rng_next(rg); r9 = rng_next(rg); }
-            const float p_env = (PUNCT || sc.n_lights) ? 0.5f : 1.0f;   // ENV: the probe's share of the light samples
+            float ra = 0.0f, rb = 0.0f;   // ESAMP: the alias pick, behind every draw the other modes make
+            if (ESAMP) { ra = rng_next(rg); rb = rng_next(rg); }
+            const float p_env = (PUNCT || ESAMP || sc.n_lights) ? 0.5f : 1.0f;   // ENV: the probe's share of the light samples
+            const float p_m = (PUNCT || sc.n_lights) ? 0.5f : 1.0f;   // ESAMP: the emitters' share of the non-probe light samples
             float am = max2(max2(fabsf(P.x), fabsf(P.y)), fabsf(P.z));
             float eps = 1.0e-4f * (1.0f + am);
             const f3 Po = mk3(P.x + Ng.x * eps, P.y + Ng.y * eps, P.z + Ng.z * eps);
@@ -1910,8 +2011,34 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
                         }
                     }
                 }
-            } else if (PUNCT && (ENV ? (r0 - p_env) / (1.0f - p_env) : r0) < pk.p_p) {   // a punctual light (SPEC §19): a delta light, so MIS weight 1 and no draw beyond r0
-                const float rl = ENV ? (r0 - p_env) / (1.0f - p_env) : r0;
+            } else if (ESAMP && light_rl<ENV, false>(r0, p_env, p_m) < p_m) {   // the emissive triangles (SPEC §23)
+                // the last bounce draws none: a sample there would stand for emission one bounce deeper than §22 adds
+                EmitterSample es;
+                if (!last_bounce && emitter_sample(sc, s_lut, ra, rb, r1, r2, Po, es)) {
+                    Hit hl;
+                    hl.t = es.dist; hl.u = 0.f; hl.v = 0.f; hl.prim = 0xFFFFFFFFu;
+                    intersect_lights(sc, Po, es.wi, hl);   // §19's rule: a rectangle light's front on the segment
+                    if (hl.prim == 0xFFFFFFFFu) {
+                        f3 f;
+                        float pb;
+                        bsdf_eval(sf, Ns, Ng, V, NoV, pspec, es.wi, f, pb);
+                        if (pb > 0.0f) {
+                            const float pl = ((es.d2 / es.cl) * es.pA) * ((ENV ? 0.5f : 1.0f) * p_m);
+                            const float pl2 = pl * pl;
+                            const float wm = pl2 / (pl2 + pb * pb);
+                            const float NoL = dot(Ns, es.wi);
+                            f3 contrib = mk3((T.x * f.x) * (((NoL * es.E.x) * wm) / pl), (T.y * f.y) * (((NoL * es.E.y) * wm) / pl), (T.z * f.z) * (((NoL * es.E.z) * wm) / pl));
+                            if (contrib.x > 0.0f || contrib.y > 0.0f || contrib.z > 0.0f) {
+                                out.want_shadow = true;
+                                out.so4 = make_float4(Po.x, Po.y, Po.z, es.dist * 0.999f);
+                                out.sd4 = make_float4(es.wi.x, es.wi.y, es.wi.z, d4.w);
+                                out.sc4 = make_float4(contrib.x, contrib.y, contrib.z, 0.f);
+                            }
+                        }
+                    }
+                }
+            } else if (PUNCT && light_rl<ENV, ESAMP>(r0, p_env, p_m) < pk.p_p) {   // a punctual light (SPEC §19): a delta light, so MIS weight 1 and no draw beyond r0
+                const float rl = light_rl<ENV, ESAMP>(r0, p_env, p_m);
                 uint32_t li = (uint32_t)((rl / pk.p_p) * (float)sc.n_punctual);
                 if (li > sc.n_punctual - 1u) li = sc.n_punctual - 1u;
                 f3 wi, E;
@@ -1937,7 +2064,7 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
                     }
                 }
             } else if (sc.n_lights) {
-                float rl = ENV ? (r0 - p_env) / (1.0f - p_env) : r0;
+                float rl = light_rl<ENV, ESAMP>(r0, p_env, p_m);
                 if (PUNCT) rl = (rl - pk.p_p) / (1.0f - pk.p_p);
                 uint32_t li = (uint32_t)(rl * (float)sc.n_lights);
                 if (li > sc.n_lights - 1u) li = sc.n_lights - 1u;
@@ -2014,11 +2141,16 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
 #ifndef LPT_SHADE_WAVES_EMIS
 #define LPT_SHADE_WAVES_EMIS(ENV, PUNCT, TRANS) 3
 #endif
-template <bool GBUF, bool ENV = false, bool PUNCT = false, bool TRANS = false, bool EMIS = false, typename... Env>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(EMIS ? LPT_SHADE_WAVES_EMIS(ENV, PUNCT, TRANS) : TRANS ? LPT_SHADE_WAVES_TRANS(ENV, PUNCT) : LPT_SHADE_WAVES(ENV, PUNCT)))) void k_shade(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue qin, const float4 *hits,
+// ESAMP (SPEC §23): the instantiations that run while emitter sampling is on and the scene has an emitter distribution
+#ifndef LPT_SHADE_WAVES_ESAMP
+#define LPT_SHADE_WAVES_ESAMP(ENV, PUNCT, TRANS) 3
+#endif
+template <bool GBUF, bool ENV = false, bool PUNCT = false, bool TRANS = false, bool EMIS = false, bool ESAMP = false, typename... Env>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ESAMP ? LPT_SHADE_WAVES_ESAMP(ENV, PUNCT, TRANS) : EMIS ? LPT_SHADE_WAVES_EMIS(ENV, PUNCT, TRANS) : TRANS ? LPT_SHADE_WAVES_TRANS(ENV, PUNCT) : LPT_SHADE_WAVES(ENV, PUNCT)))) void k_shade(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue qin, const float4 *hits,
                                                   Queue qout, ShadowQueue sq, float4 *Lsum, FrameCounters *ctr, int bounce,
                                                   uint32_t seed_base, GBufArgs gb, int sorted, Env... env) {
     static_assert(sizeof...(Env) == (ENV ? 1u : 0u), "the ENV instantiations take the distribution, the others nothing");
+    static_assert(EMIS || !ESAMP, "emitter sampling (SPEC §23) exists only for a scene with an emissive material in use");
     const DEnv ev = env_arg(env...);
     __shared__ uint32_t lds[72];
     __shared__ float s_lut[256];
@@ -2037,8 +2169,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(EMIS ? L
     const uint32_t rounded = (count + 255u) & ~255u;  // keep whole blocks in the loop for the barriers
     uint32_t n_surface = 0;
     const bool last_bounce = (uint32_t)bounce + 1u >= p.max_bounces;
-    const PunctPick pk = PUNCT ? punct_pick<ENV>(sc) : PunctPick{0.0f, 0.0f};
-    const float inv_nl = rect_inv_nl<ENV, PUNCT>(sc, pk);
+    const PunctPick pk = PUNCT ? punct_pick<ENV, ESAMP>(sc) : PunctPick{0.0f, 0.0f};
+    const float inv_nl = rect_inv_nl<ENV, PUNCT, ESAMP>(sc, pk);
     for (uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x; i0 < rounded; i0 += stride) {
         ShadeOut so;
         so.want_next = false; so.want_shadow = false; so.is_surface = false;
@@ -2046,7 +2178,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(EMIS ? L
         if (i < count) {
             const float4 d4 = ld_nt(qin.d + i), T4 = ld_nt(qin.T + i), h4 = ld_nt(hits + i);
             const uint32_t slot = __float_as_uint(d4.w);
-            shade_hit<GBUF, ENV, PUNCT, TRANS, EMIS>(sc, probe, ev, nz, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, gb, d4, T4, h4,
+            shade_hit<GBUF, ENV, PUNCT, TRANS, EMIS, ESAMP>(sc, probe, ev, nz, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, gb, d4, T4, h4,
                             [&]() { return ld_nt(qin.o + i); },
                             [&](float r, float g, float b) {
                                 float4 L = Lsum[slot];
@@ -2692,11 +2824,11 @@ __global__ __launch_bounds__(64) void k_refit_level(DScene sc, uint4 *nodes_rw, 
 
 // ------------------------------------------------------------------ device-side baking of ONE instance (SPEC §2.5, §6)
 // The object-space mesh stays on the device; a moved instance is re-baked here with exactly the host's operations
-// (bvh.cpp bake_one / woop_from_triangle: fp32 transform with the parentheses shown there, cofactor normals,
+// (bvh.cpp bake_instance / woop_from_triangle: fp32 transform with the parentheses shown there, cofactor normals,
 // Woop maps in binary64 rounded once) — -ffp-contract=off on both sides, so the results are bit-identical.
 struct BakeArgs {
     float m[16];        // model_to_world, column-major
-    float c[9];         // cofactors of its 3x3 part, as bake_one computes them (row-major c00..c22)
+    float c[9];         // cofactors of its 3x3 part, as bake_instance computes them (row-major c00..c22)
     uint32_t vertex_offset, index_offset, first_tri, n_tris;
     float4 mat[2];      // the instance's material (lpt_material verbatim), copied into every shading record
 };
