@@ -152,6 +152,16 @@ impl Scene {
         check(unsafe { ffi::lpt_scene_emitter_distribution(self.h, n, q.as_mut_ptr(), alias.as_mut_ptr(), prim.as_mut_ptr(), prim_alias.as_mut_ptr(), &mut n, &mut total) })?;
         Ok((q, alias, prim, prim_alias, total))
     }
+    /// SPEC.md §24: a tangent-space normal map; `image = None` removes it
+    pub fn set_material_normal_map(&mut self, material: u32, image: Option<u32>, scale: f32) -> Result<(), Error> {
+        check(unsafe { ffi::lpt_scene_set_material_normal_map(self.h, material, image.unwrap_or(ffi::LPT_INVALID_INDEX), scale) })
+    }
+    /// -> (image, scale)
+    pub fn material_normal_map(&self, material: u32) -> Result<(Option<u32>, f32), Error> {
+        let (mut image, mut scale) = (0u32, 0f32);
+        check(unsafe { ffi::lpt_scene_get_material_normal_map(self.h, material, &mut image, &mut scale) })?;
+        Ok((if image == ffi::LPT_INVALID_INDEX { None } else { Some(image) }, scale))
+    }
     /// SPEC.md §19: a point / spot / directional light (KHR_lights_punctual); records from `punctual_light`
     pub fn add_punctual_light(&mut self, light: &ffi::lpt_punctual_light) -> Result<u32, Error> {
         let mut out = 0u32;

@@ -118,6 +118,14 @@ class Scene {  // scene.rs:30-54
         check(lpt_scene_emitter_distribution(h_, cap, q, alias, prim_self, prim_alias, &n, sum_w));
         return n;
     }
+    // SPEC.md §24: normal maps; image = LPT_INVALID_INDEX removes the map
+    struct MaterialNormalMap { uint32_t image; float scale; };
+    void set_material_normal_map(uint32_t material, uint32_t image, float scale = 1.0f) { check(lpt_scene_set_material_normal_map(h_, material, image, scale)); }
+    MaterialNormalMap material_normal_map(uint32_t material) const {
+        MaterialNormalMap m{};
+        check(lpt_scene_get_material_normal_map(h_, material, &m.image, &m.scale));
+        return m;
+    }
     // SPEC.md §19: point / spot / directional lights (KHR_lights_punctual); records from point_light / spot_light / directional_light below
     uint32_t add_punctual_light(const lpt_punctual_light &l) { uint32_t id = 0; check(lpt_scene_add_punctual_light(h_, &l, &id)); return id; }
     void set_punctual_light(uint32_t i, const lpt_punctual_light &l) { check(lpt_scene_set_punctual_light(h_, i, &l)); }
@@ -186,6 +194,10 @@ class SceneGPU {  // scene.rs:56-64,151-188
         check(lpt_scene_gpu_sample_punctual(device.inner(), h_, light, points, n, wi, dist, E));
     }
     // SPEC.md §23: the shading kernels' emitter sample, rands[n][4] = {ra, rb, r1, r2} per point
+    // SPEC.md §24: the shading normal the shading kernels use at (prim, bary) seen along dirs, for tools and tests
+    void shading_normal(const Device &device, uint32_t n, const uint32_t *prim, const float *bary, const float *dirs, float *ns_out, uint32_t *mapped_out) const {
+        check(lpt_scene_gpu_shading_normal(device.inner(), h_, n, prim, bary, dirs, ns_out, mapped_out));
+    }
     void sample_emitter(const Device &device, uint32_t n, const float *points, const float *rands, uint32_t *prim, uint32_t *sampled, float *y, float *wi, float *dist, float *cl,
                         float *p_a, float *E) const {
         check(lpt_scene_gpu_sample_emitter(device.inner(), h_, n, points, rands, prim, sampled, y, wi, dist, cl, p_a, E));

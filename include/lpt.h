@@ -291,6 +291,16 @@ int lpt_scene_get_material_transmission(const lpt_scene *scene, uint32_t materia
 int lpt_scene_set_material_emission(lpt_scene *scene, uint32_t material_index, const float factor[3], float strength, uint32_t image);
 int lpt_scene_get_material_emission(const lpt_scene *scene, uint32_t material_index, float le[3], uint32_t *image);
 
+/* build-only extension (SPEC.md §24; the reference's loader reads no normalTexture): tangent-space normal maps.  A fourth side table
+ * beside the 32-byte lpt_material, no map by default.  A surface hit on a triangle of the material shades with the interpolated normal
+ * perturbed by the linear rgb of `image` at the hit's texture coordinate — x and y times `scale` — in a per-triangle frame made from
+ * the uv derivatives and re-orthogonalised against the interpolated normal (the TANGENT attribute is not read).
+ * image == LPT_INVALID_INDEX removes the map (the getter then reports no image and scale 1).
+ * LPT_ERR_INVALID_ARG, and nothing changed, for a material or image index out of range or a non-finite scale.  The getter's
+ * out-pointers may be NULL. */
+int lpt_scene_set_material_normal_map(lpt_scene *scene, uint32_t material_index, uint32_t image, float scale);
+int lpt_scene_get_material_normal_map(const lpt_scene *scene, uint32_t material_index, uint32_t *image, float *scale);
+
 /* Read-back of the flat arrays (the reference exposes them as pub Vec fields). */
 int lpt_scene_get_materials(const lpt_scene *s, uint32_t first, uint32_t count, lpt_material *dst);
 int lpt_scene_get_entries(const lpt_scene *s, uint32_t first, uint32_t count, lpt_blas_entry *dst);
@@ -388,6 +398,14 @@ int lpt_scene_emitter_distribution(const lpt_scene *scene, uint32_t cap, float *
  * E[n][3] (Le x the emissive image).  LPT_ERR_INVALID_ARG for a scene without a distribution.  Blocking; host arrays. */
 int lpt_scene_gpu_sample_emitter(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const float *points, const float *rands, uint32_t *prim,
                                  uint32_t *sampled, float *y, float *wi, float *dist, float *cl, float *p_a, float *E);
+
+/* build-only extension (SPEC.md §24), for tests and tools in the manner of lpt_scene_gpu_sample_emitter: the shading normal the
+ * shading kernels use at a hit of baked triangle prim[i] at barycentrics bary[i] = (u, v), seen along the unit direction dirs[i] —
+ * §12's normal, run through the kernels' own normal-map function where the triangle's material has a map.  ns_out[n][3]; mapped_out[i]
+ * = 1 where the perturbed normal was taken, 0 where §12's was kept (no map, or one of §24's fallbacks).  Works for any prim below the
+ * scene's baked triangle count (LPT_ERR_INVALID_ARG otherwise); a degenerate triangle gives zeros. */
+int lpt_scene_gpu_shading_normal(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, const float *dirs,
+                                 float *ns_out, uint32_t *mapped_out);
 
 /* build-only extension (SPEC.md §21), for tests and tools in the manner of lpt_probe_sample: the interface event of the shading kernels
  * (kernels.h interface_sample), once per element.  Inputs, n of each: dirs[n][3] the ray's unit direction d, ns[n][3] the shading

@@ -103,6 +103,8 @@ SIGNATURES = {
     "lpt_scene_get_material_transmission": (_i, [_vp, _u32, C.POINTER(_f), C.POINTER(_f), _pu32]),
     "lpt_scene_set_material_emission": (_i, [_vp, _u32, _vp, _f, _u32]),
     "lpt_scene_get_material_emission": (_i, [_vp, _u32, _vp, _pu32]),
+    "lpt_scene_set_material_normal_map": (_i, [_vp, _u32, _u32, _f]),
+    "lpt_scene_get_material_normal_map": (_i, [_vp, _u32, _pu32, C.POINTER(_f)]),
     "lpt_scene_get_materials": (_i, [_vp, _u32, _u32, _vp]),
     "lpt_scene_get_entries": (_i, [_vp, _u32, _u32, _vp]),
     "lpt_scene_get_vertices": (_i, [_vp, _u32, _u32, _vp]),
@@ -126,6 +128,7 @@ SIGNATURES = {
     "lpt_scene_gpu_sample_punctual": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
     "lpt_scene_emitter_distribution": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _pu32, C.POINTER(C.c_double)]),
     "lpt_scene_gpu_sample_emitter": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lpt_scene_gpu_shading_normal": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "lpt_interface_sample": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lpt_probe_upload": (_i, [_vp, _vp, _u32, _u32, _pvp]),
     "lpt_probe_destroy": (_i, [_vp]),

@@ -267,6 +267,20 @@ class Scene:
         out["sum_w"] = total.value
         return out
 
+    # SPEC §24: normal maps; a fourth side table of the materials, no map by default
+    def set_material_normal_map(self, material_index, image, scale=1.0):
+        """a surface hit on a triangle of the material shades with its interpolated normal perturbed by the linear rgb of `image` at the hit (x and y times
+        `scale`), in a per-triangle tangent frame made from the uv derivatives.  image=None removes the map"""
+        _check(A.lib().lpt_scene_set_material_normal_map(self._h, int(material_index), A.INVALID_INDEX if image is None else int(image), float(scale)))
+
+    def material_normal_map(self, material_index):
+        """-> (image index or None, scale)"""
+        image, scale = C.c_uint32(), C.c_float()
+        _check(A.lib().lpt_scene_get_material_normal_map(self._h, int(material_index), C.byref(image), C.byref(scale)))
+        return (None if image.value == A.INVALID_INDEX else int(image.value)), float(scale.value)
+
+    get_material_normal_map = material_normal_map
+
     def _get(self, fn, dt, count):
         out = np.zeros(count, dt)
         _check(fn(self._h, 0, count, A.ptr(out)))
@@ -381,6 +395,19 @@ class SceneGPU:
         wi, dist, E = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
         _check(A.lib().lpt_scene_gpu_sample_punctual(self._dev.inner(), self._h, int(light_index), A.ptr(pts), n, A.ptr(wi), A.ptr(dist), A.ptr(E)))
         return wi, dist, E
+
+    def shading_normal(self, prim, bary, dirs):
+        """The shading normal the shading kernels use (SPEC.md §12, §24) on the GPU: prim[n], bary[n, 2] = (u, v), dirs[n, 3] (unit) -> (Ns[n, 3] float32,
+        mapped[n] bool: the normal map's perturbed normal was taken)."""
+        pr = np.ascontiguousarray(prim, np.uint32).reshape(-1)
+        n = pr.shape[0]
+        ba = np.ascontiguousarray(bary, np.float32).reshape(-1, 2)
+        di = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if ba.shape[0] != n or di.shape[0] != n:
+            raise Error(A.LPT_ERR_INVALID_ARG, "shading_normal: one (u, v) and one direction per prim")
+        ns, mapped = np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+        _check(A.lib().lpt_scene_gpu_shading_normal(self._dev.inner(), self._h, n, A.ptr(pr), A.ptr(ba), A.ptr(di), A.ptr(ns), A.ptr(mapped)))
+        return ns, mapped != 0
 
     def sample_emitter(self, points, rands):
         """The emitter sample the shading kernels run (SPEC.md §23) on the GPU: points[n, 3], rands[n, 4] = (ra, rb, r1, r2) -> a dict of prim[n],

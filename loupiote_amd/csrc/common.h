@@ -44,6 +44,12 @@ struct MaterialEmission {
     bool emissive() const { return le[0] != 0.0f || le[1] != 0.0f || le[2] != 0.0f; }
 };
 
+// SPEC §24: a material's normal map, a fourth side table; no image = no normal map (the default)
+struct MaterialNormalMap {
+    uint32_t image = LPT_INVALID_INDEX;     // the normal image (linear rgb), or none
+    float scale = 1.0f;                     // glTF normalTexture.scale: multiplies the texel's x and y
+};
+
 }  // namespace lpt
 
 // The CPU-side scene: the flat arrays of the reference's Scene / BLASArray
@@ -63,6 +69,8 @@ struct lpt_scene {
     lpt::MaterialTransmission material_transmission(size_t i) const { return i < transmission.size() ? transmission[i] : lpt::MaterialTransmission(); }
     std::vector<lpt::MaterialEmission> emission;   // SPEC §22: side table of `materials`; a material beyond its end is non-emissive (material_emission)
     lpt::MaterialEmission material_emission(size_t i) const { return i < emission.size() ? emission[i] : lpt::MaterialEmission(); }
+    std::vector<lpt::MaterialNormalMap> normal_map;   // SPEC §24: side table of `materials`; a material beyond its end has no normal map (material_normal_map)
+    lpt::MaterialNormalMap material_normal_map(size_t i) const { return i < normal_map.size() ? normal_map[i] : lpt::MaterialNormalMap(); }
 };
 
 namespace lpt {

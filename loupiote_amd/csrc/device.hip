@@ -152,6 +152,7 @@ struct lpt_scene_gpu {
     DevMem trans_tri, trans_recs;   // SPEC §21: the per-triangle table and the records of the transmissive materials (DScene::trans_tri / trans_recs); empty without glass
     DevMem emit_tab;                // SPEC §23: the emitter distribution's entries (DScene::emit_tab); empty without a distribution
     DevMem emis_tri, emis_recs;     // SPEC §22: the per-triangle table and the records of the emissive materials (DScene::emis_tri / emis_recs); empty without emitters
+    DevMem nmap_tri, nmap_recs;     // SPEC §24: the per-triangle table and the records of the normal-mapped materials (DScene::nmap_tri / nmap_recs); empty without normal maps
     DevMem alpha_tri, alpha_recs;   // SPEC §20: the per-triangle table and the records of the masked materials (DScene::alpha_tri / alpha_recs); empty without masks
     TexturePairs pairs;
     lpt_accel_stats stats{};
@@ -667,6 +668,11 @@ static std::vector<uint64_t> pair_textures(const lpt_scene &scene, bool enable, 
         const MaterialEmission e = scene.material_emission(i);
         if (e.emissive() && e.image < scene.images.size()) { referenced[e.image] = 1; alone[e.image] = 1; }
     }
+    // SPEC §24: and a normal image — normal_map looks it up on its own too
+    for (size_t i = 0; i < scene.materials.size(); ++i) {
+        const MaterialNormalMap m = scene.material_normal_map(i);
+        if (m.image < scene.images.size()) { referenced[m.image] = 1; alone[m.image] = 1; }
+    }
     p.image_resident.assign(scene.images.size(), 1);
     for (size_t i = 0; i < scene.images.size(); ++i) p.image_resident[i] = (!referenced[i] || alone[i]) ? 1 : 0;
     return texels;
@@ -951,6 +957,48 @@ static int commit_emit(lpt_scene_gpu *sg, const EmitTable &et) {
     return LPT_OK;
 }
 
+// SPEC §24: the normal-map tables, derived and committed as the emission tables are — one record {bits of the plain image index, scale, 0, 0} per normal-mapped material
+// that an instance with triangles uses, one uint32 per baked triangle (keyed by prim id).  Both empty for a scene without a normal map in use, which then launches what it always launched.
+struct NmapTables { std::vector<float4> recs; std::vector<uint32_t> tri; };
+static int derive_nmap(const lpt_scene_gpu *sg, const lpt_scene &scene, NmapTables &out) {
+    std::vector<uint32_t> rec_of(scene.materials.size(), 0u);   // 1 + record index
+    for (size_t i = 0; i < scene.instances.size() && i < sg->inst_count.size(); ++i) {
+        const uint32_t n = sg->inst_count[i];
+        if (!n) continue;
+        const uint32_t mat = scene.instances[i].material_index < scene.materials.size() ? scene.instances[i].material_index : 0u;   // SPEC §2.5
+        const MaterialNormalMap m = scene.material_normal_map(mat);
+        if (!(m.image < scene.images.size())) continue;
+        if (!rec_of[mat]) {
+            if (!(m.image < sg->pairs.image_resident.size() && sg->pairs.image_resident[m.image]))
+                return fail(LPT_ERR_INVALID_ARG, "material %u now has a normal map whose image was uploaded only as half of an (albedo, mra) pair: upload the scene again", mat);
+            float bits;
+            memcpy(&bits, &m.image, 4);
+            out.recs.push_back(make_float4(bits, m.scale, 0.0f, 0.0f));
+            rec_of[mat] = (uint32_t)out.recs.size();
+        }
+        if (out.tri.empty()) out.tri.assign(std::max(sg->d.n_tris, 1u), 0u);
+        if ((size_t)sg->inst_first[i] + n > out.tri.size()) return fail(LPT_ERR_INVALID_ARG, "instance %zu lies beyond the baked triangles", i);
+        std::fill(out.tri.begin() + sg->inst_first[i], out.tri.begin() + sg->inst_first[i] + n, rec_of[mat]);
+    }
+    return LPT_OK;
+}
+static int commit_nmap(lpt_scene_gpu *sg, const NmapTables &nt) {
+    DScene &d = sg->d;
+    if (nt.recs.empty()) {
+        sg->nmap_tri.reset(); sg->nmap_recs.reset();
+        d.nmap_tri = nullptr; d.nmap_recs = nullptr; d.n_nmap = 0u;
+        return LPT_OK;
+    }
+    hipStream_t s = sg->dev->stream;
+    TRY(upload(sg->nmap_tri, nt.tri, s));
+    TRY(upload(sg->nmap_recs, nt.recs, s));
+    HIP_TRY(hipStreamSynchronize(s));   // the host vectors are the caller's
+    d.nmap_tri = as<const uint32_t>(sg->nmap_tri);
+    d.nmap_recs = as<const float4>(sg->nmap_recs);
+    d.n_nmap = (uint32_t)nt.recs.size();
+    return LPT_OK;
+}
+
 int lpt_scene_upload(lpt_device *dev, const lpt_scene *scene, lpt_scene_gpu **out) { return lpt_scene_upload_ex(dev, scene, LPT_ACCEL_BUILD_HOST_SAH, out); }
 
 int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags, lpt_scene_gpu **out) {
@@ -1053,6 +1101,9 @@ int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags,
         EmitTable em;   // SPEC §23
         TRY(derive_emit(sg.get(), *scene, em));
         TRY(commit_emit(sg.get(), em));
+        NmapTables nt;   // SPEC §24
+        TRY(derive_nmap(sg.get(), *scene, nt));
+        TRY(commit_nmap(sg.get(), nt));
     }
     sg->stats.triangles = d.n_tris;
     sg->stats.node_bytes = (uint32_t)sizeof(Node8);
@@ -1104,6 +1155,8 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
         TRY(derive_emis(sg, *scene, et));
         EmitTable em;   // ... and with it the emitter distribution (SPEC §23: world-space areas)
         TRY(derive_emit(sg, *scene, em));
+        NmapTables nt;    // ... or normal-mapped (SPEC §24)
+        TRY(derive_nmap(sg, *scene, nt));
         // re-bake on the device (the object-space meshes are resident, only the transforms travel); a place-driven scatter then takes the new
         // Woop maps to every place a triangle has in the tree (a split triangle has several)
         DevMem woop_prim;
@@ -1120,6 +1173,7 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
         TRY(commit_trans(sg, tt));
         TRY(commit_emis(sg, et));
         TRY(commit_emit(sg, em));
+        TRY(commit_nmap(sg, nt));
         if (sg->stats.triangles) TRY(refit(sg));
     }
     if (out_rebaked) *out_rebaked = (uint32_t)changed.size();
@@ -1147,6 +1201,9 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
         EmitTable em;   // SPEC §23
         TRY(derive_emit(sg, *scene, em));
         TRY(commit_emit(sg, em));
+        NmapTables nt;   // SPEC §24
+        TRY(derive_nmap(sg, *scene, nt));
+        TRY(commit_nmap(sg, nt));
         return upload_punctual(sg, *scene);
     }
     HIP_TRY(hipSetDevice(sg->dev->ordinal));
@@ -1166,6 +1223,9 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
         EmitTable em;   // ... and the emitter distribution (SPEC §23)
         TRY(derive_emit(sg, *scene, em));
         TRY(commit_emit(sg, em));
+        NmapTables nt;   // ... and their normal maps (SPEC §24)
+        TRY(derive_nmap(sg, *scene, nt));
+        TRY(commit_nmap(sg, nt));
     }
     DevMem woop_prim;
     TRY(dev_alloc(woop_prim, sizeof(WoopTri) * (size_t)n));
@@ -1245,6 +1305,34 @@ int lpt_scene_gpu_sample_emitter(lpt_device *dev, const lpt_scene_gpu *sg, uint3
         memcpy(y + 3u * i, e + 2, 12); memcpy(wi + 3u * i, e + 5, 12);
         memcpy(dist + i, e + 8, 4); memcpy(cl + i, e + 9, 4); memcpy(p_a + i, e + 10, 4);
         memcpy(E + 3u * i, e + 11, 12);
+    }
+    return LPT_OK;
+}
+
+// SPEC §24: the shading normal of the shading kernels (§12's, through kernels.h normal_map where the triangle has a map), once per element, for tests and tools
+int lpt_scene_gpu_shading_normal(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, const float *dirs, float *ns_out, uint32_t *mapped_out) {
+    if (!dev || !sg || (n && (!prim || !bary || !dirs || !ns_out || !mapped_out))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_shading_normal: null");
+    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_shading_normal: the scene belongs to another device");
+    for (uint32_t i = 0; i < n; ++i)
+        if (prim[i] >= sg->d.n_tris) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_shading_normal: element %u names triangle %u of %u", i, prim[i], sg->d.n_tris);
+    if (!n) return LPT_OK;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    DevMem dp, db, dd, dout;
+    TRY(dev_alloc(dp, sizeof(uint32_t) * (size_t)n));
+    TRY(dev_alloc(db, sizeof(float) * 2 * (size_t)n));
+    TRY(dev_alloc(dd, sizeof(float) * 3 * (size_t)n));
+    TRY(dev_alloc(dout, sizeof(uint32_t) * 4 * (size_t)n));
+    HIP_TRY(hipMemcpy(dp.get(), prim, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(db.get(), bary, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dd.get(), dirs, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_shading_normal, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, sg->d, as<const uint32_t>(dp), as<const float>(db), as<const float>(dd), n, as<uint32_t>(dout));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    std::vector<uint32_t> o(4u * (size_t)n);
+    HIP_TRY(hipMemcpy(o.data(), dout.get(), sizeof(uint32_t) * o.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(ns_out + 3u * i, o.data() + 4u * i, 12);
+        mapped_out[i] = o[4u * i + 3u];
     }
     return LPT_OK;
 }
@@ -2178,7 +2266,7 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
         WavefrontFacts f;
         f.n_rays = n_rays; f.n_slots = p.n_slots; f.slot0 = p.slot0; f.n_samples = n_samples; f.cus = (uint32_t)r->dev->compute_units;
         f.solo = solo; f.stats = r->stats; f.denoise = denoise; f.env = env;
-        f.masked = sc.n_alpha != 0u; f.trans = sc.n_trans != 0u; f.emis = sc.n_emis != 0u; f.punct = sc.n_punctual != 0u; f.max_depth = r->sg->stats.max_depth; f.stack_entries = sc.stack_entries;
+        f.masked = sc.n_alpha != 0u; f.trans = sc.n_trans != 0u; f.emis = sc.n_emis != 0u; f.nmap = sc.n_nmap != 0u; f.punct = sc.n_punctual != 0u; f.max_depth = r->sg->stats.max_depth; f.stack_entries = sc.stack_entries;
         f.pixel_rad = 2.0f * th / (float)std::max(r->h, 1u); f.dense = (r->w % r->tile_w == 0u) && (r->h % r->tile_h == 0u); f.block8 = p.block8 != 0u;
         f.lim = KernelLimits{kBlock, kTraceBlock, kTailMax, kCoopWavesPerCu, kPacketBlocksPerCu, kPacketMaxPixelRad};
         const LaunchTuning tune = r->tune;
@@ -2244,11 +2332,11 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
                 const uint32_t seed = seed0 + t;     // += 1 per bounce (:453, :487)
                 const Queue qin = w->q[b & 1u], qout = w->q[(b + 1u) & 1u];
                 stage_begin(r, ST_SHADE, s, slot);            // :471-480, :502-508
-                // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); PUNCT / ENV as for k_path; TRANS: SPEC §21; EMIS: SPEC §22; ESAMP: SPEC §23, only with EMIS
-                with_flags([&](auto G, auto P, auto Tr, auto Em, auto Es) {
-                    auto launch = [&](auto... e) { hipLaunchKernelGGL((k_shade<decltype(G)::value, sizeof...(e) != 0, decltype(P)::value, decltype(Tr)::value, decltype(Em)::value, decltype(Em)::value && decltype(Es)::value, decltype(e)...>), dim3(pl.shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, sort_queues, e...); };
+                // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); PUNCT / ENV as for k_path; TRANS: SPEC §21; EMIS: SPEC §22; ESAMP: SPEC §23, only with EMIS; NMAP: SPEC §24
+                with_flags([&](auto G, auto P, auto Tr, auto Em, auto Es, auto Nm) {
+                    auto launch = [&](auto... e) { hipLaunchKernelGGL((k_shade<decltype(G)::value, sizeof...(e) != 0, decltype(P)::value, decltype(Tr)::value, decltype(Em)::value, decltype(Em)::value && decltype(Es)::value, decltype(Nm)::value, decltype(e)...>), dim3(pl.shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, sort_queues, e...); };
                     if (f.env) launch(ev); else launch();
-                }, f.denoise && b == 0u, f.punct, f.trans, f.emis, esamp);
+                }, f.denoise && b == 0u, f.punct, f.trans, f.emis, esamp, f.nmap);
                 stage_end(r, s, slot);
                 if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
                 trace(b + 1u < nb ? (int)(b + 1u) : -1, (int)b);

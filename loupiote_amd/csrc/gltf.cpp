@@ -287,6 +287,8 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
     std::vector<Glass> glasses;
     struct Emitter { uint32_t material; float factor[3], strength; uint32_t image; };
     std::vector<Emitter> emitters;
+    struct Bump { uint32_t material, image; float scale; };
+    std::vector<Bump> bumps;
     for (size_t i = 0; i < mats.size(); ++i) {
         const Json &pbr = mats[i].at("pbrMetallicRoughness");
         lpt_material m = {{1.f, 1.f, 1.f, 1.f}, 1.f, 1.f, LPT_INVALID_INDEX, LPT_INVALID_INDEX};
@@ -346,6 +348,16 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
             }
             if (jt) e.image = tex_id(*jt);
             if (e.factor[0] * e.strength != 0.f || e.factor[1] * e.strength != 0.f || e.factor[2] * e.strength != 0.f) emitters.push_back(e);
+        }
+        // normalTexture (SPEC §24, §14(10)): the image and its scale go to the side table once the images are decoded (below); its texCoord is not read.
+        // A file without the key touches nothing
+        if (const Json *jn = mats[i].find("normalTexture")) {
+            Bump b{(uint32_t)tmp.materials.size() - 1u, tex_id(*jn), 1.f};
+            if (const Json *js = jn->find("scale")) {
+                if (!js->is_num() || !std::isfinite(js->num) || !std::isfinite((float)js->num)) bad("normalTexture.scale is not a finite number");
+                b.scale = (float)js->num;
+            }
+            if (b.image != LPT_INVALID_INDEX) bumps.push_back(b);
         }
     }
     const Json &nodes = d.js.at("nodes");
@@ -416,6 +428,8 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
         if (lpt_scene_set_material_transmission(&tmp, g.material, g.factor, g.ior, g.thin) != LPT_OK) bad(std::string("KHR_materials_transmission rejected: ") + lpt_last_error());
     for (const Emitter &e : emitters)
         if (lpt_scene_set_material_emission(&tmp, e.material, e.factor, e.strength, e.image) != LPT_OK) bad(std::string("emissive material rejected: ") + lpt_last_error());
+    for (const Bump &b : bumps)
+        if (lpt_scene_set_material_normal_map(&tmp, b.material, b.image, b.scale) != LPT_OK) bad(std::string("normalTexture rejected: ") + lpt_last_error());
     *scene = std::move(tmp);
 }
 

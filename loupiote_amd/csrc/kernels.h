@@ -114,6 +114,11 @@ struct DScene {
     const float4 *emit_tab;
     uint32_t n_emit;
     float emit_inv_W;
+    // SPEC §24: normal-mapped materials.  nmap_tri[prim] = 0 for a triangle without a normal map, else 1 + the index of its record {bits of the PLAIN image index, scale, 0, 0}.
+    // Null / 0 for a scene without a normal-mapped material in use; read only by the NMAP instantiations of shade_hit / k_shade and by k_shading_normal
+    const uint32_t *nmap_tri;
+    const float4 *nmap_recs;
+    uint32_t n_nmap;
 };
 constexpr uint32_t kPairedBit = 0x40000000u;
 
@@ -1690,6 +1695,71 @@ __global__ __launch_bounds__(kBlock) void k_emitter_sample(DScene sc, const floa
     }
 }
 
+// ------------------------------------------------------------------ normal maps (SPEC §24)
+// §24's arithmetic once: nm = 1 + the triangle's record, Nv §12's interpolated normal before either flip, Ngf the geometric normal flipped against d, flip = §12's own
+// decision dot(Nv, Ngf) < 0, e1 / e2 the triangle's edges, (du, dv) the uv deltas along them, (tu, tv) the hit's texture coordinate.  Returns false — and leaves Ns, which
+// comes in as §12's shading normal, untouched — wherever the section says "no perturbation".  Every operation is binary32 with the parentheses of the SPEC.
+__device__ __forceinline__ bool normal_map(const DScene &sc, const float *s_lut, const uint32_t nm, const f3 Nv, const f3 Ngf, const bool flip, const f3 e1, const f3 e2,
+                                           const float du1, const float dv1, const float du2, const float dv2, const float tu, const float tv, f3 &Ns) {
+    const float det = du1 * dv2 - du2 * dv1;
+    if (det == 0.0f || !(fabsf(det) <= 3.402823466e38f)) return false;
+    const float sg = det < 0.0f ? -1.0f : 1.0f;
+    const f3 Tr = (e1 * dv2 - e2 * dv1) * sg, Br = (e2 * du1 - e1 * du2) * sg;
+    f3 Tp = Tr - Nv * dot(Nv, Tr);
+    const float tl2 = dot(Tp, Tp);
+    if (!(tl2 > 0.0f)) return false;
+    Tp = Tp * (1.0f / sqrtf(tl2));
+    f3 Bp = cross(Nv, Tp);
+    if (dot(Bp, Br) < 0.0f) Bp = neg(Bp);
+    const float4 nr = sc.nmap_recs[nm - 1u];
+    const float4 tex = texture_lookup(sc, s_lut, __float_as_uint(nr.x), tu, tv, false);
+    const float nx = (tex.x * 2.0f - 1.0f) * nr.y, ny = (tex.y * 2.0f - 1.0f) * nr.y, nz = tex.z * 2.0f - 1.0f;
+    f3 Nm = (Tp * nx + Bp * ny) + Nv * nz;
+    const float m2 = dot(Nm, Nm);
+    if (!(m2 > 0.0f)) return false;
+    Nm = Nm * (1.0f / sqrtf(m2));
+    if (flip) Nm = neg(Nm);
+    if (!(dot(Nm, Ngf) > 0.0f)) return false;   // the map pushed the normal under the surface
+    Ns = Nm;
+    return true;
+}
+// lpt_scene_gpu_shading_normal: §12's shading normal of a hit (prim, bary) seen along d, through normal_map where the triangle has a map; one element per thread.
+// out: 4 words per element {Ns, mapped (1 / 0)}; a degenerate triangle (l2 = 0) gives zeros
+__global__ __launch_bounds__(kBlock) void k_shading_normal(DScene sc, const uint32_t *prims, const float *bary, const float *dirs, uint32_t n, uint32_t *out) {
+    __shared__ float s_lut[256];
+    s_lut[threadIdx.x] = sc.srgb_lut[threadIdx.x];  // kBlock == 256
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t prim = prims[i];
+    const float hu = bary[2u * (size_t)i], hv = bary[2u * (size_t)i + 1u];
+    const f3 d = mk3(dirs[3u * (size_t)i], dirs[3u * (size_t)i + 1u], dirs[3u * (size_t)i + 2u]);
+    const float4 *tv = sc.tri_verts + kTriRec * (size_t)prim;
+    const float4 P0 = tv[0], N0 = tv[1], P1 = tv[2], N1 = tv[3], P2 = tv[4], N2 = tv[5];
+    const uint32_t nm = sc.n_nmap ? sc.nmap_tri[prim] : 0u;
+    const float bw = (1.0f - hu) - hv;
+    const f3 p0 = mk3(P0.x, P0.y, P0.z), p1 = mk3(P1.x, P1.y, P1.z), p2 = mk3(P2.x, P2.y, P2.z);
+    f3 Ng = cross(p1 - p0, p2 - p0);
+    const float l2 = dot(Ng, Ng);
+    f3 Ns = mk3(0.0f, 0.0f, 0.0f);
+    bool mapped = false;
+    if (l2 > 0.0f) {
+        Ng = Ng * (1.0f / sqrtf(l2));
+        Ns = mk3((N0.x * bw + N1.x * hu) + N2.x * hv, (N0.y * bw + N1.y * hu) + N2.y * hv, (N0.z * bw + N1.z * hu) + N2.z * hv);
+        const float n2 = dot(Ns, Ns);
+        Ns = n2 > 0.0f ? Ns * (1.0f / sqrtf(n2)) : Ng;
+        if (dot(Ng, d) > 0.0f) Ng = neg(Ng);
+        const f3 Nv = Ns;
+        const bool flip = dot(Ns, Ng) < 0.0f;
+        if (flip) Ns = neg(Ns);
+        const float tu = (P0.w * bw + P1.w * hu) + P2.w * hv;
+        const float tvv = (N0.w * bw + N1.w * hu) + N2.w * hv;
+        if (nm != 0u) mapped = normal_map(sc, s_lut, nm, Nv, Ng, flip, p1 - p0, p2 - p0, P1.w - P0.w, N1.w - N0.w, P2.w - P0.w, N2.w - N0.w, tu, tvv, Ns);
+    }
+    uint32_t *o = out + 4u * (size_t)i;
+    o[0] = __float_as_uint(Ns.x); o[1] = __float_as_uint(Ns.y); o[2] = __float_as_uint(Ns.z); o[3] = mapped ? 1u : 0u;
+}
+
 // ------------------------------------------------------------------ transmission (SPEC §21)
 // The smooth dielectric interface event, §21's arithmetic once: d the ray's unit direction, Ns the shading normal, Ngf the geometric normal flipped against d,
 // entering = the geometric normal was not flipped.  Fresnel picks reflection (weight 1) against r4, else the ray refracts — or, thin-walled, goes straight on —
@@ -1827,7 +1897,8 @@ __device__ __forceinline__ float light_rl(const float r0, const float p_env, con
     if (ESAMP) rl = (rl - p_m) / (1.0f - p_m);
     return rl;
 }
-template <bool GBUF, bool ENV, bool PUNCT, bool TRANS = false, bool EMIS = false, bool ESAMP = false, typename LoadO, typename AddL>
+// NMAP (SPEC §24): the scene has a normal-mapped material in use; a surface hit on such a triangle shades with normal_map's Ns — and changes nothing else of the hit.
+template <bool GBUF, bool ENV, bool PUNCT, bool TRANS = false, bool EMIS = false, bool ESAMP = false, bool NMAP = false, typename LoadO, typename AddL>
 __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe, const DEnv &ev, const DNoise &nz, const FrameParams &p, const float *s_lut,
                                           const uint32_t bounce, const bool last_bounce, const uint32_t seed_base, const float inv_nl, const PunctPick &pk, const GBufArgs &gb,
                                           const float4 d4, const float4 T4, const float4 h4, LoadO load_o, AddL add_l, ShadeOut &out) {
@@ -1878,6 +1949,8 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
         const float4 mc = tv[6], mp = tv[7];
         uint32_t em = 0u;   // EMIS: 0, or 1 + the triangle's emission record.  The word depends on `prim` alone, so its load goes out with the record's, not behind the texture taps
         if (EMIS) em = sc.emis_tri[prim];
+        uint32_t nm = 0u;   // NMAP: 0, or 1 + the triangle's normal-map record; as `em`, the word goes out with the record
+        if (NMAP) nm = sc.nmap_tri[prim];
         float bw = (1.0f - hu) - hv;
         const f3 p0 = mk3(P0.x, P0.y, P0.z), p1 = mk3(P1.x, P1.y, P1.z), p2 = mk3(P2.x, P2.y, P2.z);
         f3 P = mk3((p0.x * bw + p1.x * hu) + p2.x * hv, (p0.y * bw + p1.y * hu) + p2.y * hv, (p0.z * bw + p1.z * hu) + p2.z * hv);
@@ -1891,9 +1964,13 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
             Ns = n2 > 0.0f ? Ns * (1.0f / sqrtf(n2)) : Ng;
             const bool entering = !(dot(Ng, d) > 0.0f);   // (read by TRANS only)
             if (dot(Ng, d) > 0.0f) Ng = neg(Ng);
-            if (dot(Ns, Ng) < 0.0f) Ns = neg(Ns);
+            const f3 Nv = Ns;   // (read by NMAP only: §12's normal before the flip)
+            const bool flip = dot(Ns, Ng) < 0.0f;
+            if (flip) Ns = neg(Ns);
             float tu = (P0.w * bw + P1.w * hu) + P2.w * hv;
             float tvv = (N0.w * bw + N1.w * hu) + N2.w * hv;
+            // SPEC §24: behind the divergent branch, and before the material's own taps, so that the edges and the uv deltas are dead by then
+            if (NMAP && nm != 0u) normal_map(sc, s_lut, nm, Nv, Ng, flip, p1 - p0, p2 - p0, P1.w - P0.w, N1.w - N0.w, P2.w - P0.w, N2.w - N0.w, tu, tvv, Ns);
             f3 base = mk3(mc.x, mc.y, mc.z);
             float rough = mp.x, metal = mp.y;
             const uint32_t atex = __float_as_uint(mp.z), mtex = __float_as_uint(mp.w);
@@ -2145,8 +2222,12 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
 #ifndef LPT_SHADE_WAVES_ESAMP
 #define LPT_SHADE_WAVES_ESAMP(ENV, PUNCT, TRANS) 3
 #endif
-template <bool GBUF, bool ENV = false, bool PUNCT = false, bool TRANS = false, bool EMIS = false, bool ESAMP = false, typename... Env>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ESAMP ? LPT_SHADE_WAVES_ESAMP(ENV, PUNCT, TRANS) : EMIS ? LPT_SHADE_WAVES_EMIS(ENV, PUNCT, TRANS) : TRANS ? LPT_SHADE_WAVES_TRANS(ENV, PUNCT) : LPT_SHADE_WAVES(ENV, PUNCT)))) void k_shade(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue qin, const float4 *hits,
+// NMAP (SPEC §24): the instantiations that run while the scene has a normal-mapped material in use
+#ifndef LPT_SHADE_WAVES_NMAP
+#define LPT_SHADE_WAVES_NMAP(ENV, PUNCT, TRANS, EMIS, ESAMP) 3
+#endif
+template <bool GBUF, bool ENV = false, bool PUNCT = false, bool TRANS = false, bool EMIS = false, bool ESAMP = false, bool NMAP = false, typename... Env>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NMAP ? LPT_SHADE_WAVES_NMAP(ENV, PUNCT, TRANS, EMIS, ESAMP) : ESAMP ? LPT_SHADE_WAVES_ESAMP(ENV, PUNCT, TRANS) : EMIS ? LPT_SHADE_WAVES_EMIS(ENV, PUNCT, TRANS) : TRANS ? LPT_SHADE_WAVES_TRANS(ENV, PUNCT) : LPT_SHADE_WAVES(ENV, PUNCT)))) void k_shade(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue qin, const float4 *hits,
                                                   Queue qout, ShadowQueue sq, float4 *Lsum, FrameCounters *ctr, int bounce,
                                                   uint32_t seed_base, GBufArgs gb, int sorted, Env... env) {
     static_assert(sizeof...(Env) == (ENV ? 1u : 0u), "the ENV instantiations take the distribution, the others nothing");
@@ -2178,7 +2259,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(ESAMP ? 
         if (i < count) {
             const float4 d4 = ld_nt(qin.d + i), T4 = ld_nt(qin.T + i), h4 = ld_nt(hits + i);
             const uint32_t slot = __float_as_uint(d4.w);
-            shade_hit<GBUF, ENV, PUNCT, TRANS, EMIS, ESAMP>(sc, probe, ev, nz, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, gb, d4, T4, h4,
+            shade_hit<GBUF, ENV, PUNCT, TRANS, EMIS, ESAMP, NMAP>(sc, probe, ev, nz, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, gb, d4, T4, h4,
                             [&]() { return ld_nt(qin.o + i); },
                             [&](float r, float g, float b) {
                                 float4 L = Lsum[slot];

@@ -254,6 +254,31 @@ int lpt_scene_get_material_emission(const lpt_scene *s, uint32_t material_index,
     return LPT_OK;
 }
 
+// ---- normal maps (SPEC §24): a fourth side table of `materials`, grown on the first write; LPT_INVALID_INDEX removes the map
+int lpt_scene_set_material_normal_map(lpt_scene *s, uint32_t material_index, uint32_t image, float scale) {
+    if (!s) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_normal_map: null");
+    if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_normal_map: material %u of %zu", material_index, s->materials.size());
+    if (!std::isfinite(scale)) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_normal_map: the scale must be finite");
+    if (image != LPT_INVALID_INDEX && image >= s->images.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_normal_map: image %u of %zu", image, s->images.size());
+    if (image == LPT_INVALID_INDEX) {   // no map again: the record is dropped, whatever the scale says
+        if (material_index < s->normal_map.size()) s->normal_map[material_index] = MaterialNormalMap();
+        return LPT_OK;
+    }
+    if (s->normal_map.size() < s->materials.size()) s->normal_map.resize(s->materials.size());
+    s->normal_map[material_index].image = image;
+    s->normal_map[material_index].scale = scale;
+    return LPT_OK;
+}
+
+int lpt_scene_get_material_normal_map(const lpt_scene *s, uint32_t material_index, uint32_t *image, float *scale) {
+    if (!s) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_normal_map: null");
+    if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_normal_map: material %u of %zu", material_index, s->materials.size());
+    const MaterialNormalMap m = s->material_normal_map(material_index);
+    if (image) *image = m.image;
+    if (scale) *scale = m.scale;
+    return LPT_OK;
+}
+
 int lpt_scene_add_image(lpt_scene *s, const uint8_t *rgba8, uint32_t w, uint32_t h, uint32_t *out_index) {
     if (!s || !rgba8 || !w || !h) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_add_image: null or empty");
     Image im;
