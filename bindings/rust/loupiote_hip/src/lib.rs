@@ -361,6 +361,25 @@ impl Renderer {
     pub fn set_seed(&mut self, seed: u32) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_seed(self.h, seed) }) }
     /// `SPEC.md` §18: next-event estimation samples the environment probe too (off by default; frames change with it)
     pub fn set_env_sampling(&mut self, on: bool) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_env_sampling(self.h, on as i32) }) }
+    /// SPEC.md §25: a thin-lens camera — lens radius in world units (0, the default: the pinhole) and the distance of the plane in focus; frames change
+    /// with it, so `reset_accumulation` belongs after the call
+    pub fn set_lens(&mut self, radius: f32, focus_distance: f32) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_lens(self.h, radius, focus_distance) }) }
+    /// (radius, focus distance)
+    pub fn lens(&self) -> Result<(f32, f32), Error> {
+        let (mut r, mut f) = (0f32, 0f32);
+        check(unsafe { ffi::lpt_renderer_get_lens(self.h, &mut r, &mut f) })?;
+        Ok((r, f))
+    }
+    /// SPEC.md §25, for tests and tools: the primary rays of sample `sample` of the next `raytrace` call, `(origins, dirs)` with 3 floats per pixel of the
+    /// full frame (zeros at pixels this rank does not own)
+    pub fn primary_rays(&mut self, view_transform: &[f32; 16], sample: u32) -> Result<(Vec<f32>, Vec<f32>), Error> {
+        let (mut w, mut h) = (0u32, 0u32);
+        check(unsafe { ffi::lpt_renderer_get_size(self.h, &mut w, &mut h) })?;
+        let n = 3 * (w as usize) * (h as usize);
+        let (mut o, mut d) = (vec![0f32; n], vec![0f32; n]);
+        check(unsafe { ffi::lpt_renderer_primary_rays(self.h, view_transform.as_ptr(), sample, o.as_mut_ptr(), d.as_mut_ptr()) })?;
+        Ok((o, d))
+    }
     /// SPEC.md §23: next-event estimation samples the emissive triangles too; off by default
     pub fn set_emissive_sampling(&mut self, on: bool) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_emissive_sampling(self.h, on as i32) }) }
     pub fn emissive_sampling(&self) -> Result<bool, Error> {

@@ -270,6 +270,11 @@ class Renderer {  // renderer.rs:169-811
     // SPEC.md §23: next-event estimation samples the emissive triangles too; off by default
     void set_emissive_sampling(bool on) { check(lpt_renderer_set_emissive_sampling(h_, on ? 1 : 0)); }
     bool emissive_sampling() const { int f = 0; check(lpt_renderer_get_emissive_sampling(h_, &f)); return f != 0; }
+    /// SPEC.md §25: a thin-lens camera — lens radius in world units (0, the default: the pinhole) and the distance of the plane in focus; frames change with it, so reset_accumulation() belongs after the call
+    void set_lens(float radius, float focus_distance = 1.0f) { check(lpt_renderer_set_lens(h_, radius, focus_distance)); }
+    std::pair<float, float> lens() const { float r = 0.f, f = 0.f; check(lpt_renderer_get_lens(h_, &r, &f)); return {r, f}; }
+    /// SPEC.md §25, for tests and tools: the primary rays of sample `sample` of the next raytrace(), 3 floats per pixel of the full frame each (zeros at pixels this rank does not own)
+    void primary_rays(const Mat4 &view_transform, uint32_t sample, float *origins, float *dirs) { check(lpt_renderer_primary_rays(h_, view_transform.data(), sample, origins, dirs)); }
     void set_seed(uint32_t s) { check(lpt_renderer_set_seed(h_, s)); }
     void set_vfov(float radians) { check(lpt_renderer_set_vfov(h_, radians)); }
     /// `weights` (one small integer per rank, the same on every rank; nullptr = equal shares): unequal tile shares, e.g. fewer tiles for the rank that also assembles the frame

@@ -584,6 +584,20 @@ int lpt_renderer_get_env_sampling(const lpt_renderer *r, int *flag);
  * scene has an emitter distribution (an emissive material in use on a triangle with an area); recorded calls are submitted first. */
 int lpt_renderer_set_emissive_sampling(lpt_renderer *r, int flag);
 int lpt_renderer_get_emissive_sampling(const lpt_renderer *r, int *flag);
+/* new (SPEC.md §25): a thin-lens camera.  `radius` >= 0 is the lens radius in world units (0, the default: the pinhole of SPEC.md §11, and
+ * every frame, launch and kernel is what it was, whatever the focus distance); `focus_distance` > 0 (default 1) is the distance of the
+ * plane in focus along the view's forward column, in units of its length.  A point on that plane is seen from the pixel the pinhole sees
+ * it from; a point at depth z spreads over a disc of radius R |1/F - 1/z| in §11's screen coordinates.  A renderer setting, not scene
+ * data (glTF has no such field).  LPT_ERR_INVALID_ARG, with nothing changed, for a negative or non-finite radius and for a focus distance
+ * that is not finite and > 0.  Frames change with the call, so lpt_renderer_reset_accumulation belongs after it; recorded calls are
+ * submitted first.  The getter's out-pointers may be NULL. */
+int lpt_renderer_set_lens(lpt_renderer *r, float radius, float focus_distance);
+int lpt_renderer_get_lens(const lpt_renderer *r, float *radius, float *focus_distance);
+/* build-only extension (SPEC.md §25), for tests and tools in the manner of lpt_scene_gpu_shading_normal: the primary rays of the
+ * renderer's own ray-generation kernel for its current size, shard, seed state, noise texture, vfov and lens, as sample `sample` (< 64)
+ * of the next lpt_renderer_raytrace call would start them.  origins[h][w][3], dirs[h][w][3] in full-frame pixel order, zeros at the
+ * pixels this rank does not own.  Frame state and accumulation are untouched; recorded calls are submitted first.  Blocking; host arrays. */
+int lpt_renderer_primary_rays(lpt_renderer *r, const float view_transform[16], uint32_t sample, float *origins, float *dirs);
 int lpt_renderer_set_seed(lpt_renderer *r, uint32_t user_seed);
 /* vertical field of view in radians (reference: Camera::default inside albedo) */
 int lpt_renderer_set_vfov(lpt_renderer *r, float radians);

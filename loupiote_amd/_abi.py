@@ -177,6 +177,9 @@ SIGNATURES = {
     "lpt_renderer_get_env_sampling": (_i, [_vp, C.POINTER(_i)]),
     "lpt_renderer_set_emissive_sampling": (_i, [_vp, _i]),
     "lpt_renderer_get_emissive_sampling": (_i, [_vp, C.POINTER(_i)]),
+    "lpt_renderer_set_lens": (_i, [_vp, _f, _f]),
+    "lpt_renderer_get_lens": (_i, [_vp, C.POINTER(_f), C.POINTER(_f)]),
+    "lpt_renderer_primary_rays": (_i, [_vp, _vp, _u32, _vp, _vp]),
     "lpt_renderer_set_seed": (_i, [_vp, _u32]),
     "lpt_renderer_set_vfov": (_i, [_vp, _f]),
     "lpt_renderer_set_shard": (_i, [_vp, _u32, _u32, _u32, _u32]),

@@ -652,6 +652,27 @@ class Renderer:
         _check(A.lib().lpt_renderer_get_emissive_sampling(self._h, C.byref(f)))
         return bool(f.value)
 
+    def set_lens(self, radius, focus_distance=1.0):
+        """SPEC.md §25: a thin-lens camera.  `radius` >= 0 in world units (0, the default: the pinhole, and every frame is what it was), `focus_distance` > 0 the
+        distance of the plane in focus along the view's forward column.  Frames change with the call: `reset_accumulation` belongs after it"""
+        _check(A.lib().lpt_renderer_set_lens(self._h, float(radius), float(focus_distance)))
+
+    @property
+    def lens(self):
+        """(radius, focus_distance)"""
+        r, f = C.c_float(), C.c_float()
+        _check(A.lib().lpt_renderer_get_lens(self._h, C.byref(r), C.byref(f)))
+        return r.value, f.value
+
+    def primary_rays(self, view, sample=0):
+        """SPEC.md §25, for tests and tools: (origins, dirs), (h, w, 3) float32 each — the rays the renderer's own ray-generation kernel starts for sample `sample`
+        of the next raytrace() call (current size, shard, seeds, noise texture, vfov, lens); zeros at pixels this rank does not own.  Frame state is untouched"""
+        w, h = self.get_size()
+        v = np.ascontiguousarray(view, np.float32).reshape(16)
+        o, d = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 3), np.float32)
+        _check(A.lib().lpt_renderer_primary_rays(self._h, A.ptr(v), int(sample), A.ptr(o), A.ptr(d)))
+        return o, d
+
     def set_seed(self, s):
         _check(A.lib().lpt_renderer_set_seed(self._h, int(s)))
 

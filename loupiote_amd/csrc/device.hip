@@ -239,6 +239,7 @@ struct lpt_renderer {
     int emissive_sampling = 0; // SPEC §23 (lpt_renderer_set_emissive_sampling): the ESAMP kernels while the bound scene has an emitter distribution
     int env_sampling = 0;      // SPEC §18 (lpt_renderer_set_env_sampling): the ENV kernels while the bound probe has a distribution
     float vfov = 0.78539816339744830962f;
+    float lens_r = 0.0f, lens_f = 1.0f;   // SPEC §25 (lpt_renderer_set_lens): the lens radius (0: the pinhole of §11) and the focus distance
     uint32_t rank = 0, world = 1, tile_w = 32, tile_h = 8;
     std::vector<uint32_t> weights;   // tile-ownership weights of the ranks (empty = every rank 1: tile id mod world)
     ShardMap map{1u, 1u, {0u}};      // this rank's part of the ownership rule
@@ -1885,6 +1886,20 @@ int lpt_renderer_get_emissive_sampling(const lpt_renderer *r, int *flag) {
     *flag = r->emissive_sampling;
     return LPT_OK;
 }
+int lpt_renderer_set_lens(lpt_renderer *r, float radius, float focus_distance) {
+    if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_lens: null");
+    if (!std::isfinite(radius) || radius < 0.0f) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_lens: the radius must be finite and >= 0");
+    if (!std::isfinite(focus_distance) || !(focus_distance > 0.0f)) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_lens: the focus distance must be finite and > 0");
+    FLUSH_OR_RETURN(r);
+    r->lens_r = radius; r->lens_f = focus_distance;
+    return LPT_OK;
+}
+int lpt_renderer_get_lens(const lpt_renderer *r, float *radius, float *focus_distance) {
+    if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_get_lens: null");
+    if (radius) *radius = r->lens_r;
+    if (focus_distance) *focus_distance = r->lens_f;
+    return LPT_OK;
+}
 int lpt_renderer_set_seed(lpt_renderer *r, uint32_t s) {
     if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_seed: null");
     FLUSH_OR_RETURN(r);
@@ -2167,16 +2182,9 @@ struct Ticket {
     std::function<int(uint32_t, const PhaseHooks &)> run;
 };
 
-// First half of a wavefront: the launches of `n_samples` recorded raytrace() calls over the rank's pixel slots
-// [slot0, slot0 + piece_slots) — ray generation, traversal, shading — on the wavefront's lane, from the protocol state the first
-// of the calls saw (frame_count0, seed0, acc0 = its accumulate flag; the later ones ran with accumulate == true by construction).
-// `defer`: the launches are left in tk.run for the caller to enqueue stage by stage; otherwise they are enqueued here.
-static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_samples, uint32_t frame_count0, uint32_t seed0, bool acc0,
-                           uint32_t slot0, uint32_t piece_slots, Ticket &tk, bool solo, bool defer = false) {
-    HIP_TRY(hipSetDevice(r->dev->ordinal));
-    hipStream_t sm = r->stream;                  // accumulation, filter passes, bookkeeping, reads, the exchange: in call order
-    const uint32_t nb = r->max_bounces;          // reference constant 3 (:398-399)
-
+// What the launches of one wavefront read about the frame: the camera of `view`, the renderer's size, seeds, shard and lens, `n_samples` samples over the rank's
+// slots [slot0, slot0 + piece_slots) (wavefront_trace; lpt_renderer_primary_rays runs k_raygen alone from the same record)
+static FrameParams frame_params(const lpt_renderer *r, const float view[16], uint32_t n_samples, uint32_t frame_count0, uint32_t seed0, bool acc0, uint32_t slot0, uint32_t piece_slots) {
     FrameParams p;
     p.right = mk3(view[0], view[1], view[2]);    // camera.rs:101-108: cols = right, up, direction, origin
     p.up = mk3(view[4], view[5], view[6]);
@@ -2195,9 +2203,33 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
     p.block8 = (r->tile_w % 8u == 0u && r->tile_h % 8u == 0u) ? 1u : 0u;
     p.n_slots = piece_slots;                     // the slots of THIS wavefront
     p.frame_count = frame_count0;
-    p.max_bounces = nb;
+    p.max_bounces = r->max_bounces;
     p.n_samples = n_samples;
     p.fc_inc0 = acc0 ? 1u : 0u;
+    // SPEC §25: rn = normalize(right), un = normalize(up), §3's normalize in binary32, once per frame
+    const auto unit = [](f3 a) {
+        const float l2 = (a.x * a.x + a.y * a.y) + a.z * a.z;
+        if (!(l2 > 0.0f)) return mk3(0.0f, 0.0f, 0.0f);
+        const float inv = 1.0f / sqrtf(l2);
+        return mk3(a.x * inv, a.y * inv, a.z * inv);
+    };
+    p.lens_r = r->lens_r; p.lens_f = r->lens_f;
+    p.lens_rn = unit(p.right); p.lens_un = unit(p.up);
+    return p;
+}
+
+// First half of a wavefront: the launches of `n_samples` recorded raytrace() calls over the rank's pixel slots
+// [slot0, slot0 + piece_slots) — ray generation, traversal, shading — on the wavefront's lane, from the protocol state the first
+// of the calls saw (frame_count0, seed0, acc0 = its accumulate flag; the later ones ran with accumulate == true by construction).
+// `defer`: the launches are left in tk.run for the caller to enqueue stage by stage; otherwise they are enqueued here.
+static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_samples, uint32_t frame_count0, uint32_t seed0, bool acc0,
+                           uint32_t slot0, uint32_t piece_slots, Ticket &tk, bool solo, bool defer = false) {
+    HIP_TRY(hipSetDevice(r->dev->ordinal));
+    hipStream_t sm = r->stream;                  // accumulation, filter passes, bookkeeping, reads, the exchange: in call order
+    const uint32_t nb = r->max_bounces;          // reference constant 3 (:398-399)
+
+    const FrameParams p = frame_params(r, view, n_samples, frame_count0, seed0, acc0, slot0, piece_slots);
+    const float th = tanf(0.5f * r->vfov);
     const uint32_t n_rays = p.n_slots * n_samples;
     const bool denoise = r->mode != LPT_BLIT_PATHTRACE;
     // the lane (Wavefront) this call's rays live in: consecutive calls take the lanes in turn; the denoising modes
@@ -2266,7 +2298,7 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
         WavefrontFacts f;
         f.n_rays = n_rays; f.n_slots = p.n_slots; f.slot0 = p.slot0; f.n_samples = n_samples; f.cus = (uint32_t)r->dev->compute_units;
         f.solo = solo; f.stats = r->stats; f.denoise = denoise; f.env = env;
-        f.masked = sc.n_alpha != 0u; f.trans = sc.n_trans != 0u; f.emis = sc.n_emis != 0u; f.nmap = sc.n_nmap != 0u; f.punct = sc.n_punctual != 0u; f.max_depth = r->sg->stats.max_depth; f.stack_entries = sc.stack_entries;
+        f.masked = sc.n_alpha != 0u; f.trans = sc.n_trans != 0u; f.emis = sc.n_emis != 0u; f.nmap = sc.n_nmap != 0u; f.lens = r->lens_r > 0.0f; f.punct = sc.n_punctual != 0u; f.max_depth = r->sg->stats.max_depth; f.stack_entries = sc.stack_entries;
         f.pixel_rad = 2.0f * th / (float)std::max(r->h, 1u); f.dense = (r->w % r->tile_w == 0u) && (r->h % r->tile_h == 0u); f.block8 = p.block8 != 0u;
         f.lim = KernelLimits{kBlock, kTraceBlock, kTailMax, kCoopWavesPerCu, kPacketBlocksPerCu, kPacketMaxPixelRad};
         const LaunchTuning tune = r->tune;
@@ -2306,7 +2338,7 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
                 HIP_TRY(hipMemsetAsync(w->ctr, 0, sizeof(FrameCounters), s));
                 // "ray generation" (:444-448)
                 stage_begin(r, ST_RAYGEN, s, slot);
-                with_flags([&](auto D) { hipLaunchKernelGGL(k_raygen<decltype(D)::value>, dim3(pl.stream_blocks), dim3(kBlock), 0, s, p, nz, w->q[0], w->Lsum, w->ctr); }, f.dense);
+                with_flags([&](auto D, auto L) { hipLaunchKernelGGL((k_raygen<decltype(D)::value, decltype(L)::value>), dim3(pl.stream_blocks), dim3(kBlock), 0, s, p, nz, w->q[0], w->Lsum, w->ctr); }, f.dense, f.lens);   // LENS: SPEC §25
                 stage_end(r, s, slot);
                 if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
                 if (pl.packet) {
@@ -2575,6 +2607,59 @@ int lpt_renderer_raytrace_n(lpt_renderer *r, const float view[16], uint32_t n_sa
     if (st == LPT_OK) st = flush_pending(r);   // still with the explicit batch size: one wavefront, not the automatic spatial cut
     r->max_fused = keep;
     return st;
+}
+
+// SPEC §25, for tests and tools in the manner of lpt_scene_gpu_shading_normal: the renderer's own k_raygen, alone, over the rank's slots, for sample `sample` of the
+// next raytrace() call; its queue comes back to the host and is laid out by pixel.  Buffers of its own: no lane, no frame state, no accumulation is touched.
+int lpt_renderer_primary_rays(lpt_renderer *r, const float view[16], uint32_t sample, float *origins, float *dirs) {
+    if (!r || !view || !origins || !dirs) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_primary_rays: null");
+    if (sample >= 64u) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_primary_rays: sample must be below 64");
+    if (!r->w || !r->h) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_primary_rays: the renderer has no size");
+    FLUSH_OR_RETURN(r);
+    HIP_TRY(hipSetDevice(r->dev->ordinal));
+    uint32_t tiles_x, n_tiles, n_slots;
+    shard_geometry(r, tiles_x, n_tiles, n_slots);
+    const size_t npx = (size_t)r->w * r->h;
+    std::fill(origins, origins + 3u * npx, 0.0f);
+    std::fill(dirs, dirs + 3u * npx, 0.0f);
+    if (!n_slots) return LPT_OK;
+    // the sample-th of consecutive calls: its seeds are max_bounces per call further (record_call); frame_count does not reach k_raygen
+    const FrameParams p = frame_params(r, view, 1u, r->frame_count, r->seed + sample * r->max_bounces, r->accumulate, 0u, n_slots);
+    DevMem qo, qd, qT, lsum, ctr;
+    TRY(dev_alloc(qo, sizeof(float4) * n_slots));
+    TRY(dev_alloc(qd, sizeof(float4) * n_slots));
+    TRY(dev_alloc(qT, sizeof(float4) * n_slots));
+    TRY(dev_alloc(lsum, sizeof(float4) * n_slots));
+    TRY(dev_alloc(ctr, sizeof(FrameCounters)));
+    hipStream_t s = r->stream;
+    HIP_TRY(hipMemsetAsync(ctr.get(), 0, sizeof(FrameCounters), s));
+    const DNoise nz{(const uint8_t *)r->noise, r->noise_w, r->noise_h, (r->use_noise && r->noise) ? 1u : 0u};
+    const Queue q{as<float4>(qo), as<float4>(qd), as<float4>(qT)};
+    const bool dense = (r->w % r->tile_w == 0u) && (r->h % r->tile_h == 0u);
+    const uint32_t blocks = std::min<uint32_t>(div_up(n_slots, kBlock), (uint32_t)r->dev->compute_units * 8u);   // launch_plan.h stream_blocks
+    with_flags([&](auto D, auto L) { hipLaunchKernelGGL((k_raygen<decltype(D)::value, decltype(L)::value>), dim3(blocks), dim3(kBlock), 0, s, p, nz, q, as<float4>(lsum), as<FrameCounters>(ctr)); }, dense, r->lens_r > 0.0f);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    const auto hc = std::make_unique<FrameCounters>();
+    HIP_TRY(hipMemcpy(hc.get(), ctr.get(), sizeof(FrameCounters), hipMemcpyDeviceToHost));
+    const uint32_t n = QC(hc.get(), 0);
+    if (n > n_slots) return fail(LPT_ERR_HIP, "lpt_renderer_primary_rays: k_raygen queued %u rays for %u slots", n, n_slots);
+    std::vector<float4> ho(n), hd(n), hT(n);
+    if (n) {
+        HIP_TRY(hipMemcpy(ho.data(), qo.get(), sizeof(float4) * n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hd.data(), qd.get(), sizeof(float4) * n, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hT.data(), qT.get(), sizeof(float4) * n, hipMemcpyDeviceToHost));
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        uint32_t pxy;
+        memcpy(&pxy, &hT[i].w, 4);   // x | y << 13 | sample << 26
+        const uint32_t x = pxy & 0x1FFFu, y = (pxy >> 13) & 0x1FFFu;
+        if (x >= r->w || y >= r->h) return fail(LPT_ERR_HIP, "lpt_renderer_primary_rays: a queued ray names pixel (%u, %u)", x, y);
+        const size_t at = 3u * ((size_t)y * r->w + x);
+        origins[at] = ho[i].x; origins[at + 1u] = ho[i].y; origins[at + 2u] = ho[i].z;
+        dirs[at] = hd[i].x; dirs[at + 1u] = hd[i].y; dirs[at + 2u] = hd[i].z;
+    }
+    return LPT_OK;
 }
 
 int lpt_renderer_stream(lpt_renderer *r, void **stream) {

@@ -213,6 +213,10 @@ struct FrameParams {
     // consecutive raytrace() calls: seeds advance by max_bounces per sample, frame_count by fc_inc0
     // after the first sample and by 1 after every later one.  Virtual slot = sample * n_slots + slot.
     uint32_t n_samples, fc_inc0;
+    // SPEC §25 (lpt_renderer_set_lens): the lens radius R (0: the pinhole of §11; no kernel reads the rest then), the focus distance F in units of |fwd|,
+    // and rn = normalize(right), un = normalize(up), computed once per frame on the host in binary32.  Read by k_raygen<.., LENS> alone
+    float lens_r, lens_f;
+    f3 lens_rn, lens_un;
 };
 
 // streaming accesses (ray queues, hit records): the `nt` hint keeps the ~400 MB that stream through a frame from
@@ -344,7 +348,11 @@ __device__ __forceinline__ void noise_shift(const DNoise &nz, uint32_t x, uint32
 // ------------------------------------------------------------------ ray generation
 // DENSE: every slot maps to a pixel (image is a whole number of tiles) -> queue index = slot and
 // qcount[0] is simply the slot count; otherwise invalid slots are compacted away.
-template <bool DENSE>
+// LENS (SPEC §25): the lens is open (R > 0).  Two more draws of the pixel's stream behind jx, jy (no blue-noise shift) pick a point of the lens disc — the
+// polar map with a correctly rounded square root and §5's sincos2pi —, the ray starts there (q.o holds o' instead of the shared origin) and runs through the
+// point the pinhole ray reaches on the focal plane, origin + dir F.  The consumers of a lens frame read the origin from the queue (launch_plan.h keeps it off
+// k_trace_packet and k_path, which rest on the shared origin); the LENS = false instantiations are the kernels of every frame before the feature.
+template <bool DENSE, bool LENS = false>
 __global__ __launch_bounds__(kBlock) void k_raygen(FrameParams p, DNoise nz, Queue q, float4 *Lsum, FrameCounters *ctr) {
     __shared__ uint32_t lds[8];
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -358,7 +366,7 @@ __global__ __launch_bounds__(kBlock) void k_raygen(FrameParams p, DNoise nz, Que
         uint32_t x = 0, y = 0;
         const bool valid = vslot < total && slot_to_pixel(p, p.slot0 + slot, x, y);
         if (vslot < total) Lsum[vslot] = make_float4(0.f, 0.f, 0.f, 0.f);
-        f3 d = mk3(0.f, 0.f, 0.f);
+        f3 d = mk3(0.f, 0.f, 0.f), o = p.origin;
         if (valid) {
             const uint32_t pixel = y * p.width + x;
             Rng r = rng_init(pixel, stage_seed(p.user_seed, seed_counter), LPT_TAG_RAYGEN);
@@ -370,11 +378,21 @@ __global__ __launch_bounds__(kBlock) void k_raygen(FrameParams p, DNoise nz, Que
             float cy = (1.0f - 2.0f * sy) * p.ay;
             f3 dir = mk3((p.right.x * cx + p.up.x * cy) + p.fwd.x, (p.right.y * cx + p.up.y * cy) + p.fwd.y,
                          (p.right.z * cx + p.up.z * cy) + p.fwd.z);
-            d = normalize(dir);
+            if (LENS) {
+                const float lx = rng_next(r), ly = rng_next(r);   // the third and fourth draws: never shifted by the noise texture
+                const float rr = sqrtf(lx);
+                float sn, cs;
+                sincos2pi(ly, sn, cs);
+                const float a = (p.lens_r * rr) * cs, b = (p.lens_r * rr) * sn;
+                const f3 off = mk3(p.lens_rn.x * a + p.lens_un.x * b, p.lens_rn.y * a + p.lens_un.y * b, p.lens_rn.z * a + p.lens_un.z * b);
+                o = p.origin + off;
+                d = normalize(dir * p.lens_f - off);
+            } else
+                d = normalize(dir);
         }
         const uint32_t idx = DENSE ? vslot : block_compact(valid, &QC(ctr, 0), lds);
         if (valid) {
-            st_nt(q.o + idx, make_float4(p.origin.x, p.origin.y, p.origin.z, -1.0f));
+            st_nt(q.o + idx, make_float4(o.x, o.y, o.z, -1.0f));
             st_nt(q.d + idx, make_float4(d.x, d.y, d.z, __uint_as_float(vslot)));
             q.T[idx] = make_float4(1.f, 1.f, 1.f, __uint_as_float(x | (y << 13) | (sample << 26)));  // pixel + sample ride along: no divisions in k_shade
         }

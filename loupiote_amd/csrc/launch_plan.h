@@ -48,6 +48,7 @@ struct WavefrontFacts {
     bool masked = false, trans = false, punct = false, env = false;   // SPEC §20, §21, §19, §18
     bool emis = false;                // SPEC §22: an emissive material is in use
     bool nmap = false;                // SPEC §24: a normal-mapped material is in use
+    bool lens = false;                // SPEC §25: the renderer's lens is open (R > 0): every primary ray has an origin of its own
     uint32_t max_depth = 0, stack_entries = 0;   // the tree's depth / per-lane stack capacity
     float pixel_rad = 0.0f;           // angle per pixel (2 tan(vfov / 2) / height)
     bool dense = false, block8 = false;   // whole tiles only / 8x8-pixel blocks inside the tiles
@@ -79,6 +80,8 @@ struct LaunchPlan {
 //   trans (a transmissive material used) | path (k_path's instantiations do not double); k_shade<.., TRANS>| SPEC §21
 //   emis (an emissive material used)     | path (k_path's instantiations do not double); k_shade<.., EMIS> | SPEC §22
 //   nmap (a normal-mapped material used) | path (k_path's instantiations do not double); k_shade<.., NMAP> | SPEC §24
+//   lens (the lens radius R > 0)         | packet, path: k_trace_packet rests on ONE origin per packet and  | SPEC §25
+//                                        | k_path reads the shared origin; k_raygen<.., LENS> fills q.o    |
 //   coop-all (n_rays <= coop_rays)       | path                                                            | DESIGN §5.5
 //   tail (solo, n_rays <= budget_rays)   | budget (nothing is dropped, so nothing to re-trace)             | DESIGN §5.5
 //   env, punct                           | nothing: they pick the ENV / PUNCT forms of k_shade and k_path  | SPEC §18, §19
@@ -105,7 +108,7 @@ inline LaunchPlan plan_wavefront(const LaunchTuning &t, const WavefrontFacts &f)
     // for rays that need 14.9 each, and the walk runs at 11.5 Grays/s against 6.2 per ray; at 240x135 the same patch spans eight times the
     // angle, the walk visits several times the nodes, and the packet launch is a third of the frame (0.43 of 1.37 ms; 0.39 ms at 480x270,
     // where the per-ray launch needs 0.13).  LPT_OPT_PACKET_PRIMARY 2 (default): packets up to 1.8 mrad per pixel; 1: always; 0: never.
-    pl.packet = !f.masked && (t.packet_primary == 1u || (t.packet_primary == 2u && f.pixel_rad <= k.kPacketMaxPixelRad));
+    pl.packet = !f.masked && !f.lens && (t.packet_primary == 1u || (t.packet_primary == 2u && f.pixel_rad <= k.kPacketMaxPixelRad));
     if (pl.packet) {
         pl.packet_blocks = std::min(div_up(n_rays, 64u), cus * k.kPacketBlocksPerCu);
         pl.packet_lds = (48u + 7u * f.max_depth + 8u) * (uint32_t)sizeof(uint32_t);
@@ -128,7 +131,7 @@ inline LaunchPlan plan_wavefront(const LaunchTuning &t, const WavefrontFacts &f)
     // k_trace_coop's grid: a wave per ray of both queues, or a wave per straggler of a budgeted launch (most waves of that grid find none and leave at once)
     pl.coop_blocks = pl.coop_all ? std::min(2u * n_rays, cus * k.kCoopWavesPerCu) : (pl.budget ? cus * k.kCoopWavesPerCu : 0u);
     // A small wavefront (the tile shard of a multi-GPU frame): every bounce behind the primary hits in ONE persistent launch (k_path); the primary hits are there, whichever kernel found them
-    pl.path = !f.masked && !f.trans && !f.emis && !f.nmap && t.path_rays && n_rays <= t.path_rays && !pl.coop_all;
+    pl.path = !f.masked && !f.trans && !f.emis && !f.nmap && !f.lens && t.path_rays && n_rays <= t.path_rays && !pl.coop_all;
     if (pl.path) pl.path_blocks = std::min<uint32_t>(div_up(n_rays, k.kTraceBlock), std::max(8u, (cus * t.path_waves_per_cu) & ~7u));
     pl.variant = f.masked ? (f.stats ? TraceVariant::StatsMask : TraceVariant::Mask)
                : pl.tail  ? (pl.pipe ? TraceVariant::PipeTail : TraceVariant::Tail)
