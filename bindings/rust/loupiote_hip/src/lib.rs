@@ -74,6 +74,14 @@ impl Device {
         })?;
         Ok((wi, weight, kind))
     }
+    /// the shading kernels' BSDF on the GPU (SPEC.md §10), once per element: rows of {base, roughness, metallic, N, Ng, V, L, r3, r4, r5} ->
+    /// (rows of {pspec, f, pdf, L_s, weight, pdf_s}, ok: 1 where the sample exists)
+    pub fn bsdf_probe(&self, rows: &[[f32; 20]]) -> Result<(Vec<[f32; 12]>, Vec<u32>), Error> {
+        let n = rows.len();
+        let (mut out, mut ok) = (vec![[0f32; 12]; n], vec![0u32; n]);
+        check(unsafe { ffi::lpt_bsdf_probe(self.h(), n as u32, rows.as_ptr() as *const f32, out.as_mut_ptr() as *mut f32, ok.as_mut_ptr()) })?;
+        Ok((out, ok))
+    }
 }
 
 /// reference `crates/lib/src/scene.rs:30-54` `Scene` (`Scene::default()` seeds one dummy element per array)

@@ -36,6 +36,8 @@ class Device {  // device.rs:72-141
                           const uint32_t *thin, const float *r4, float *wi, float *weight, uint32_t *kind) const {
         check(lpt_interface_sample(h_, n, dirs, ns, ngf, entering, base, ior, thin, r4, wi, weight, kind));
     }
+    /// SPEC.md §10, the shading kernels' BSDF on the GPU, once per element: in[n][20] -> out[n][12], ok[n] (see lpt_bsdf_probe)
+    void bsdf_probe(uint32_t n, const float *in, float *out, uint32_t *ok) const { check(lpt_bsdf_probe(h_, n, in, out, ok)); }
 
    private:
     lpt_device *h_ = nullptr;

@@ -415,6 +415,14 @@ int lpt_scene_gpu_shading_normal(lpt_device *dev, const lpt_scene_gpu *sg, uint3
 int lpt_interface_sample(lpt_device *dev, uint32_t n, const float *dirs, const float *ns, const float *ngf, const uint32_t *entering,
                          const float *base, const float *ior, const uint32_t *thin, const float *r4, float *wi, float *weight, uint32_t *kind);
 
+/* build-only extension (SPEC.md §10), for tests and tools in the manner of lpt_interface_sample: the BSDF of the shading kernels
+ * (device_math.h), once per element, set up as a surface hit sets it up: make_surface, NoV = max(dot(N, V), LPT_MIN_NOV),
+ * spec_probability; then bsdf_eval at L and bsdf_sample with the draws (r3, r4, r5).  in[n][20] = {base[3], roughness, metallic,
+ * N[3] the shading normal, Ng[3] the geometric normal, V[3] the unit direction towards the viewer, L[3] the unit direction to
+ * evaluate, r3, r4, r5}.  out[n][12] = {pspec, f[3], pdf (of L), L_s[3] the sampled direction, weight[3], pdf_s (of L_s)};
+ * ok[n] = 1 where the sample exists, else 0 and its five outputs are zero.  Blocking; host arrays. */
+int lpt_bsdf_probe(lpt_device *dev, uint32_t n, const float *in, float *out, uint32_t *ok);
+
 /* replaces: ProbeGPU::new(device, queue, data, width, height)
  * (crates/lib/src/scene.rs:72-121): 4 bytes/pixel RGBE8, equirectangular. */
 int lpt_probe_upload(lpt_device *dev, const uint8_t *rgbe8, uint32_t width, uint32_t height,

@@ -130,6 +130,7 @@ SIGNATURES = {
     "lpt_scene_gpu_sample_emitter": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lpt_scene_gpu_shading_normal": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "lpt_interface_sample": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lpt_bsdf_probe": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "lpt_probe_upload": (_i, [_vp, _vp, _u32, _u32, _pvp]),
     "lpt_probe_destroy": (_i, [_vp]),
     "lpt_env_distribution": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),

@@ -79,6 +79,15 @@ class Device:
                                             A.ptr(wi), A.ptr(weight), A.ptr(kind)))
         return wi, weight, kind
 
+    def bsdf_probe(self, rows):
+        """The BSDF of the shading kernels (SPEC.md §10) on the GPU, once per element: rows [n, 20] = {base[3], roughness, metallic, N[3], Ng[3],
+        V[3], L[3], r3, r4, r5} -> (out[n, 12] = {pspec, f[3], pdf, L_s[3], weight[3], pdf_s}, ok[n])."""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 20)
+        n = rows.shape[0]
+        out, ok = np.zeros((n, 12), np.float32), np.zeros(n, np.uint32)
+        _check(A.lib().lpt_bsdf_probe(self._h, n, A.ptr(rows), A.ptr(out), A.ptr(ok)))
+        return out, ok
+
     def close(self):
         if self._h:
             A.lib().lpt_device_destroy(self._h)

@@ -1368,6 +1368,29 @@ int lpt_interface_sample(lpt_device *dev, uint32_t n, const float *dirs, const f
     return LPT_OK;
 }
 
+// SPEC §10: the BSDF of the shading kernels as shade_hit sets it up (device_math.h make_surface, spec_probability, bsdf_eval, bsdf_sample), once per element,
+// for tests and tools.  The host rows are the kernel's words already: 20 in, 12 floats + ok out
+int lpt_bsdf_probe(lpt_device *dev, uint32_t n, const float *in, float *out, uint32_t *ok) {
+    if (!dev || (n && (!in || !out || !ok))) return fail(LPT_ERR_INVALID_ARG, "lpt_bsdf_probe: null");
+    if (!n) return LPT_OK;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    DevMem din, dout;
+    TRY(dev_alloc(din, sizeof(uint32_t) * 20u * (size_t)n));
+    TRY(dev_alloc(dout, sizeof(uint32_t) * 13u * (size_t)n));
+    HIP_TRY(hipMemcpy(din.get(), in, sizeof(uint32_t) * 20u * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_bsdf_probe, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, as<const uint32_t>(din), n, as<uint32_t>(dout));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    std::vector<uint32_t> res(13u * (size_t)n);
+    HIP_TRY(hipMemcpy(res.data(), dout.get(), sizeof(uint32_t) * res.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t *e = res.data() + 13u * i;
+        memcpy(out + 12u * i, e, 20); memcpy(out + 12u * i + 5u, e + 6, 28);   // {pspec, f, pdf}, then {L_s, weight, pdf_s}
+        ok[i] = e[5];
+    }
+    return LPT_OK;
+}
+
 // ============================================================================ ProbeGPU
 int lpt_probe_upload(lpt_device *dev, const uint8_t *rgbe8, uint32_t w, uint32_t h, lpt_probe **out) {
     if (!dev || !rgbe8 || !w || !h || !out) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_upload: null or empty");

@@ -154,8 +154,12 @@ __device__ __forceinline__ void bsdf_eval(const Surface &s, f3 N, f3 Ng, f3 V, f
     f.y = (s.diff.y * LPT_INV_PI) * (1.0f - F.y) + dv * F.y;
     f.z = (s.diff.z * LPT_INV_PI) * (1.0f - F.z) + dv * F.z;
     float pdf_d = NoL * LPT_INV_PI;
-    float pdf_s = VoH > 0.0f ? (D * NoH) / (4.0f * VoH) : 0.0f;
+    float pdf_s = (D * NoH) / (4.0f * VoH);   // VoH = 0: discarded below
     pdf = pspec * pdf_s + (1.0f - pspec) * pdf_d;
+    if (!(VoH > 0.0f)) {   // L = -V, or V + L so short that its rounding decides the sign: no half vector, no lobe (SPEC §10)
+        f = mk3(0.0f, 0.0f, 0.0f);
+        pdf = 0.0f;
+    }
 }
 __device__ __forceinline__ bool bsdf_sample(const Surface &s, f3 N, f3 Ng, f3 V, float NoV, float pspec, float r3, float r4, float r5,
                                             f3 &Lout, f3 &weight, float &pdf) {

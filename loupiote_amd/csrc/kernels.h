@@ -1822,6 +1822,30 @@ __global__ __launch_bounds__(kBlock) void k_interface_sample(const uint32_t *in,
     o[3] = __float_as_uint(io.weight.x); o[4] = __float_as_uint(io.weight.y); o[5] = __float_as_uint(io.weight.z);
     o[6] = io.transmit ? 1u : 0u;
 }
+// lpt_bsdf_probe: §10 as shade_hit sets it up (make_surface, the clamped NoV, spec_probability), then bsdf_eval on L and bsdf_sample on (r3, r4, r5); one element per
+// thread.  in: 20 words per element {base, roughness, metallic, N, Ng, V, L, r3, r4, r5}; out: 13 words {pspec, f, pdf, ok, L_s, weight, pdf_s} (a failed sample: zeros)
+__global__ __launch_bounds__(kBlock) void k_bsdf_probe(const uint32_t *in, uint32_t n, uint32_t *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t *e = in + 20u * (size_t)i;
+    auto g = [&](uint32_t k) { return __uint_as_float(e[k]); };
+    const f3 N = mk3(g(5), g(6), g(7)), Ng = mk3(g(8), g(9), g(10)), V = mk3(g(11), g(12), g(13));
+    const Surface sf = make_surface(mk3(g(0), g(1), g(2)), g(3), g(4));
+    const float NoV = max2(dot(N, V), LPT_MIN_NOV);
+    const float pspec = spec_probability(sf, NoV);
+    f3 f, Ls = mk3(0.0f, 0.0f, 0.0f), w = mk3(0.0f, 0.0f, 0.0f);
+    float pdf, pdf_s = 0.0f;
+    bsdf_eval(sf, N, Ng, V, NoV, pspec, mk3(g(14), g(15), g(16)), f, pdf);
+    const bool ok = bsdf_sample(sf, N, Ng, V, NoV, pspec, g(17), g(18), g(19), Ls, w, pdf_s);
+    uint32_t *o = out + 13u * (size_t)i;
+    o[0] = __float_as_uint(pspec);
+    o[1] = __float_as_uint(f.x); o[2] = __float_as_uint(f.y); o[3] = __float_as_uint(f.z);
+    o[4] = __float_as_uint(pdf);
+    o[5] = ok ? 1u : 0u;
+    o[6] = __float_as_uint(Ls.x); o[7] = __float_as_uint(Ls.y); o[8] = __float_as_uint(Ls.z);
+    o[9] = __float_as_uint(w.x); o[10] = __float_as_uint(w.y); o[11] = __float_as_uint(w.z);
+    o[12] = __float_as_uint(pdf_s);
+}
 
 // ------------------------------------------------------------------ SPEC §15 helpers (denoiser path)
 __device__ __forceinline__ uint32_t oct_encode(f3 n) {

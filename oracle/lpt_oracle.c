@@ -574,8 +574,11 @@ static inline void bsdf_eval(const surf_t *s, v3 N, v3 Ng, v3 V, float NoV, floa
     f->y = (s->diff.y * ORC_INV_PI) * (1.0f - F.y) + dv * F.y;
     f->z = (s->diff.z * ORC_INV_PI) * (1.0f - F.z) + dv * F.z;
     float pdf_d = NoL * ORC_INV_PI;
-    float pdf_s = VoH > 0.0f ? (D * NoH) / (4.0f * VoH) : 0.0f;
+    float pdf_s = (D * NoH) / (4.0f * VoH); /* VoH = 0: discarded below */
     *pdf = pspec * pdf_s + (1.0f - pspec) * pdf_d;
+    if (!(VoH > 0.0f)) { /* L = -V, or V + L so short that its rounding decides the sign: no half vector, no lobe */
+        *f = V3(0.0f, 0.0f, 0.0f); *pdf = 0.0f;
+    }
 }
 static inline int bsdf_sample(const surf_t *s, v3 N, v3 Ng, v3 V, float NoV, float pspec, float r3, float r4, float r5,
                               v3 *Lout, v3 *weight, float *pdf) {
@@ -628,6 +631,24 @@ int orc_bsdf_sample(const float base[3], float roughness, float metallic, const 
     int ok = bsdf_sample(&s, n, V3(Ng[0], Ng[1], Ng[2]), v, NoV, ps, r3, r4, r5, &l, &w, pdf);
     if (ok) { L[0] = l.x; L[1] = l.y; L[2] = l.z; weight[0] = w.x; weight[1] = w.y; weight[2] = w.z; }
     return ok;
+}
+/* batched twin of the device hook lpt_bsdf_probe: in[n][20] = {base, roughness, metallic, N, Ng, V, L, r3, r4, r5} ->
+ * out[n][12] = {pspec, f, pdf, L_s, weight, pdf_s}, ok[n] (a failed sample: zeros) */
+void orc_bsdf_probe(uint32_t n, const float *in, float *out, uint32_t *ok) {
+    for (uint32_t i = 0; i < n; ++i) {
+        const float *e = in + 20u * (size_t)i;
+        float *o = out + 12u * (size_t)i;
+        surf_t s = make_surface(e, e[3], e[4]);
+        v3 N = V3(e[5], e[6], e[7]), Ng = V3(e[8], e[9], e[10]), V = V3(e[11], e[12], e[13]);
+        float NoV = fmax2(dot3(N, V), ORC_MIN_NOV);
+        float ps = spec_probability(&s, NoV);
+        v3 f, l = V3(0.0f, 0.0f, 0.0f), w = V3(0.0f, 0.0f, 0.0f);
+        float pdf, pdf_s = 0.0f;
+        bsdf_eval(&s, N, Ng, V, NoV, ps, V3(e[14], e[15], e[16]), &f, &pdf);
+        ok[i] = (uint32_t)bsdf_sample(&s, N, Ng, V, NoV, ps, e[17], e[18], e[19], &l, &w, &pdf_s);
+        o[0] = ps; o[1] = f.x; o[2] = f.y; o[3] = f.z; o[4] = pdf;
+        o[5] = l.x; o[6] = l.y; o[7] = l.z; o[8] = w.x; o[9] = w.y; o[10] = w.z; o[11] = pdf_s;
+    }
 }
 
 /* ------------------------------------------------------------------ SPEC §11 camera */

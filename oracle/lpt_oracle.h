@@ -116,6 +116,9 @@ void orc_bsdf_eval(const float base[3], float roughness, float metallic, const f
 /* samples L from (r3,r4,r5); returns 0 when the path terminates */
 int orc_bsdf_sample(const float base[3], float roughness, float metallic, const float N[3], const float Ng[3],
                     const float V[3], float r3, float r4, float r5, float L[3], float weight[3], float *pdf);
+/* the two above, batched and set up as a surface hit sets them up (the device hook lpt_bsdf_probe's twin): in[n][20] = {base[3],
+ * roughness, metallic, N[3], Ng[3], V[3], L[3], r3, r4, r5} -> out[n][12] = {pspec, f[3], pdf, L_s[3], weight[3], pdf_s}, ok[n] */
+void orc_bsdf_probe(uint32_t n, const float *in, float *out, uint32_t *ok);
 void orc_env_lookup(const orc_scene *s, const float d[3], float rgb[3]);
 void orc_texture_lookup(const orc_scene *s, uint32_t image, float u, float v, int srgb, float rgba[4]);
 float orc_srgb_lut(uint32_t i);

@@ -105,6 +105,7 @@ def lib(path=None):
         L.orc_bsdf_eval.argtypes = [vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, f32p]
         L.orc_bsdf_sample.restype = C.c_int
         L.orc_bsdf_sample.argtypes = [vp, C.c_float, C.c_float, vp, vp, vp, C.c_float, C.c_float, C.c_float, vp, vp, f32p]
+        L.orc_bsdf_probe.argtypes = [u32, vp, vp, vp]
         L.orc_env_lookup.argtypes = [vp, vp, vp]
         L.orc_texture_lookup.argtypes = [vp, u32, C.c_float, C.c_float, C.c_int, vp]
         L.orc_srgb_lut.restype = C.c_float
@@ -292,3 +293,13 @@ def raygen(width, height, view, vfov, x, y, user_seed=0, seed_counter=0):
     d = (C.c_float * 3)()
     lib().orc_raygen(C.byref(p), x, y, o, d)
     return np.array(o[:], np.float32), np.array(d[:], np.float32)
+
+
+def bsdf_probe(rows):
+    """SPEC §10 once per row, the device hook `Device.bsdf_probe`'s twin: rows [n, 20] = {base[3], roughness, metallic, N[3], Ng[3], V[3], L[3],
+    r3, r4, r5} -> (out[n, 12] = {pspec, f[3], pdf, L_s[3], weight[3], pdf_s}, ok[n])"""
+    rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 20)
+    n = rows.shape[0]
+    out, ok = np.zeros((n, 12), np.float32), np.zeros(n, np.uint32)
+    lib().orc_bsdf_probe(n, _p(rows), _p(out), _p(ok))
+    return out, ok
