@@ -27,6 +27,7 @@
 #include "common.h"
 #include "env_dist.h"
 #include "emit_dist.h"
+#include "material_tables.h"
 #include "kernels.h"
 #include "build_kernels.h"
 #include "launch_plan.h"
@@ -149,11 +150,8 @@ struct lpt_scene_gpu {
     DevTree tree;
     DevMem tri_verts, materials, lights, texels, images, srgb_lut, pair_texels, pair_images;
     DevMem punctual;                // SPEC §19: lpt_punctual_light records (DScene::punctual)
-    DevMem trans_tri, trans_recs;   // SPEC §21: the per-triangle table and the records of the transmissive materials (DScene::trans_tri / trans_recs); empty without glass
+    struct { DevMem tri, recs; } mat_tab[MAT_KINDS];   // SPEC §20, §21, §22, §24: per kind of material_tables.h the per-triangle table and the records (DScene::alpha_tri / alpha_recs, ...); empty where the scene does not use the kind
     DevMem emit_tab;                // SPEC §23: the emitter distribution's entries (DScene::emit_tab); empty without a distribution
-    DevMem emis_tri, emis_recs;     // SPEC §22: the per-triangle table and the records of the emissive materials (DScene::emis_tri / emis_recs); empty without emitters
-    DevMem nmap_tri, nmap_recs;     // SPEC §24: the per-triangle table and the records of the normal-mapped materials (DScene::nmap_tri / nmap_recs); empty without normal maps
-    DevMem alpha_tri, alpha_recs;   // SPEC §20: the per-triangle table and the records of the masked materials (DScene::alpha_tri / alpha_recs); empty without masks
     TexturePairs pairs;
     lpt_accel_stats stats{};
     // refit bookkeeping (lpt_scene_gpu_update_instances)
@@ -652,30 +650,9 @@ static std::vector<uint64_t> pair_textures(const lpt_scene &scene, bool enable, 
         p.map[std::make_pair(a, r)] = (uint32_t)p.descs.size();
         p.descs.push_back(di);
     }
-    // an image no material references is kept: a later material edit (lpt_scene_gpu_update_instances) may start to sample it
-    std::vector<uint8_t> referenced(scene.images.size(), 0), alone(scene.images.size(), 0);
-    for (const lpt_material &m : scene.materials) {
-        const bool paired = p.map.count(std::make_pair(m.albedo_texture, m.mra_texture)) != 0;
-        for (uint32_t id : {m.albedo_texture, m.mra_texture})
-            if (id < scene.images.size()) { referenced[id] = 1; if (!paired) alone[id] = 1; }
-    }
-    // SPEC §20: the alpha lookup of the traversal reads the plain tiled image, never the paired copy: a mask's image stays in the atlas
-    for (size_t i = 0; i < scene.materials.size(); ++i) {
-        const MaterialAlpha a = scene.material_alpha(i);
-        if (a.mode == LPT_ALPHA_MASK && a.image < scene.images.size()) { referenced[a.image] = 1; alone[a.image] = 1; }
-    }
-    // SPEC §22: so does an emissive image — shade_hit<.., EMIS> looks it up on its own, whatever pair it is also half of
-    for (size_t i = 0; i < scene.materials.size(); ++i) {
-        const MaterialEmission e = scene.material_emission(i);
-        if (e.emissive() && e.image < scene.images.size()) { referenced[e.image] = 1; alone[e.image] = 1; }
-    }
-    // SPEC §24: and a normal image — normal_map looks it up on its own too
-    for (size_t i = 0; i < scene.materials.size(); ++i) {
-        const MaterialNormalMap m = scene.material_normal_map(i);
-        if (m.image < scene.images.size()) { referenced[m.image] = 1; alone[m.image] = 1; }
-    }
-    p.image_resident.assign(scene.images.size(), 1);
-    for (size_t i = 0; i < scene.images.size(); ++i) p.image_resident[i] = (!referenced[i] || alone[i]) ? 1 : 0;
+    std::vector<uint8_t> paired(scene.materials.size(), 0);
+    for (size_t i = 0; i < scene.materials.size(); ++i) paired[i] = p.map.count(std::make_pair(scene.materials[i].albedo_texture, scene.materials[i].mra_texture)) != 0;
+    p.image_resident = plain_image_residency(scene, paired);   // material_tables.h: an image a side-table record names stays in the atlas
     return texels;
 }
 
@@ -800,128 +777,28 @@ static int upload_punctual(lpt_scene_gpu *sg, const lpt_scene &scene) {
     return LPT_OK;
 }
 
-// SPEC §20: the alpha tables of the scene as it is now — one record per masked material that an instance with triangles uses, one uint32 per baked triangle (keyed by
-// prim id: a refit leaves it alone).  Derived on the host from the instance layout; both empty for a scene without masks, which then launches what it always launched.
-struct AlphaTables { std::vector<float4> recs; std::vector<uint32_t> tri; };
-static int derive_alpha(const lpt_scene_gpu *sg, const lpt_scene &scene, AlphaTables &out) {
-    std::vector<uint32_t> rec_of(scene.materials.size(), 0u);   // 1 + record index
-    for (size_t i = 0; i < scene.instances.size() && i < sg->inst_count.size(); ++i) {
-        const uint32_t n = sg->inst_count[i];
-        if (!n) continue;
-        const uint32_t mat = scene.instances[i].material_index < scene.materials.size() ? scene.instances[i].material_index : 0u;   // SPEC §2.5
-        const MaterialAlpha a = scene.material_alpha(mat);
-        if (a.mode != LPT_ALPHA_MASK) continue;
-        if (!rec_of[mat]) {
-            uint32_t image = a.image < scene.images.size() ? a.image : LPT_INVALID_INDEX;
-            if (image != LPT_INVALID_INDEX && !(image < sg->pairs.image_resident.size() && sg->pairs.image_resident[image]))
-                return fail(LPT_ERR_INVALID_ARG, "material %u now masks with an image that was uploaded only as half of an (albedo, mra) pair: upload the scene again", mat);
-            float bits;
-            memcpy(&bits, &image, 4);
-            out.recs.push_back(make_float4(a.cutoff, scene.materials[mat].color[3], bits, 0.f));
-            rec_of[mat] = (uint32_t)out.recs.size();
-        }
-        if (out.tri.empty()) out.tri.assign(std::max(sg->d.n_tris, 1u), 0u);
-        if ((size_t)sg->inst_first[i] + n > out.tri.size()) return fail(LPT_ERR_INVALID_ARG, "instance %zu lies beyond the baked triangles", i);
-        std::fill(out.tri.begin() + sg->inst_first[i], out.tri.begin() + sg->inst_first[i] + n, rec_of[mat]);
-    }
-    return LPT_OK;
-}
-// ... onto the device and into the view the kernels get; the caller has made sure nothing in flight reads the old tables
-static int commit_alpha(lpt_scene_gpu *sg, const AlphaTables &at) {
-    DScene &d = sg->d;
-    if (at.recs.empty()) {
-        sg->alpha_tri.reset(); sg->alpha_recs.reset();
-        d.alpha_tri = nullptr; d.alpha_recs = nullptr; d.n_alpha = 0u;
+// SPEC §20, §21, §22, §24: one material side table (material_tables.h) onto the device and into the view the kernels get; the caller has made sure nothing in flight
+// reads the old tables, and waits for the stream before the host vectors go
+struct DSceneTable { const uint32_t *DScene::*tri; const float4 *DScene::*recs; uint32_t DScene::*n; };
+static const DSceneTable kDSceneTables[MAT_KINDS] = {
+    {&DScene::alpha_tri, &DScene::alpha_recs, &DScene::n_alpha},
+    {&DScene::trans_tri, &DScene::trans_recs, &DScene::n_trans},
+    {&DScene::emis_tri, &DScene::emis_recs, &DScene::n_emis},
+    {&DScene::nmap_tri, &DScene::nmap_recs, &DScene::n_nmap},
+};
+static int commit_table(lpt_scene_gpu *sg, int kind, const MaterialTable &t) {
+    auto &mem = sg->mat_tab[kind];
+    const DSceneTable &view = kDSceneTables[kind];
+    if (t.recs.empty()) {
+        mem.tri.reset(); mem.recs.reset();
+        sg->d.*view.tri = nullptr; sg->d.*view.recs = nullptr; sg->d.*view.n = 0u;
         return LPT_OK;
     }
-    hipStream_t s = sg->dev->stream;
-    TRY(upload(sg->alpha_tri, at.tri, s));
-    TRY(upload(sg->alpha_recs, at.recs, s));
-    HIP_TRY(hipStreamSynchronize(s));   // the host vectors are the caller's
-    d.alpha_tri = as<const uint32_t>(sg->alpha_tri);
-    d.alpha_recs = as<const float4>(sg->alpha_recs);
-    d.n_alpha = (uint32_t)at.recs.size();
-    return LPT_OK;
-}
-
-// SPEC §21: the transmission tables, derived and committed as the alpha tables are — one record {transmission, ior, thin, 0} per transmissive material that an
-// instance with triangles uses, one uint32 per baked triangle (keyed by prim id).  Both empty for a scene without glass in use, which then launches what it always launched.
-struct TransTables { std::vector<float4> recs; std::vector<uint32_t> tri; };
-static int derive_trans(const lpt_scene_gpu *sg, const lpt_scene &scene, TransTables &out) {
-    std::vector<uint32_t> rec_of(scene.materials.size(), 0u);   // 1 + record index
-    for (size_t i = 0; i < scene.instances.size() && i < sg->inst_count.size(); ++i) {
-        const uint32_t n = sg->inst_count[i];
-        if (!n) continue;
-        const uint32_t mat = scene.instances[i].material_index < scene.materials.size() ? scene.instances[i].material_index : 0u;   // SPEC §2.5
-        const MaterialTransmission t = scene.material_transmission(mat);
-        if (!(t.factor > 0.0f)) continue;
-        if (!rec_of[mat]) {
-            out.recs.push_back(make_float4(t.factor, t.ior, t.thin_walled ? 1.0f : 0.0f, 0.f));
-            rec_of[mat] = (uint32_t)out.recs.size();
-        }
-        if (out.tri.empty()) out.tri.assign(std::max(sg->d.n_tris, 1u), 0u);
-        if ((size_t)sg->inst_first[i] + n > out.tri.size()) return fail(LPT_ERR_INVALID_ARG, "instance %zu lies beyond the baked triangles", i);
-        std::fill(out.tri.begin() + sg->inst_first[i], out.tri.begin() + sg->inst_first[i] + n, rec_of[mat]);
-    }
-    return LPT_OK;
-}
-static int commit_trans(lpt_scene_gpu *sg, const TransTables &tt) {
-    DScene &d = sg->d;
-    if (tt.recs.empty()) {
-        sg->trans_tri.reset(); sg->trans_recs.reset();
-        d.trans_tri = nullptr; d.trans_recs = nullptr; d.n_trans = 0u;
-        return LPT_OK;
-    }
-    hipStream_t s = sg->dev->stream;
-    TRY(upload(sg->trans_tri, tt.tri, s));
-    TRY(upload(sg->trans_recs, tt.recs, s));
-    HIP_TRY(hipStreamSynchronize(s));   // the host vectors are the caller's
-    d.trans_tri = as<const uint32_t>(sg->trans_tri);
-    d.trans_recs = as<const float4>(sg->trans_recs);
-    d.n_trans = (uint32_t)tt.recs.size();
-    return LPT_OK;
-}
-
-// SPEC §22: the emission tables, derived and committed as the alpha tables are — one record {Le.r, Le.g, Le.b, bits of the plain image index} per emissive material
-// that an instance with triangles uses, one uint32 per baked triangle (keyed by prim id).  Both empty for a scene without an emitter in use, which then launches what it always launched.
-struct EmisTables { std::vector<float4> recs; std::vector<uint32_t> tri; };
-static int derive_emis(const lpt_scene_gpu *sg, const lpt_scene &scene, EmisTables &out) {
-    std::vector<uint32_t> rec_of(scene.materials.size(), 0u);   // 1 + record index
-    for (size_t i = 0; i < scene.instances.size() && i < sg->inst_count.size(); ++i) {
-        const uint32_t n = sg->inst_count[i];
-        if (!n) continue;
-        const uint32_t mat = scene.instances[i].material_index < scene.materials.size() ? scene.instances[i].material_index : 0u;   // SPEC §2.5
-        const MaterialEmission e = scene.material_emission(mat);
-        if (!e.emissive()) continue;
-        if (!rec_of[mat]) {
-            const uint32_t image = e.image < scene.images.size() ? e.image : LPT_INVALID_INDEX;
-            if (image != LPT_INVALID_INDEX && !(image < sg->pairs.image_resident.size() && sg->pairs.image_resident[image]))
-                return fail(LPT_ERR_INVALID_ARG, "material %u now emits with an image that was uploaded only as half of an (albedo, mra) pair: upload the scene again", mat);
-            float bits;
-            memcpy(&bits, &image, 4);
-            out.recs.push_back(make_float4(e.le[0], e.le[1], e.le[2], bits));
-            rec_of[mat] = (uint32_t)out.recs.size();
-        }
-        if (out.tri.empty()) out.tri.assign(std::max(sg->d.n_tris, 1u), 0u);
-        if ((size_t)sg->inst_first[i] + n > out.tri.size()) return fail(LPT_ERR_INVALID_ARG, "instance %zu lies beyond the baked triangles", i);
-        std::fill(out.tri.begin() + sg->inst_first[i], out.tri.begin() + sg->inst_first[i] + n, rec_of[mat]);
-    }
-    return LPT_OK;
-}
-static int commit_emis(lpt_scene_gpu *sg, const EmisTables &et) {
-    DScene &d = sg->d;
-    if (et.recs.empty()) {
-        sg->emis_tri.reset(); sg->emis_recs.reset();
-        d.emis_tri = nullptr; d.emis_recs = nullptr; d.n_emis = 0u;
-        return LPT_OK;
-    }
-    hipStream_t s = sg->dev->stream;
-    TRY(upload(sg->emis_tri, et.tri, s));
-    TRY(upload(sg->emis_recs, et.recs, s));
-    HIP_TRY(hipStreamSynchronize(s));   // the host vectors are the caller's
-    d.emis_tri = as<const uint32_t>(sg->emis_tri);
-    d.emis_recs = as<const float4>(sg->emis_recs);
-    d.n_emis = (uint32_t)et.recs.size();
+    TRY(upload(mem.tri, t.tri, sg->dev->stream));
+    TRY(upload(mem.recs, t.recs, sg->dev->stream));
+    sg->d.*view.tri = as<const uint32_t>(mem.tri);
+    sg->d.*view.recs = as<const float4>(mem.recs);
+    sg->d.*view.n = (uint32_t)t.recs.size();
     return LPT_OK;
 }
 
@@ -929,7 +806,6 @@ static int commit_emis(lpt_scene_gpu *sg, const EmisTables &et) {
 // committed beside the emission tables — at upload, rebuild and every instance update, since the weights are world-space areas.  The cost is a host bake of every
 // emissive instance (bake_instance: normals too, which the distribution does not read) on every update, also one that moves no emitter: linear in the emissive
 // triangles, meant for lamps of a few thousand triangles, not for a scene that is mostly emissive.
-static inline float bits_as_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 struct EmitTable { std::vector<float4> tab; float inv_W = 0.0f; };
 static int derive_emit(const lpt_scene_gpu *sg, const lpt_scene &scene, EmitTable &out) {
     EmitDist dist;
@@ -951,53 +827,25 @@ static int commit_emit(lpt_scene_gpu *sg, const EmitTable &et) {
     }
     hipStream_t s = sg->dev->stream;
     TRY(upload(sg->emit_tab, et.tab, s));
-    HIP_TRY(hipStreamSynchronize(s));   // the host vector is the caller's
     d.emit_tab = as<const float4>(sg->emit_tab);
     d.n_emit = (uint32_t)et.tab.size();
     d.emit_inv_W = et.inv_W;
     return LPT_OK;
 }
 
-// SPEC §24: the normal-map tables, derived and committed as the emission tables are — one record {bits of the plain image index, scale, 0, 0} per normal-mapped material
-// that an instance with triangles uses, one uint32 per baked triangle (keyed by prim id).  Both empty for a scene without a normal map in use, which then launches what it always launched.
-struct NmapTables { std::vector<float4> recs; std::vector<uint32_t> tri; };
-static int derive_nmap(const lpt_scene_gpu *sg, const lpt_scene &scene, NmapTables &out) {
-    std::vector<uint32_t> rec_of(scene.materials.size(), 0u);   // 1 + record index
-    for (size_t i = 0; i < scene.instances.size() && i < sg->inst_count.size(); ++i) {
-        const uint32_t n = sg->inst_count[i];
-        if (!n) continue;
-        const uint32_t mat = scene.instances[i].material_index < scene.materials.size() ? scene.instances[i].material_index : 0u;   // SPEC §2.5
-        const MaterialNormalMap m = scene.material_normal_map(mat);
-        if (!(m.image < scene.images.size())) continue;
-        if (!rec_of[mat]) {
-            if (!(m.image < sg->pairs.image_resident.size() && sg->pairs.image_resident[m.image]))
-                return fail(LPT_ERR_INVALID_ARG, "material %u now has a normal map whose image was uploaded only as half of an (albedo, mra) pair: upload the scene again", mat);
-            float bits;
-            memcpy(&bits, &m.image, 4);
-            out.recs.push_back(make_float4(bits, m.scale, 0.0f, 0.0f));
-            rec_of[mat] = (uint32_t)out.recs.size();
-        }
-        if (out.tri.empty()) out.tri.assign(std::max(sg->d.n_tris, 1u), 0u);
-        if ((size_t)sg->inst_first[i] + n > out.tri.size()) return fail(LPT_ERR_INVALID_ARG, "instance %zu lies beyond the baked triangles", i);
-        std::fill(out.tri.begin() + sg->inst_first[i], out.tri.begin() + sg->inst_first[i] + n, rec_of[mat]);
-    }
-    return LPT_OK;
+// Everything the device keeps per triangle of the scene's materials: the four side tables and the emitter distribution.  Derived on the host (an edit is checked
+// before anything is baked), committed together — at upload, rebuild and every instance update.  The distribution goes last: commit_emit reads the committed n_emis.
+struct SceneTables { MaterialTable mat[MAT_KINDS]; EmitTable emit; };
+static int derive_tables(const lpt_scene_gpu *sg, const lpt_scene &scene, SceneTables &out) {
+    TRY(derive_material_tables(scene, sg->inst_first, sg->inst_count, sg->d.n_tris, sg->pairs.image_resident, out.mat));
+    return derive_emit(sg, scene, out.emit);
 }
-static int commit_nmap(lpt_scene_gpu *sg, const NmapTables &nt) {
-    DScene &d = sg->d;
-    if (nt.recs.empty()) {
-        sg->nmap_tri.reset(); sg->nmap_recs.reset();
-        d.nmap_tri = nullptr; d.nmap_recs = nullptr; d.n_nmap = 0u;
-        return LPT_OK;
-    }
-    hipStream_t s = sg->dev->stream;
-    TRY(upload(sg->nmap_tri, nt.tri, s));
-    TRY(upload(sg->nmap_recs, nt.recs, s));
-    HIP_TRY(hipStreamSynchronize(s));   // the host vectors are the caller's
-    d.nmap_tri = as<const uint32_t>(sg->nmap_tri);
-    d.nmap_recs = as<const float4>(sg->nmap_recs);
-    d.n_nmap = (uint32_t)nt.recs.size();
-    return LPT_OK;
+static int commit_tables(lpt_scene_gpu *sg, const SceneTables &t) {
+    int st = LPT_OK;
+    for (int k = 0; k < MAT_KINDS && st == LPT_OK; ++k) st = commit_table(sg, k, t.mat[k]);
+    if (st == LPT_OK) st = commit_emit(sg, t.emit);
+    HIP_TRY(hipStreamSynchronize(sg->dev->stream));   // the host vectors are the caller's: waited for behind a failed upload too
+    return st;
 }
 
 int lpt_scene_upload(lpt_device *dev, const lpt_scene *scene, lpt_scene_gpu **out) { return lpt_scene_upload_ex(dev, scene, LPT_ACCEL_BUILD_HOST_SAH, out); }
@@ -1090,21 +938,9 @@ int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags,
     d.n_images = (uint32_t)scene->images.size();
     TRY(upload_punctual(sg.get(), *scene));
     {
-        AlphaTables at;
-        TRY(derive_alpha(sg.get(), *scene, at));
-        TRY(commit_alpha(sg.get(), at));
-        TransTables tt;
-        TRY(derive_trans(sg.get(), *scene, tt));
-        TRY(commit_trans(sg.get(), tt));
-        EmisTables et;
-        TRY(derive_emis(sg.get(), *scene, et));
-        TRY(commit_emis(sg.get(), et));
-        EmitTable em;   // SPEC §23
-        TRY(derive_emit(sg.get(), *scene, em));
-        TRY(commit_emit(sg.get(), em));
-        NmapTables nt;   // SPEC §24
-        TRY(derive_nmap(sg.get(), *scene, nt));
-        TRY(commit_nmap(sg.get(), nt));
+        SceneTables tables;
+        TRY(derive_tables(sg.get(), *scene, tables));
+        TRY(commit_tables(sg.get(), tables));
     }
     sg->stats.triangles = d.n_tris;
     sg->stats.node_bytes = (uint32_t)sizeof(Node8);
@@ -1147,17 +983,10 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
     for (size_t i = 0; i < scene->instances.size(); ++i)
         if (memcmp(&scene->instances[i], &sg->instances[i], sizeof(lpt_instance)) != 0) changed.push_back((uint32_t)i);
     if (!changed.empty()) {
-        // SPEC §20: an instance whose material changed may have become masked or opaque; checked before anything is baked
-        AlphaTables at;
-        TRY(derive_alpha(sg, *scene, at));
-        TransTables tt;   // ... or transmissive (SPEC §21)
-        TRY(derive_trans(sg, *scene, tt));
-        EmisTables et;    // ... or emissive (SPEC §22)
-        TRY(derive_emis(sg, *scene, et));
-        EmitTable em;   // ... and with it the emitter distribution (SPEC §23: world-space areas)
-        TRY(derive_emit(sg, *scene, em));
-        NmapTables nt;    // ... or normal-mapped (SPEC §24)
-        TRY(derive_nmap(sg, *scene, nt));
+        // an instance whose material changed may have become masked, transmissive, emissive or normal-mapped, or stopped being so, and the emitter distribution
+        // weighs world-space areas (SPEC §20 - §24); checked before anything is baked
+        SceneTables tables;
+        TRY(derive_tables(sg, *scene, tables));
         // re-bake on the device (the object-space meshes are resident, only the transforms travel); a place-driven scatter then takes the new
         // Woop maps to every place a triangle has in the tree (a split triangle has several)
         DevMem woop_prim;
@@ -1170,11 +999,7 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
             if (sg->inst_count[i]) scatter_woop(sg->tree, woop_prim.get(), sg->inst_first[i], sg->inst_count[i], sg->dev->stream);
         }
         if (st != LPT_OK) return st;
-        TRY(commit_alpha(sg, at));
-        TRY(commit_trans(sg, tt));
-        TRY(commit_emis(sg, et));
-        TRY(commit_emit(sg, em));
-        TRY(commit_nmap(sg, nt));
+        TRY(commit_tables(sg, tables));
         if (sg->stats.triangles) TRY(refit(sg));
     }
     if (out_rebaked) *out_rebaked = (uint32_t)changed.size();
@@ -1190,21 +1015,9 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
     const uint32_t n = sg->stats.triangles;
     if (n < 16u) {
         TRY(lpt_scene_gpu_update_instances(sg, scene, nullptr));   // (flushes and waits first)
-        AlphaTables at;   // SPEC §20: a rebuild re-derives the alpha tables whether or not an instance changed
-        TRY(derive_alpha(sg, *scene, at));
-        TRY(commit_alpha(sg, at));
-        TransTables tt;   // ... and the transmission tables (SPEC §21)
-        TRY(derive_trans(sg, *scene, tt));
-        TRY(commit_trans(sg, tt));
-        EmisTables et;    // ... and the emission tables (SPEC §22)
-        TRY(derive_emis(sg, *scene, et));
-        TRY(commit_emis(sg, et));
-        EmitTable em;   // SPEC §23
-        TRY(derive_emit(sg, *scene, em));
-        TRY(commit_emit(sg, em));
-        NmapTables nt;   // SPEC §24
-        TRY(derive_nmap(sg, *scene, nt));
-        TRY(commit_nmap(sg, nt));
+        SceneTables tables;   // a rebuild re-derives the tables whether or not an instance changed
+        TRY(derive_tables(sg, *scene, tables));
+        TRY(commit_tables(sg, tables));
         return upload_punctual(sg, *scene);
     }
     HIP_TRY(hipSetDevice(sg->dev->ordinal));
@@ -1212,21 +1025,9 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
     HIP_TRY(hipDeviceSynchronize());  // frames in flight on the renderers' streams still read what is rebuilt here
     TRY(upload_punctual(sg, *scene));   // lights are scene data: a rebuild carries them too, whatever their number (SPEC §19)
     {
-        AlphaTables at;   // ... and so are the materials' alpha states (SPEC §20)
-        TRY(derive_alpha(sg, *scene, at));
-        TRY(commit_alpha(sg, at));
-        TransTables tt;   // ... and their transmission states (SPEC §21)
-        TRY(derive_trans(sg, *scene, tt));
-        TRY(commit_trans(sg, tt));
-        EmisTables et;    // ... and their emission (SPEC §22)
-        TRY(derive_emis(sg, *scene, et));
-        TRY(commit_emis(sg, et));
-        EmitTable em;   // ... and the emitter distribution (SPEC §23)
-        TRY(derive_emit(sg, *scene, em));
-        TRY(commit_emit(sg, em));
-        NmapTables nt;   // ... and their normal maps (SPEC §24)
-        TRY(derive_nmap(sg, *scene, nt));
-        TRY(commit_nmap(sg, nt));
+        SceneTables tables;   // ... and so are the materials' side tables and the emitter distribution (SPEC §20 - §24)
+        TRY(derive_tables(sg, *scene, tables));
+        TRY(commit_tables(sg, tables));
     }
     DevMem woop_prim;
     TRY(dev_alloc(woop_prim, sizeof(WoopTri) * (size_t)n));

@@ -164,3 +164,117 @@ def test_refit_large_scene_statue_moves(device):
     a, b = sg.trace_closest(o, d), fresh.trace_closest(o, d)
     assert a.tobytes() == b.tobytes() and (a["prim"] != 0xFFFFFFFF).mean() > 0.5
     fresh.close(); sg.close()
+
+
+# ---------------------------------------------------------------- the four material side tables (SPEC §20, §21, §22, §24) and the emitter distribution (§23) follow the edits
+def _quad(scene, x, mat, z=-3.0, half=0.35):
+    pos = np.array([[x - half, -half, z], [x + half, -half, z], [x + half, half, z], [x - half, half, z]], np.float32)
+    nrm = np.tile(np.float32([[0, 0, 1]]), (4, 1))
+    uv = np.array([(0, 0), (1.5, 0), (1.5, 1.5), (0, 1.5)], np.float32)
+    return scene.add_instance(scene.add_mesh(pos, nrm, uv, np.array([0, 1, 2, 0, 2, 3], np.uint32)), np.eye(4, dtype=np.float32), mat)
+
+
+def _nudged(dy):
+    m = np.eye(4, dtype=np.float32)
+    m[1, 3] = dy
+    return m.T
+
+
+def _table_frame(device, sg, probe):
+    """64x36 pixels, 4 samples, a fixed seed, emitter sampling on"""
+    r = lp.Renderer(device, (64, 36))
+    r.downsample_factor = 1.0
+    r.resize(device, sg, probe, (64, 36))
+    r.set_max_bounces(3)
+    r.set_vfov(0.6)
+    r.set_seed(11)
+    r.set_emissive_sampling(True)
+    r.reset_accumulation()
+    r.accumulate = True
+    view = T.look((0.0, 0.0, 0.0), (0.0, 0.0, -1.0))
+    for _ in range(4):
+        r.raytrace(view)
+    img = r.read_radiance()
+    r.close()
+    return img
+
+
+@pytest.mark.parametrize("big", [False, True], ids=["fewer-than-16-triangles", "16-triangles-and-more"])
+def test_material_tables_follow_update_and_rebuild(device, big):
+    """a masked, a glass, an emissive (with an image) and a normal-mapped material on four instances; the features change places by an instance update, then by a
+    rebuild (its refit arm below 16 triangles, its GPU build from 16 on): every frame is that of a fresh upload of the scene as edited.  An edit that names an image
+    uploaded only as half of a pair is InvalidArg and leaves the scene on the device as it was"""
+    rng = np.random.RandomState(31)
+    mask = rng.randint(0, 256, (4, 4, 4)).astype(np.uint8)
+    glow = rng.randint(0, 256, (4, 4, 4)).astype(np.uint8)
+    bump = rng.randint(64, 192, (5, 3, 4)).astype(np.uint8)
+    bump[..., 2] = 230
+    s = lp.Scene()
+    dark = np.zeros(1, lp._abi.LIGHT_DT)
+    dark["normal"], dark["tangent"], dark["bitangent"], dark["origin"] = (0, -1, 0, 0), (1, 0, 0, 0.1), (0, 0, 1, 0.1), (0, -50.0, 0, 0.0)
+    s.set_light(0, dark)
+    i_mask, i_glow, i_bump = s.add_image(mask), s.add_image(glow), s.add_image(bump)
+    i_pa, i_pb = s.add_image(rng.randint(0, 256, (4, 4, 4)).astype(np.uint8)), s.add_image(rng.randint(0, 256, (4, 4, 4)).astype(np.uint8))
+    mats = [s.add_material((0.9, 0.8, 0.7, 1.0), 0.6, 0.0) for _ in range(4)]
+    inst = [_quad(s, x, m) for x, m in zip((-1.2, -0.4, 0.4, 1.2), mats)]
+    _quad(s, 0.0, s.add_material((0.7, 0.7, 0.9, 1.0), 0.9, 0.0), z=-4.0, half=2.5)                 # a backdrop: what the cut-away texels and the glass show
+    _quad(s, 0.0, s.add_material((1.0, 1.0, 1.0, 1.0), 1.0, 0.0, i_pa, i_pb), z=-3.5, half=0.2)    # (i_pa, i_pb) is a pair: neither image is resident on its own
+    if big:
+        g = np.linspace(-2.5, 2.5, 4, dtype=np.float32)
+        pos = np.array([[x, -0.8, z - 3.0] for z in g for x in g], np.float32)
+        idx = np.array([[a, a + 1, a + 5, a, a + 5, a + 4] for a in (j * 4 + i for j in range(3) for i in range(3))], np.uint32).reshape(-1)
+        s.add_instance(s.add_mesh(pos, np.tile(np.float32([[0, 1, 0]]), (16, 1)), None, idx), np.eye(4, dtype=np.float32), s.add_material((0.5, 0.5, 0.5, 1.0), 1.0, 0.0))
+
+    def assign(order):
+        """material mats[order[k]] gets feature k (mask, glass, emission, normal map) and no other"""
+        for m in mats:
+            s.set_material_alpha(m, "OPAQUE")
+            s.set_material_transmission(m, 0.0)
+            s.set_material_emission(m, 0.0)
+            s.set_material_normal_map(m, None)
+        s.set_material_alpha(mats[order[0]], "MASK", 0.5, i_mask)
+        s.set_material_transmission(mats[order[1]], 1.0, 1.5, True)
+        s.set_material_emission(mats[order[2]], (1.0, 0.5, 0.25), 2.0, i_glow)
+        s.set_material_normal_map(mats[order[3]], i_bump, 2.0)
+
+    assign((0, 1, 2, 3))
+    sg = lp.SceneGPU.new_from_scene(s, device)
+    assert (sg.stats().triangles >= 16) == big and sg.stats().texture_pairs == 1
+    probe = lp.ProbeGPU(device, np.array([[[128, 128, 128, 128]]], np.uint8), 1, 1)
+    seen = []
+
+    def check():
+        fresh_sg = lp.SceneGPU.new_from_scene(s, device)
+        got, fresh = _table_frame(device, sg, probe), _table_frame(device, fresh_sg, probe)
+        fresh_sg.close()
+        assert np.all(np.isfinite(fresh)) and got.tobytes() == fresh.tobytes()
+        assert all(fresh.tobytes() != f.tobytes() for f in seen)      # every edit shows
+        seen.append(fresh)
+
+    check()
+    assign((1, 2, 3, 0))                                  # the features move one instance on, by an instance update
+    for i in inst:
+        s.set_instance_transform(i, _nudged(0.02))
+    assert sg.update_instances(s) == 4
+    check()
+    assign((3, 0, 1, 2))                                  # ... and again, by a rebuild that finds no instance changed
+    sg.rebuild(s)
+    check()
+    before = seen[-1]
+    # a pair-only image: each of the three kinds that name an image refuses it, by an update and by a rebuild, before anything on the device changed
+    edits = [lambda: s.set_material_alpha(mats[3], "MASK", 0.5, i_pa), lambda: s.set_material_emission(mats[1], (1.0, 0.5, 0.25), 2.0, i_pb),
+             lambda: s.set_material_normal_map(mats[2], i_pa, 2.0)]
+    for edit in edits:
+        for call in (sg.update_instances, sg.rebuild):
+            edit()
+            s.set_instance_transform(inst[0], _nudged(0.3))
+            with pytest.raises(lp.Error) as e:
+                call(s)
+            assert e.value.kind == "InvalidArg" and "only as half of an (albedo, mra) pair" in str(e.value)
+            assert _table_frame(device, sg, probe).tobytes() == before.tobytes()
+            s.set_instance_transform(inst[0], _nudged(0.02))
+            assign((3, 0, 1, 2))
+    assert sg.update_instances(s) == 0
+    assert _table_frame(device, sg, probe).tobytes() == before.tobytes()
+    probe.close()
+    sg.close()

@@ -522,3 +522,50 @@ def test_bench_renders_the_glass_file():
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
     j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert j["data"] == "real" and "glass-pane.glb" in j["config"]["workload"] and j["config"]["frame_complete"] is True and j["value"] > 0
+
+
+# ---------------------------------------------------------------- 10. the tables follow the scene through an instance update and both arms of a rebuild
+@pytest.mark.parametrize("big", [False, True], ids=["fewer-than-16-triangles", "16-triangles"])
+def test_tables_follow_update_and_rebuild(device, big):
+    """a pane whose material turns into glass by an instance update, is edited again by a rebuild alone, and turns opaque again by an instance update: after each
+    step the frame is the frame of a fresh upload of the scene as edited.  A scene of fewer than 16 triangles takes the rebuild's refit arm, one of 16 its GPU build"""
+    probe = const_probe(0.5)
+    kw = dict(n=4, size=(64, 36), depth=3)
+
+    def moved(dx):
+        m = np.eye(4, dtype=np.float32)
+        m[0, 3] = dx
+        return m.T
+
+    s = lp.Scene()
+    s.set_light(0, _dark_light())
+    pane_mat = s.add_material(BASE + (1.0,), 0.3, 0.0)
+    pane = add_rect(s, (0, 0, -2), (1, 0, 0), (0, 1, 0), 0.4, 0.4, pane_mat)
+    add_rect(s, (0.3, 0.1, -3), (1, 0, 0), (0, 1, 0), 0.5, 0.5, s.add_material((0.8, 0.2, 0.2, 1.0), 1.0, 0.0))       # behind the pane: seen through the glass only
+    if big:
+        pos, nrm, idx = cube_mesh(0.3)
+        xf = np.eye(4, dtype=np.float32)
+        xf[:3, 3] = (-0.5, 0.1, -3.5)
+        s.add_instance(s.add_mesh(pos, nrm, np.zeros((len(pos), 2), np.float32), idx), xf.T, s.add_material((0.2, 0.8, 0.2, 1.0), 0.8, 0.0))
+    sg = lp.SceneGPU.new_from_scene(s, device)
+    assert (sg.stats().triangles >= 16) == big
+
+    def check(other_than=None):
+        got, fresh = frame_of(device, s, probe, sg=sg, **kw), frame_of(device, s, probe, **kw)
+        assert np.all(np.isfinite(fresh)) and got.tobytes() == fresh.tobytes()
+        assert other_than is None or fresh.tobytes() != other_than.tobytes()
+        return fresh
+
+    opaque = check()
+    s.set_material_transmission(pane_mat, 1.0, 1.5, True)         # opaque -> glass, by an instance update
+    s.set_instance_transform(pane, moved(0.05))
+    assert sg.update_instances(s) == 1
+    glass = check(other_than=opaque)
+    s.set_material_transmission(pane_mat, 0.6, 1.33, False)       # no instance changed: the rebuild alone carries the new record
+    sg.rebuild(s)
+    check(other_than=glass)
+    s.set_material_transmission(pane_mat, 0.0)                    # ... and opaque again, by an instance update
+    s.set_instance_transform(pane, moved(0.0))
+    assert sg.update_instances(s) == 1
+    assert check(other_than=glass).tobytes() == opaque.tobytes()
+    sg.close()

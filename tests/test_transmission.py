@@ -93,7 +93,7 @@ def test_set_get_round_trip_and_factor_zero_is_opaque():
     m2 = s.add_material((1, 1, 1, 1), 1.0, 0.0)      # a material added after the table was first written
     assert s.material_transmission(m2) == OPAQUE
     s.set_material_transmission(m, 0.0, ior=2.0, thin_walled=False)
-    assert s.material_transmission(m)[0] == 0.0      # opaque again: the table entry of its triangles is 0 (device.hip derive_trans reads factor > 0)
+    assert s.material_transmission(m)[0] == 0.0      # opaque again: the table entry of its triangles is 0 (material_tables.h trans_state reads factor > 0)
     assert s.materials[:2].tobytes() == before and A.MATERIAL_DT.itemsize == 32
 
 
