@@ -290,6 +290,12 @@ inline void normalize3(float v[3]) {
 
 }  // namespace
 
+// SPEC §2.5: det = (m0·c00 + m4·c01) + m8·c02 < 0 in binary32, the first row's cofactors as bake_instance forms them
+bool bake_mirrored(const float m[16]) {
+    const float c00 = m[5] * m[10] - m[9] * m[6], c01 = m[9] * m[2] - m[1] * m[10], c02 = m[1] * m[6] - m[5] * m[2];
+    return (m[0] * c00 + m[4] * c01) + m[8] * c02 < 0.f;
+}
+
 // SPEC §2.5: one instance -> world-space triangles (appended to `verts`, 3 per triangle); returns the material.  Also emit_dist.cpp's bake (common.h)
 uint32_t bake_instance(const lpt_scene &s, size_t ii, std::vector<lpt_vertex> &verts) {
     const lpt_instance &inst = s.instances[ii];
@@ -303,9 +309,11 @@ uint32_t bake_instance(const lpt_scene &s, size_t ii, std::vector<lpt_vertex> &v
     const float c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
     const float c10 = a02 * a21 - a01 * a22, c11 = a00 * a22 - a02 * a20, c12 = a01 * a20 - a00 * a21;
     const float c20 = a01 * a12 - a02 * a11, c21 = a02 * a10 - a00 * a12, c22 = a00 * a11 - a01 * a10;
+    // a mirroring transform (det < 0) reverses the winding (glTF): vertices 1 and 2 change places and the normal keeps the object's own side
+    const bool mirrored = bake_mirrored(m);
     for (uint32_t t = 0; t < ntri; ++t) {
         for (int k = 0; k < 3; ++k) {
-            const lpt_vertex &v = s.vertices[e.vertex_offset + s.indices[e.index_offset + 3 * t + k]];
+            const lpt_vertex &v = s.vertices[e.vertex_offset + s.indices[e.index_offset + 3 * t + (mirrored && k ? 3 - k : k)]];
             const float x = v.position[0], y = v.position[1], z = v.position[2];
             lpt_vertex o;
             o.position[0] = ((m[0] * x + m[4] * y) + m[8] * z) + m[12];
@@ -314,6 +322,7 @@ uint32_t bake_instance(const lpt_scene &s, size_t ii, std::vector<lpt_vertex> &v
             o.position[3] = v.position[3];
             const float nx = v.normal[0], ny = v.normal[1], nz = v.normal[2];
             float n[3] = {(c00 * nx + c01 * ny) + c02 * nz, (c10 * nx + c11 * ny) + c12 * nz, (c20 * nx + c21 * ny) + c22 * nz};
+            if (mirrored) { n[0] = -n[0]; n[1] = -n[1]; n[2] = -n[2]; }
             normalize3(n);
             o.normal[0] = n[0]; o.normal[1] = n[1]; o.normal[2] = n[2]; o.normal[3] = v.normal[3];
             verts.push_back(o);
@@ -361,7 +370,8 @@ struct Collapse {
             const BuildNode &b = n[id];
             const float A = b.box.half_area();
             float *c = &C[7 * id];
-            const float leaf = b.pcount <= kLeafMax ? A * (float)b.pcount * kPrimCost : 1e30f;
+            const bool may_leaf = b.pcount <= kLeafMax;   // decided by the count alone: a cost sentinel loses against the areas of a scene 10^15 across (inf beyond 10^19), and a leaf of more than kLeafMax triangles writes past its node's places
+            const float leaf = may_leaf ? A * (float)b.pcount * kPrimCost : 1e30f;
             if (b.count) { for (int i = 0; i < 7; ++i) c[i] = leaf; continue; }
             const float *l = &C[7 * (size_t)b.left], *r = &C[7 * (size_t)b.right];
             float D[9];
@@ -376,7 +386,7 @@ struct Collapse {
             k8[id] = Dk[8];
             const float inner = D[8] + A * kNodeCost;
             c[0] = std::min(leaf, inner);
-            how[7 * id] = inner < leaf ? 1 : 0;
+            how[7 * id] = (!may_leaf || inner < leaf) ? 1 : 0;
             for (int i = 2; i <= 7; ++i) {
                 if (D[i] < c[i - 2]) { c[i - 1] = D[i]; how[7 * id + i - 1] = Dk[i]; }
                 else { c[i - 1] = c[i - 2]; how[7 * id + i - 1] = 0; }

@@ -146,6 +146,7 @@ constexpr float kScenePad = 2e-6f;   // triangle padding per unit of the scene's
 // bvh.cpp
 int bake_and_build(const lpt_scene &scene, Accel &out);
 uint32_t bake_instance(const lpt_scene &scene, size_t instance, std::vector<lpt_vertex> &verts);   // SPEC §2.5: one instance's world-space triangles appended, 3 vertices each; returns its material
+bool bake_mirrored(const float model_to_world[16]);   // SPEC §2.5: the binary32 determinant of the 3x3 part is negative: the bake exchanges vertices 1 and 2 and negates cof·N
 void woop_from_triangle(const float p0[3], const float p1[3], const float p2[3], WoopTri &w);
 
 // png.cpp

@@ -563,6 +563,7 @@ static int bake_instances(lpt_scene_gpu *sg, const lpt_scene &scene, const std::
         a.c[3] = a02 * a21 - a01 * a22; a.c[4] = a00 * a22 - a02 * a20; a.c[5] = a01 * a20 - a00 * a21;
         a.c[6] = a01 * a12 - a02 * a11; a.c[7] = a02 * a10 - a00 * a12; a.c[8] = a00 * a11 - a01 * a10;
         a.vertex_offset = e.vertex_offset; a.index_offset = e.index_offset; a.first_tri = sg->inst_first[i]; a.n_tris = n;
+        a.mirrored = bake_mirrored(m) ? 1u : 0u;
         bool resident = true;
         const lpt_material dm = device_material(sg->pairs, scene.materials[now.material_index < scene.materials.size() ? now.material_index : 0u], &resident);
         if (!resident) return fail(LPT_ERR_INVALID_ARG, "instance %u now samples a texture on its own that was uploaded only as half of an (albedo, mra) pair: upload the scene again", i);

@@ -2953,6 +2953,7 @@ struct BakeArgs {
     float m[16];        // model_to_world, column-major
     float c[9];         // cofactors of its 3x3 part, as bake_instance computes them (row-major c00..c22)
     uint32_t vertex_offset, index_offset, first_tri, n_tris;
+    uint32_t mirrored;  // bvh.cpp bake_mirrored(m): vertices 1 and 2 change places, cof·N is negated
     float4 mat[2];      // the instance's material (lpt_material verbatim), copied into every shading record
 };
 
@@ -2979,7 +2980,7 @@ __global__ __launch_bounds__(256) void k_bake_instance(BakeArgs a, const float4 
     const float *m = a.m;
     float P[3][3];
     for (int k = 0; k < 3; ++k) {
-        const uint32_t vi = a.vertex_offset + indices[a.index_offset + 3u * t + k];
+        const uint32_t vi = a.vertex_offset + indices[a.index_offset + 3u * t + (a.mirrored && k ? 3u - k : (uint32_t)k)];
         const float4 vp = obj_verts[2u * (size_t)vi], vn = obj_verts[2u * (size_t)vi + 1];
         const float x = vp.x, y = vp.y, z = vp.z;
         float4 op;
@@ -2989,6 +2990,7 @@ __global__ __launch_bounds__(256) void k_bake_instance(BakeArgs a, const float4 
         op.w = vp.w;
         const float nx = vn.x, ny = vn.y, nz = vn.z;
         float n0 = (a.c[0] * nx + a.c[1] * ny) + a.c[2] * nz, n1 = (a.c[3] * nx + a.c[4] * ny) + a.c[5] * nz, n2 = (a.c[6] * nx + a.c[7] * ny) + a.c[8] * nz;
+        if (a.mirrored) { n0 = -n0; n1 = -n1; n2 = -n2; }
         const float l2 = (n0 * n0 + n1 * n1) + n2 * n2;
         if (!(l2 > 0.f)) { n0 = n1 = n2 = 0.f; }
         else { const float inv = 1.0f / sqrtf(l2); n0 *= inv; n1 *= inv; n2 *= inv; }

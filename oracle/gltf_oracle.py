@@ -135,11 +135,14 @@ def _f32(x):
 def _normalize_rows(v):
     """SPEC §3: v * (1/sqrt((x*x + y*y) + z*z)); zero rows stay zero.  fp32, one rounding per op."""
     v = _f32(v)
-    l2 = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+    with np.errstate(over="ignore"):
+        l2 = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
     ok = l2 > 0
     inv = np.zeros_like(l2)
     inv[ok] = np.float32(1.0) / np.sqrt(l2[ok])
-    return v * inv[:, None]
+    out = v * inv[:, None]
+    out[~ok] = 0          # +0 whatever the signs, as the product writes it (a zero or underflowed vector)
+    return out
 
 
 def _cross(a, b):
@@ -375,6 +378,12 @@ def bake(scene):
         wn = np.stack([(c00 * nx + c01 * ny) + c02 * nz,
                        (c10 * nx + c11 * ny) + c12 * nz,
                        (c20 * nx + c21 * ny) + c22 * nz], axis=1).astype(np.float32)
+        # a mirroring transform (SPEC §2.5: det < 0 in binary32) reverses the winding: vertices 1 and 2 change places, the normal keeps the object's own side
+        with np.errstate(over="ignore"):
+            mirrored = np.float32(np.float32(a00 * c00 + a01 * c01) + a02 * c02) < 0
+        if mirrored:
+            wn = -wn
+            idx = idx.reshape(-1, 3)[:, [0, 2, 1]].reshape(-1)
         wn = _normalize_rows(wn)
         out = np.zeros(v.shape[0], VERTEX_DT)
         out["position"][:, :3] = wp

@@ -74,6 +74,15 @@ def test_degenerate_soups(bvh_check, tmp_path):
     assert out["triangles"] == 0 and out["hits"] == 0 and out["nodes"] == 1
 
 
+@pytest.mark.parametrize("scale", [2.0 ** 50, 2.0 ** 60], ids=["areas-above-1e30", "areas-overflow"])
+def test_astronomic_extent_keeps_leaves_within_their_places(bvh_check, tmp_path, scale):
+    """a scene 10^16 and 10^19 across: box areas exceed any finite cost sentinel, then overflow.  The collapse must still never form a leaf of more than two triangles
+    (it wrote past its node's triangle places: a heap overflow in the upload); the tree stays conservative"""
+    rng = np.random.default_rng(60)
+    out = run(bvh_check, tmp_path, random_soup(rng, 200) * np.float32(scale), 2000)
+    assert out["triangles"] == 200 and out["mismatches"] == 0 and out["bad_refs"] == 0
+
+
 def test_grid_mesh_quality(bvh_check, tmp_path):
     """a tessellated wall: the SAH-optimal collapse fills nodes (fewer, fuller nodes than the greedy one) and
     does not visit more nodes per ray"""
