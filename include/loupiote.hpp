@@ -200,6 +200,10 @@ class SceneGPU {  // scene.rs:56-64,151-188
     void shading_normal(const Device &device, uint32_t n, const uint32_t *prim, const float *bary, const float *dirs, float *ns_out, uint32_t *mapped_out) const {
         check(lpt_scene_gpu_shading_normal(device.inner(), h_, n, prim, bary, dirs, ns_out, mapped_out));
     }
+    // SPEC.md §9: what a hit (prim, bary) reads from its textures through the shading kernels' lookups, out[n][16] (lpt.h), for tools and tests
+    void sample_textures(const Device &device, uint32_t n, const uint32_t *prim, const float *bary, float *out) const {
+        check(lpt_scene_gpu_sample_textures(device.inner(), h_, n, prim, bary, out));
+    }
     void sample_emitter(const Device &device, uint32_t n, const float *points, const float *rands, uint32_t *prim, uint32_t *sampled, float *y, float *wi, float *dist, float *cl,
                         float *p_a, float *E) const {
         check(lpt_scene_gpu_sample_emitter(device.inner(), h_, n, points, rands, prim, sampled, y, wi, dist, cl, p_a, E));
@@ -221,6 +225,8 @@ class ProbeGPU {  // scene.rs:66-121
         check(lpt_probe_sample(device.inner(), h_, uniforms, n, dirs, pdf_s, radiance));
     }
     void pdf(const Device &device, const float *dirs, uint32_t n, float *pdf_e) const { check(lpt_probe_pdf(device.inner(), h_, dirs, n, pdf_e)); }
+    /// SPEC.md §9: the probe's radiance along dirs[n][3] -> radiance[n][3]
+    void lookup(const Device &device, const float *dirs, uint32_t n, float *radiance) const { check(lpt_probe_lookup(device.inner(), h_, dirs, n, radiance)); }
 
    private:
     lpt_probe *h_ = nullptr;

@@ -223,7 +223,11 @@ int lpt_scene_counts_get(const lpt_scene *scene, lpt_scene_counts *out);
  * NULL.  Without indices, vertices are consumed three at a time.  Missing
  * normals become flat face normals (crates/lib/src/loaders/binary.rs:31-49).
  * LPT_ERR_ACCEL_BUILD on an out-of-range index or a count that is not a
- * multiple of three. */
+ * multiple of three.  Texture coordinates must be finite and at most LPT_UV_MAX
+ * in magnitude (SPEC.md §9: beyond it u x width is not a binary32 number and the
+ * filter weights would be NaN): LPT_ERR_INVALID_ARG otherwise, and the scene is
+ * unchanged. */
+#define LPT_UV_MAX 7.9228162514264338e28f /* 2^96 */
 int lpt_scene_add_mesh(lpt_scene *scene, const void *positions, size_t position_stride,
                        const void *normals, size_t normal_stride, const void *uvs,
                        size_t uv_stride, uint32_t vertex_count, const uint32_t *indices,
@@ -407,6 +411,14 @@ int lpt_scene_gpu_sample_emitter(lpt_device *dev, const lpt_scene_gpu *sg, uint3
 int lpt_scene_gpu_shading_normal(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, const float *dirs,
                                  float *ns_out, uint32_t *mapped_out);
 
+/* build-only extension (SPEC.md §9), for tests and tools in the manner of lpt_scene_gpu_shading_normal: what a hit of baked triangle
+ * prim[i] at barycentrics bary[i] = (u, v) reads from its textures, through the shading kernels' own lookups and dispatch.
+ * out[n][16] = {albedo rgb (sRGB-decoded), mra g, mra b (1 where the material has no such texture), the emissive image's texel rgb
+ * (1 without one), the normal map's texel xyz as stored in [0, 1] (0 without one), 1 where §20's alpha mask cuts the hit away else 0
+ * (0 in a scene without masks), the interpolated texture coordinate (tu, tv), 0, 0}.  LPT_ERR_INVALID_ARG for a prim at or beyond the
+ * scene's baked triangle count.  Blocking; host arrays. */
+int lpt_scene_gpu_sample_textures(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, float *out);
+
 /* build-only extension (SPEC.md §21), for tests and tools in the manner of lpt_probe_sample: the interface event of the shading kernels
  * (kernels.h interface_sample), once per element.  Inputs, n of each: dirs[n][3] the ray's unit direction d, ns[n][3] the shading
  * normal, ngf[n][3] the geometric normal flipped against d, entering[n] (non-zero: the geometric normal was not flipped), base[n][3]
@@ -441,6 +453,9 @@ int lpt_env_distribution(const uint8_t *rgbe8, uint32_t width, uint32_t height, 
  * dirs[n][3] (0 without a distribution).  Blocking; host arrays.  The distribution is built on first use and kept with the probe. */
 int lpt_probe_sample(lpt_device *dev, lpt_probe *probe, const float *uniforms, uint32_t n, float *dirs, float *pdf_s, float *radiance);
 int lpt_probe_pdf(lpt_device *dev, lpt_probe *probe, const float *dirs, uint32_t n, float *pdf_e);
+/* build-only extension (SPEC.md §9), for tests and tools: the probe's radiance radiance[n][3] along dirs[n][3], through the lookup a
+ * miss and an environment sample run (any probe; no distribution is needed).  Blocking; host arrays. */
+int lpt_probe_lookup(lpt_device *dev, lpt_probe *probe, const float *dirs, uint32_t n, float *radiance);
 
 /* ---- ray queries (the IntersectorPass on its own) -------------------------
  * replaces: passes::IntersectorPass dispatch (crates/lib/src/renderer.rs:458-463)

@@ -129,6 +129,7 @@ SIGNATURES = {
     "lpt_scene_emitter_distribution": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _pu32, C.POINTER(C.c_double)]),
     "lpt_scene_gpu_sample_emitter": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lpt_scene_gpu_shading_normal": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "lpt_scene_gpu_sample_textures": (_i, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "lpt_interface_sample": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lpt_bsdf_probe": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "lpt_probe_upload": (_i, [_vp, _vp, _u32, _u32, _pvp]),
@@ -136,6 +137,7 @@ SIGNATURES = {
     "lpt_env_distribution": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "lpt_probe_sample": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     "lpt_probe_pdf": (_i, [_vp, _vp, _vp, _u32, _vp]),
+    "lpt_probe_lookup": (_i, [_vp, _vp, _vp, _u32, _vp]),
     "lpt_trace_closest": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),
     "lpt_trace_occluded": (_i, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "lpt_renderer_create": (_i, [_vp, _u32, _u32, _pvp]),

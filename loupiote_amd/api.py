@@ -418,6 +418,20 @@ class SceneGPU:
         _check(A.lib().lpt_scene_gpu_shading_normal(self._dev.inner(), self._h, n, A.ptr(pr), A.ptr(ba), A.ptr(di), A.ptr(ns), A.ptr(mapped)))
         return ns, mapped != 0
 
+    def sample_textures(self, prim, bary):
+        """What a hit reads from its textures (SPEC.md §9) through the shading kernels' own lookups: prim[n], bary[n, 2] = (u, v) -> a dict of albedo[n, 3],
+        mra[n, 2] (g, b), emissive[n, 3] (the image's texel; 1 without one), normal[n, 3] (the map's raw texel; 0 without one), rejected[n] (bool, SPEC §20) and
+        uv[n, 2] (the interpolated texture coordinate), all float32."""
+        pr = np.ascontiguousarray(prim, np.uint32).reshape(-1)
+        n = pr.shape[0]
+        ba = np.ascontiguousarray(bary, np.float32).reshape(-1, 2)
+        if ba.shape[0] != n:
+            raise Error(A.LPT_ERR_INVALID_ARG, "sample_textures: one (u, v) per prim")
+        out = np.zeros((n, 16), np.float32)
+        _check(A.lib().lpt_scene_gpu_sample_textures(self._dev.inner(), self._h, n, A.ptr(pr), A.ptr(ba), A.ptr(out)))
+        return {"albedo": out[:, 0:3].copy(), "mra": out[:, 3:5].copy(), "emissive": out[:, 5:8].copy(), "normal": out[:, 8:11].copy(),
+                "rejected": out[:, 11].view(np.uint32) != 0, "uv": out[:, 12:14].copy()}
+
     def sample_emitter(self, points, rands):
         """The emitter sample the shading kernels run (SPEC.md §23) on the GPU: points[n, 3], rands[n, 4] = (ra, rb, r1, r2) -> a dict of prim[n],
         sampled[n] (bool), y[n, 3], wi[n, 3], dist[n], cl[n], p_a[n], E[n, 3]; zeros where there is no sample (prim is still the pick)."""
@@ -480,6 +494,13 @@ class ProbeGPU:
         d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
         out = np.zeros(d.shape[0], np.float32)
         _check(A.lib().lpt_probe_pdf(self._dev.inner(), self._h, A.ptr(d), d.shape[0], A.ptr(out)))
+        return out
+
+    def lookup(self, dirs):
+        """The probe's radiance (SPEC.md §9) along dirs[n, 3], through the kernels' own lookup -> [n, 3] float32"""
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        out = np.zeros((d.shape[0], 3), np.float32)
+        _check(A.lib().lpt_probe_lookup(self._dev.inner(), self._h, A.ptr(d), d.shape[0], A.ptr(out)))
         return out
 
     def close(self):

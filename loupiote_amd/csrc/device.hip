@@ -1140,6 +1140,28 @@ int lpt_scene_gpu_shading_normal(lpt_device *dev, const lpt_scene_gpu *sg, uint3
     return LPT_OK;
 }
 
+// SPEC §9: what a hit reads from its textures (kernels.h k_sample_textures: shade_hit's dispatch over texture_lookup / texture_lookup_pair / alpha_rejects), once per
+// element, for tests and tools.  out[n][16]
+int lpt_scene_gpu_sample_textures(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, float *out) {
+    if (!dev || !sg || (n && (!prim || !bary || !out))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_textures: null");
+    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_textures: the scene belongs to another device");
+    for (uint32_t i = 0; i < n; ++i)
+        if (prim[i] >= sg->d.n_tris) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_textures: element %u names triangle %u of %u", i, prim[i], sg->d.n_tris);
+    if (!n) return LPT_OK;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    DevMem dp, db, dout;
+    TRY(dev_alloc(dp, sizeof(uint32_t) * (size_t)n));
+    TRY(dev_alloc(db, sizeof(float) * 2 * (size_t)n));
+    TRY(dev_alloc(dout, sizeof(uint32_t) * 16 * (size_t)n));
+    HIP_TRY(hipMemcpy(dp.get(), prim, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(db.get(), bary, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_sample_textures, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, sg->d, as<const uint32_t>(dp), as<const float>(db), n, as<uint32_t>(dout));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    HIP_TRY(hipMemcpy(out, dout.get(), sizeof(uint32_t) * 16 * (size_t)n, hipMemcpyDeviceToHost));
+    return LPT_OK;
+}
+
 // SPEC §21: the interface event of the shading kernels (kernels.h interface_sample), once per element, for tests and tools
 int lpt_interface_sample(lpt_device *dev, uint32_t n, const float *dirs, const float *ns, const float *ngf, const uint32_t *entering, const float *base, const float *ior,
                          const uint32_t *thin, const float *r4, float *wi, float *weight, uint32_t *kind) {
@@ -1288,6 +1310,23 @@ int lpt_probe_pdf(lpt_device *dev, lpt_probe *probe, const float *dirs, uint32_t
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(dev->stream));
     HIP_TRY(hipMemcpy(pdf_e, dp.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    return LPT_OK;
+}
+
+// SPEC §9: env_lookup over caller-supplied directions (needs no distribution: any probe answers)
+int lpt_probe_lookup(lpt_device *dev, lpt_probe *probe, const float *dirs, uint32_t n, float *radiance) {
+    if (!dev || !probe || (n && (!dirs || !radiance))) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_lookup: null");
+    if (probe->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_lookup: the probe belongs to another device");
+    if (!n) return LPT_OK;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    DevMem dd, dr;
+    TRY(env_alloc(dd, sizeof(float) * 3 * (size_t)n));
+    TRY(env_alloc(dr, sizeof(float) * 3 * (size_t)n));
+    HIP_TRY(hipMemcpy(dd.get(), dirs, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_env_lookup, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, probe->d, as<const float>(dd), n, as<float>(dr));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    HIP_TRY(hipMemcpy(radiance, dr.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
     return LPT_OK;
 }
 

@@ -1606,6 +1606,13 @@ __global__ __launch_bounds__(kBlock) void k_env_pdf(DEnv ev, const float *dirs, 
     if (i >= n) return;
     pdf_e[i] = env_pdf(ev, mk3(dirs[3u * (size_t)i], dirs[3u * (size_t)i + 1u], dirs[3u * (size_t)i + 2u]));
 }
+// lpt_probe_lookup: SPEC §9's env_lookup, the function a miss and every environment sample run, one direction per thread
+__global__ __launch_bounds__(kBlock) void k_env_lookup(DProbe probe, const float *dirs, uint32_t n, float *radiance) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f3 Le = env_lookup(probe, mk3(dirs[3u * (size_t)i], dirs[3u * (size_t)i + 1u], dirs[3u * (size_t)i + 2u]));
+    radiance[3u * (size_t)i] = Le.x; radiance[3u * (size_t)i + 1u] = Le.y; radiance[3u * (size_t)i + 2u] = Le.z;
+}
 
 // ------------------------------------------------------------------ punctual lights (SPEC §19)
 // One sample of punctual light `l` seen from Po: the unit direction towards it, the distance (LPT_T_INF: directional) and the incident term E = colour x intensity x
@@ -1776,6 +1783,61 @@ __global__ __launch_bounds__(kBlock) void k_shading_normal(DScene sc, const uint
     }
     uint32_t *o = out + 4u * (size_t)i;
     o[0] = __float_as_uint(Ns.x); o[1] = __float_as_uint(Ns.y); o[2] = __float_as_uint(Ns.z); o[3] = mapped ? 1u : 0u;
+}
+
+// lpt_scene_gpu_sample_textures: what a hit (prim, bary) reads from its textures (SPEC §9), through the functions and the dispatch of shade_hit (which is repeated
+// here, not shared: k_shade sits at its register limit), one element per thread.  out: 16 words per element {albedo rgb, mra g, mra b (1 without the texture),
+// emissive texel rgb (1 without one), normal-map texel xyz, raw (0 without one), alpha_rejects (1 / 0; 0 in a scene without masks), tu, tv, 0, 0}
+__global__ __launch_bounds__(kBlock) void k_sample_textures(DScene sc, const uint32_t *prims, const float *bary, uint32_t n, uint32_t *out) {
+    __shared__ float s_lut[256];
+    s_lut[threadIdx.x] = sc.srgb_lut[threadIdx.x];  // kBlock == 256
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t prim = prims[i];
+    const float hu = bary[2u * (size_t)i], hv = bary[2u * (size_t)i + 1u];
+    const float4 *tv = sc.tri_verts + kTriRec * (size_t)prim;
+    const float4 P0 = tv[0], N0 = tv[1], P1 = tv[2], N1 = tv[3], P2 = tv[4], N2 = tv[5];
+    const float4 mp = tv[7];
+    const uint32_t em = sc.n_emis ? sc.emis_tri[prim] : 0u;
+    const uint32_t nm = sc.n_nmap ? sc.nmap_tri[prim] : 0u;
+    const float bw = (1.0f - hu) - hv;
+    const float tu = (P0.w * bw + P1.w * hu) + P2.w * hv;
+    const float tvv = (N0.w * bw + N1.w * hu) + N2.w * hv;
+    f3 alb = mk3(1.0f, 1.0f, 1.0f), emi = mk3(1.0f, 1.0f, 1.0f), nrm = mk3(0.0f, 0.0f, 0.0f);
+    float mg = 1.0f, mb = 1.0f;
+    const uint32_t atex = __float_as_uint(mp.z), mtex = __float_as_uint(mp.w);
+    if ((atex >> 30) == 1u) {   // kPairedBit set, not LPT_INVALID_INDEX
+        texture_lookup_pair(sc, s_lut, atex & ~kPairedBit, mtex, tu, tvv, alb, mg, mb);
+    } else {
+        if (atex < sc.n_images) {
+            const float4 tex = texture_lookup(sc, s_lut, atex, tu, tvv, true);
+            alb = mk3(tex.x, tex.y, tex.z);
+        }
+        if (mtex < sc.n_images) {
+            const float4 tex = texture_lookup(sc, s_lut, mtex, tu, tvv, false);
+            mg = tex.y; mb = tex.z;
+        }
+    }
+    if (em != 0u) {
+        const uint32_t etex = __float_as_uint(sc.emis_recs[em - 1u].w);
+        if (etex < sc.n_images) {
+            const float4 tex = texture_lookup(sc, s_lut, etex, tu, tvv, true);
+            emi = mk3(tex.x, tex.y, tex.z);
+        }
+    }
+    if (nm != 0u) {
+        const float4 tex = texture_lookup(sc, s_lut, __float_as_uint(sc.nmap_recs[nm - 1u].x), tu, tvv, false);
+        nrm = mk3(tex.x, tex.y, tex.z);
+    }
+    const bool cut = sc.n_alpha != 0u && alpha_rejects(sc, prim, hu, hv);
+    uint32_t *o = out + 16u * (size_t)i;
+    o[0] = __float_as_uint(alb.x); o[1] = __float_as_uint(alb.y); o[2] = __float_as_uint(alb.z);
+    o[3] = __float_as_uint(mg); o[4] = __float_as_uint(mb);
+    o[5] = __float_as_uint(emi.x); o[6] = __float_as_uint(emi.y); o[7] = __float_as_uint(emi.z);
+    o[8] = __float_as_uint(nrm.x); o[9] = __float_as_uint(nrm.y); o[10] = __float_as_uint(nrm.z);
+    o[11] = cut ? 1u : 0u;
+    o[12] = __float_as_uint(tu); o[13] = __float_as_uint(tvv); o[14] = 0u; o[15] = 0u;
 }
 
 // ------------------------------------------------------------------ transmission (SPEC §21)

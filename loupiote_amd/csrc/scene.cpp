@@ -111,6 +111,15 @@ int lpt_scene_add_mesh(lpt_scene *s, const void *positions, size_t position_stri
         for (uint32_t i = 0; i < index_count; ++i)
             if (indices[i] >= vertex_count)
                 return fail(LPT_ERR_ACCEL_BUILD, "index %u out of range (%u vertices)", indices[i], vertex_count);
+    // SPEC §9: the lookups' domain.  A NaN or infinite coordinate (or one so large that u x width overflows) gives NaN filter weights, and a NaN radiance never
+    // leaves the accumulation buffer; checked before the scene is touched
+    if (uvs)
+        for (uint32_t i = 0; i < vertex_count; ++i) {
+            float t[2];
+            memcpy(t, (const uint8_t *)uvs + (size_t)i * uv_stride, 8);
+            if (!(std::fabs(t[0]) <= LPT_UV_MAX) || !(std::fabs(t[1]) <= LPT_UV_MAX))
+                return fail(LPT_ERR_INVALID_ARG, "lpt_scene_add_mesh: texture coordinate (%g, %g) of vertex %u is not finite or exceeds LPT_UV_MAX", (double)t[0], (double)t[1], i);
+        }
     lpt_blas_entry e;
     e.vertex_offset = (uint32_t)s->vertices.size();
     e.vertex_count = vertex_count;

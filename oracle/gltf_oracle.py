@@ -28,6 +28,7 @@ import struct
 import numpy as np
 
 INVALID = 0xFFFFFFFF
+UV_MAX = np.float32(2.0 ** 96)   # lpt.h LPT_UV_MAX
 
 MATERIAL_DT = np.dtype([("color", "<f4", 4), ("roughness", "<f4"), ("reflectivity", "<f4"),
                         ("albedo_texture", "<u4"), ("mra_texture", "<u4")])
@@ -93,6 +94,8 @@ class Scene:
         v["position"][:, :3] = positions
         if uvs is not None:
             uvs = np.asarray(uvs, np.float32)
+            if not np.all(np.abs(uvs[:, :2]) <= UV_MAX):   # SPEC §9: NaN, infinite or beyond the lookups' domain, as lpt_scene_add_mesh
+                raise ValueError("texture coordinate not finite or beyond UV_MAX")
             v["position"][:, 3] = uvs[:, 0]
             v["normal"][:, 3] = uvs[:, 1]
         if normals is not None:

@@ -482,14 +482,23 @@ void orc_trace_occluded(const orc_scene *s, const float *origins, const float *d
 
 /* ------------------------------------------------------------------ SPEC §9 textures / environment */
 static inline int wrap_i(int x, int n) { int m = x % n; return m < 0 ? m + n : m; }
+/* SPEC §9: sat(floor(fx)), the conversion saturated to the int32 range (NaN -> 0) — what the device's conversion instruction gives, and defined in C for every input */
+static inline int sat_i(float f) {
+    if (!(f == f)) return 0;
+    if (f >= 2147483648.0f) return INT32_MAX;
+    if (f <= -2147483648.0f) return INT32_MIN;
+    return (int)f;
+}
+/* wrap(x + 1) from w = wrap(x): no overflow of x + 1 */
+static inline int wrap_next(int w, int n) { return w + 1 == n ? 0 : w + 1; }
 void orc_texture_lookup(const orc_scene *s, uint32_t image, float u, float v, int srgb, float out[4]) {
     const orc_image *im = &s->images[image];
     int W = (int)im->width, H = (int)im->height;
     float fx = u * (float)W - 0.5f, fy = v * (float)H - 0.5f;
     float x0f = floorf(fx), y0f = floorf(fy);
     float tx = fx - x0f, ty = fy - y0f;
-    int x0 = wrap_i((int)x0f, W), x1 = wrap_i((int)x0f + 1, W);
-    int y0 = wrap_i((int)y0f, H), y1 = wrap_i((int)y0f + 1, H);
+    int x0 = wrap_i(sat_i(x0f), W), x1 = wrap_next(x0, W);
+    int y0 = wrap_i(sat_i(y0f), H), y1 = wrap_next(y0, H);
     const uint8_t *p00 = im->rgba8 + 4 * ((size_t)y0 * W + x0), *p10 = im->rgba8 + 4 * ((size_t)y0 * W + x1);
     const uint8_t *p01 = im->rgba8 + 4 * ((size_t)y1 * W + x0), *p11 = im->rgba8 + 4 * ((size_t)y1 * W + x1);
     for (int ch = 0; ch < 4; ++ch) {
@@ -502,6 +511,10 @@ void orc_texture_lookup(const orc_scene *s, uint32_t image, float u, float v, in
         float top = c00 * (1.0f - tx) + c10 * tx, bot = c01 * (1.0f - tx) + c11 * tx;
         out[ch] = top * (1.0f - ty) + bot * ty;
     }
+}
+/* n lookups of one image: uv[n][2] -> out[n][4] (the tests' batches) */
+void orc_texture_lookup_n(const orc_scene *s, uint32_t image, const float *uv, uint32_t n, int srgb, float *out) {
+    for (uint32_t i = 0; i < n; ++i) orc_texture_lookup(s, image, uv[2 * (size_t)i], uv[2 * (size_t)i + 1], srgb, out + 4 * (size_t)i);
 }
 static inline void rgbe_decode(const uint8_t *p, float rgb[3]) {
     uint32_t e = p[3];
@@ -519,8 +532,8 @@ void orc_env_lookup(const orc_scene *s, const float d[3], float rgb[3]) {
     float fx = u * (float)W - 0.5f, fy = v * (float)H - 0.5f;
     float x0f = floorf(fx), y0f = floorf(fy);
     float tx = fx - x0f, ty = fy - y0f;
-    int x0 = wrap_i((int)x0f, W), x1 = wrap_i((int)x0f + 1, W);
-    int y0 = (int)y0f, y1 = (int)y0f + 1;
+    int x0 = wrap_i(sat_i(x0f), W), x1 = wrap_next(x0, W);
+    int y0 = sat_i(y0f), y1 = y0 == INT32_MAX ? y0 : y0 + 1;
     if (y0 < 0) y0 = 0; if (y0 > H - 1) y0 = H - 1;
     if (y1 < 0) y1 = 0; if (y1 > H - 1) y1 = H - 1;
     float c00[3], c10[3], c01[3], c11[3];
@@ -530,6 +543,10 @@ void orc_env_lookup(const orc_scene *s, const float d[3], float rgb[3]) {
         float top = c00[ch] * (1.0f - tx) + c10[ch] * tx, bot = c01[ch] * (1.0f - tx) + c11[ch] * tx;
         rgb[ch] = top * (1.0f - ty) + bot * ty;
     }
+}
+
+void orc_env_lookup_n(const orc_scene *s, const float *d, uint32_t n, float *rgb) {
+    for (uint32_t i = 0; i < n; ++i) orc_env_lookup(s, d + 3 * (size_t)i, rgb + 3 * (size_t)i);
 }
 
 /* ------------------------------------------------------------------ SPEC §10 BSDF */

@@ -121,6 +121,9 @@ int orc_bsdf_sample(const float base[3], float roughness, float metallic, const 
 void orc_bsdf_probe(uint32_t n, const float *in, float *out, uint32_t *ok);
 void orc_env_lookup(const orc_scene *s, const float d[3], float rgb[3]);
 void orc_texture_lookup(const orc_scene *s, uint32_t image, float u, float v, int srgb, float rgba[4]);
+/* batches of the two above: d[n][3] -> rgb[n][3]; uv[n][2] -> rgba[n][4] */
+void orc_env_lookup_n(const orc_scene *s, const float *d, uint32_t n, float *rgb);
+void orc_texture_lookup_n(const orc_scene *s, uint32_t image, const float *uv, uint32_t n, int srgb, float *rgba);
 float orc_srgb_lut(uint32_t i);
 
 #endif

@@ -108,6 +108,8 @@ def lib(path=None):
         L.orc_bsdf_probe.argtypes = [u32, vp, vp, vp]
         L.orc_env_lookup.argtypes = [vp, vp, vp]
         L.orc_texture_lookup.argtypes = [vp, u32, C.c_float, C.c_float, C.c_int, vp]
+        L.orc_env_lookup_n.argtypes = [vp, vp, u32, vp]
+        L.orc_texture_lookup_n.argtypes = [vp, u32, vp, u32, C.c_int, vp]
         L.orc_srgb_lut.restype = C.c_float
         L.orc_srgb_lut.argtypes = [u32]
         _LIB = L

@@ -77,6 +77,25 @@ def test_add_mesh_rejects_bad_indices_with_accel_build():
     assert s.counts().entries == 1  # nothing appended
 
 
+@pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf, 3e38, -3e38, 2.0 ** 97, -(2.0 ** 97)])
+def test_add_mesh_rejects_texture_coordinates_outside_the_domain(bad):
+    """SPEC §9 (tests/texture_ref.REJECTED_UV): no mesh carries a NaN, infinite or larger-than-LPT_UV_MAX texture coordinate to the lookups; the scene stays as it was,
+    and LPT_UV_MAX itself is accepted.  A mesh without uvs is not looked at."""
+    pos = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32)
+    for where in ((0, 0), (2, 1)):
+        s = lp.Scene()
+        uv = np.zeros((3, 2), np.float32)
+        uv[where] = bad
+        with pytest.raises(lp.Error) as e:
+            s.add_mesh(pos, uvs=uv)
+        assert e.value.kind == "InvalidArg" and "texture coordinate" in str(e.value)
+        c = s.counts()
+        assert (c.entries, c.vertices, c.indices) == (1, 1, 0)
+        uv[where] = np.float32(2.0 ** 96) * (-1 if bad < 0 else 1)
+        assert s.add_mesh(pos, uvs=uv) == 1 and s.add_mesh(pos) == 2
+        assert s.vertices[1 + where[0]][("position", "normal")[where[1]]][3] == uv[where]
+
+
 def test_invalid_arguments_are_reported_not_crashed():
     s = lp.Scene()
     with pytest.raises(lp.Error) as e:

@@ -213,6 +213,27 @@ def test_hostile_offsets_and_counts_are_rejected(mutate):
     assert (after.vertices, after.entries, after.images) == (before.vertices, before.entries, before.images)
 
 
+@pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf, 3e38, -3e38, 2.0 ** 97])
+@pytest.mark.parametrize("where", [(0, 0), (3, 1)])
+def test_texture_coordinates_outside_the_domain_are_rejected(bad, where):
+    """SPEC §9: a TEXCOORD_0 that is NaN, infinite or beyond LPT_UV_MAX (2^96) would give NaN filter weights and a NaN pixel that never leaves the accumulation buffer;
+    both loaders refuse the file and leave the scene as it was.  2^96 itself, and anything finite below it, loads."""
+    uv = np.array(QUV, np.float32).copy()
+    uv[where] = bad
+    data = make_gltf([[dict(pos=QUAD, nrm=QN, uv=uv, idx=[0, 1, 2, 0, 2, 3])]], [{"mesh": 0}])
+    s = lp.Scene()
+    before = s.counts()
+    with pytest.raises(lp.Error) as e:
+        lp.loaders.load_gltf(data, s)
+    assert e.value.kind == "FileNotFound" and "texture coordinate" in str(e.value)
+    after = s.counts()
+    assert (after.vertices, after.entries) == (before.vertices, before.entries)
+    with pytest.raises(FileNotFoundError):
+        G.load_gltf(data, G.Scene())
+    uv[where] = np.float32(2.0 ** 96) * (-1 if bad < 0 else 1)
+    assert_same(*both(make_gltf([[dict(pos=QUAD, nrm=QN, uv=uv, idx=[0, 1, 2, 0, 2, 3])]], [{"mesh": 0}])))
+
+
 def test_hostile_baseline_still_loads():
     s = lp.Scene()
     lp.loaders.load_gltf(_hostile(lambda j: None), s)
