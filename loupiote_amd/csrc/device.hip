@@ -29,6 +29,7 @@
 #include "emit_dist.h"
 #include "material_tables.h"
 #include "kernels.h"
+#include "probe_kernels.h"
 #include "build_kernels.h"
 #include "launch_plan.h"
 #include <hipcub/hipcub.hpp>
@@ -334,6 +335,43 @@ static int dev_alloc(DevMem &m, size_t bytes) {
     void *p = nullptr;
     HIP_TRY(hipMalloc(&p, bytes));
     m.reset(p);
+    return LPT_OK;
+}
+
+// The one path of every per-element probe (probe_kernels.h; the entry points are under "per-element probes" below): n elements up, one launch, n answers back.  Each
+// input and output is a host array and its bytes per element; `launch(grid, d)` gets the grid of `block`-thread blocks that covers n and the device arrays, the inputs
+// first, each list in its order.  Everything runs on dev->stream and is waited for once at the end, so nothing depends on how the null stream orders against a
+// non-blocking one; the host arrays are the caller's until then.  Argument checks are the entry point's.
+struct ProbeIn { const void *host; size_t stride; };
+struct ProbeOut { void *host; size_t stride; };
+template <typename Launch>
+static int run_probe(lpt_device *dev, uint32_t n, uint32_t block, std::initializer_list<ProbeIn> ins, std::initializer_list<ProbeOut> outs, Launch &&launch) {
+    if (!n) return LPT_OK;
+    HIP_TRY(hipSetDevice(dev->ordinal));
+    std::vector<DevMem> d(ins.size() + outs.size());
+    size_t k = 0;
+    for (const ProbeIn &b : ins) TRY(dev_alloc(d[k++], b.stride * n));
+    for (const ProbeOut &b : outs) TRY(dev_alloc(d[k++], b.stride * n));
+    k = 0;
+    for (const ProbeIn &b : ins) HIP_TRY(hipMemcpyAsync(d[k++].get(), b.host, b.stride * n, hipMemcpyHostToDevice, dev->stream));
+    launch(dim3(div_up(n, block)), d.data());
+    HIP_TRY(hipGetLastError());
+    for (const ProbeOut &b : outs) HIP_TRY(hipMemcpyAsync(b.host, d[k++].get(), b.stride * n, hipMemcpyDeviceToHost, dev->stream));
+    HIP_TRY(hipStreamSynchronize(dev->stream));
+    return LPT_OK;
+}
+// the ray queries: a ray goes up as two float4, (origin, tmax — read by the occlusion query alone) and (direction, -)
+static void pack_rays(const float *origins, const float *dirs, const float *tmax, uint32_t n, std::vector<float4> &o, std::vector<float4> &d) {
+    o.resize(n); d.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        o[i] = make_float4(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], tmax ? tmax[i] : 0.f);
+        d[i] = make_float4(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], 0.f);
+    }
+}
+// the (prim, ...) probes: every element names a triangle of the scene
+static int check_prims(const char *who, const DScene &d, const uint32_t *prim, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (prim[i] >= d.n_tris) return fail(LPT_ERR_INVALID_ARG, "%s: element %u names triangle %u of %u", who, i, prim[i], d.n_tris);
     return LPT_OK;
 }
 
@@ -1062,159 +1100,6 @@ int lpt_scene_gpu_update_punctual(lpt_scene_gpu *sg, const lpt_scene *scene) {
     return upload_punctual(sg, *scene);
 }
 
-int lpt_scene_gpu_sample_punctual(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t light_index, const float *points, uint32_t n, float *wi, float *dist, float *E) {
-    if (!dev || !sg || (n && (!points || !wi || !dist || !E))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_punctual: null");
-    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_punctual: the scene belongs to another device");
-    if (light_index >= sg->d.n_punctual) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_punctual: light %u of %u", light_index, sg->d.n_punctual);
-    if (!n) return LPT_OK;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    DevMem dp, dw, dd, de;
-    TRY(dev_alloc(dp, sizeof(float) * 3 * (size_t)n));
-    TRY(dev_alloc(dw, sizeof(float) * 3 * (size_t)n));
-    TRY(dev_alloc(dd, sizeof(float) * (size_t)n));
-    TRY(dev_alloc(de, sizeof(float) * 3 * (size_t)n));
-    HIP_TRY(hipMemcpy(dp.get(), points, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_punctual_sample, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, sg->d, light_index, as<const float>(dp), n, as<float>(dw), as<float>(dd), as<float>(de));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(dev->stream));
-    HIP_TRY(hipMemcpy(wi, dw.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(dist, dd.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(E, de.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
-    return LPT_OK;
-}
-
-// SPEC §23: the emitter sample of the shading kernels (kernels.h emitter_sample), once per point, for tests and tools
-int lpt_scene_gpu_sample_emitter(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const float *points, const float *rands, uint32_t *prim, uint32_t *sampled, float *y,
-                                 float *wi, float *dist, float *cl, float *p_a, float *E) {
-    if (!dev || !sg || (n && (!points || !rands || !prim || !sampled || !y || !wi || !dist || !cl || !p_a || !E))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_emitter: null");
-    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_emitter: the scene belongs to another device");
-    if (!sg->d.n_emit) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_emitter: the scene has no emitter distribution");
-    if (!n) return LPT_OK;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    DevMem dp, dr, dout;
-    TRY(dev_alloc(dp, sizeof(float) * 3 * (size_t)n));
-    TRY(dev_alloc(dr, sizeof(float) * 4 * (size_t)n));
-    TRY(dev_alloc(dout, sizeof(uint32_t) * 16 * (size_t)n));
-    HIP_TRY(hipMemcpy(dp.get(), points, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dr.get(), rands, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_emitter_sample, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, sg->d, as<const float>(dp), as<const float>(dr), n, as<uint32_t>(dout));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(dev->stream));
-    std::vector<uint32_t> o(16u * (size_t)n);
-    HIP_TRY(hipMemcpy(o.data(), dout.get(), sizeof(uint32_t) * o.size(), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i) {
-        const uint32_t *e = o.data() + 16u * i;
-        prim[i] = e[0]; sampled[i] = e[1];
-        memcpy(y + 3u * i, e + 2, 12); memcpy(wi + 3u * i, e + 5, 12);
-        memcpy(dist + i, e + 8, 4); memcpy(cl + i, e + 9, 4); memcpy(p_a + i, e + 10, 4);
-        memcpy(E + 3u * i, e + 11, 12);
-    }
-    return LPT_OK;
-}
-
-// SPEC §24: the shading normal of the shading kernels (§12's, through kernels.h normal_map where the triangle has a map), once per element, for tests and tools
-int lpt_scene_gpu_shading_normal(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, const float *dirs, float *ns_out, uint32_t *mapped_out) {
-    if (!dev || !sg || (n && (!prim || !bary || !dirs || !ns_out || !mapped_out))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_shading_normal: null");
-    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_shading_normal: the scene belongs to another device");
-    for (uint32_t i = 0; i < n; ++i)
-        if (prim[i] >= sg->d.n_tris) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_shading_normal: element %u names triangle %u of %u", i, prim[i], sg->d.n_tris);
-    if (!n) return LPT_OK;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    DevMem dp, db, dd, dout;
-    TRY(dev_alloc(dp, sizeof(uint32_t) * (size_t)n));
-    TRY(dev_alloc(db, sizeof(float) * 2 * (size_t)n));
-    TRY(dev_alloc(dd, sizeof(float) * 3 * (size_t)n));
-    TRY(dev_alloc(dout, sizeof(uint32_t) * 4 * (size_t)n));
-    HIP_TRY(hipMemcpy(dp.get(), prim, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(db.get(), bary, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dd.get(), dirs, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_shading_normal, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, sg->d, as<const uint32_t>(dp), as<const float>(db), as<const float>(dd), n, as<uint32_t>(dout));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(dev->stream));
-    std::vector<uint32_t> o(4u * (size_t)n);
-    HIP_TRY(hipMemcpy(o.data(), dout.get(), sizeof(uint32_t) * o.size(), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i) {
-        memcpy(ns_out + 3u * i, o.data() + 4u * i, 12);
-        mapped_out[i] = o[4u * i + 3u];
-    }
-    return LPT_OK;
-}
-
-// SPEC §9: what a hit reads from its textures (kernels.h k_sample_textures: shade_hit's dispatch over texture_lookup / texture_lookup_pair / alpha_rejects), once per
-// element, for tests and tools.  out[n][16]
-int lpt_scene_gpu_sample_textures(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, float *out) {
-    if (!dev || !sg || (n && (!prim || !bary || !out))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_textures: null");
-    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_textures: the scene belongs to another device");
-    for (uint32_t i = 0; i < n; ++i)
-        if (prim[i] >= sg->d.n_tris) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_textures: element %u names triangle %u of %u", i, prim[i], sg->d.n_tris);
-    if (!n) return LPT_OK;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    DevMem dp, db, dout;
-    TRY(dev_alloc(dp, sizeof(uint32_t) * (size_t)n));
-    TRY(dev_alloc(db, sizeof(float) * 2 * (size_t)n));
-    TRY(dev_alloc(dout, sizeof(uint32_t) * 16 * (size_t)n));
-    HIP_TRY(hipMemcpy(dp.get(), prim, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(db.get(), bary, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_sample_textures, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, sg->d, as<const uint32_t>(dp), as<const float>(db), n, as<uint32_t>(dout));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(dev->stream));
-    HIP_TRY(hipMemcpy(out, dout.get(), sizeof(uint32_t) * 16 * (size_t)n, hipMemcpyDeviceToHost));
-    return LPT_OK;
-}
-
-// SPEC §21: the interface event of the shading kernels (kernels.h interface_sample), once per element, for tests and tools
-int lpt_interface_sample(lpt_device *dev, uint32_t n, const float *dirs, const float *ns, const float *ngf, const uint32_t *entering, const float *base, const float *ior,
-                         const uint32_t *thin, const float *r4, float *wi, float *weight, uint32_t *kind) {
-    if (!dev || (n && (!dirs || !ns || !ngf || !entering || !base || !ior || !thin || !r4 || !wi || !weight || !kind))) return fail(LPT_ERR_INVALID_ARG, "lpt_interface_sample: null");
-    if (!n) return LPT_OK;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    // one input block: d, Ns, Ngf, base (3 floats each), ior, r4, then entering and thin as uint32 — 16 words per element; one output block: wi, weight, kind — 7 words
-    std::vector<uint32_t> in(16u * (size_t)n, 0u);
-    for (size_t i = 0; i < n; ++i) {
-        uint32_t *e = in.data() + 16u * i;
-        memcpy(e, dirs + 3u * i, 12); memcpy(e + 3, ns + 3u * i, 12); memcpy(e + 6, ngf + 3u * i, 12); memcpy(e + 9, base + 3u * i, 12);
-        memcpy(e + 12, ior + i, 4); memcpy(e + 13, r4 + i, 4);
-        e[14] = entering[i] ? 1u : 0u; e[15] = thin[i] ? 1u : 0u;
-    }
-    DevMem din, dout;
-    TRY(dev_alloc(din, sizeof(uint32_t) * in.size()));
-    TRY(dev_alloc(dout, sizeof(uint32_t) * 7u * (size_t)n));
-    HIP_TRY(hipMemcpy(din.get(), in.data(), sizeof(uint32_t) * in.size(), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_interface_sample, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, as<const uint32_t>(din), n, as<uint32_t>(dout));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(dev->stream));
-    std::vector<uint32_t> res(7u * (size_t)n);
-    HIP_TRY(hipMemcpy(res.data(), dout.get(), sizeof(uint32_t) * res.size(), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i) {
-        memcpy(wi + 3u * i, res.data() + 7u * i, 12); memcpy(weight + 3u * i, res.data() + 7u * i + 3u, 12);
-        kind[i] = res[7u * i + 6u];
-    }
-    return LPT_OK;
-}
-
-// SPEC §10: the BSDF of the shading kernels as shade_hit sets it up (device_math.h make_surface, spec_probability, bsdf_eval, bsdf_sample), once per element,
-// for tests and tools.  The host rows are the kernel's words already: 20 in, 12 floats + ok out
-int lpt_bsdf_probe(lpt_device *dev, uint32_t n, const float *in, float *out, uint32_t *ok) {
-    if (!dev || (n && (!in || !out || !ok))) return fail(LPT_ERR_INVALID_ARG, "lpt_bsdf_probe: null");
-    if (!n) return LPT_OK;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    DevMem din, dout;
-    TRY(dev_alloc(din, sizeof(uint32_t) * 20u * (size_t)n));
-    TRY(dev_alloc(dout, sizeof(uint32_t) * 13u * (size_t)n));
-    HIP_TRY(hipMemcpy(din.get(), in, sizeof(uint32_t) * 20u * (size_t)n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_bsdf_probe, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, as<const uint32_t>(din), n, as<uint32_t>(dout));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(dev->stream));
-    std::vector<uint32_t> res(13u * (size_t)n);
-    HIP_TRY(hipMemcpy(res.data(), dout.get(), sizeof(uint32_t) * res.size(), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i) {
-        const uint32_t *e = res.data() + 13u * i;
-        memcpy(out + 12u * i, e, 20); memcpy(out + 12u * i + 5u, e + 6, 28);   // {pspec, f, pdf}, then {L_s, weight, pdf_s}
-        ok[i] = e[5];
-    }
-    return LPT_OK;
-}
-
 // ============================================================================ ProbeGPU
 int lpt_probe_upload(lpt_device *dev, const uint8_t *rgbe8, uint32_t w, uint32_t h, lpt_probe **out) {
     if (!dev || !rgbe8 || !w || !h || !out) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_upload: null or empty");
@@ -1260,76 +1145,6 @@ static int probe_env(lpt_probe *p, bool &has) {
     return LPT_OK;
 }
 
-static int env_alloc(DevMem &m, size_t bytes) {
-    void *p = nullptr;
-    HIP_TRY(hipMalloc(&p, bytes));
-    m.reset(p);
-    return LPT_OK;
-}
-
-int lpt_probe_sample(lpt_device *dev, lpt_probe *probe, const float *u, uint32_t n, float *dirs, float *pdf_s, float *radiance) {
-    if (!dev || !probe || (n && (!u || !dirs || !pdf_s || !radiance))) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_sample: null");
-    if (probe->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_sample: the probe belongs to another device");
-    if (!n) return LPT_OK;
-    bool has = false;
-    TRY(probe_env(probe, has));
-    if (!has) {
-        std::fill(dirs, dirs + 3 * (size_t)n, 0.0f); std::fill(pdf_s, pdf_s + n, 0.0f); std::fill(radiance, radiance + 3 * (size_t)n, 0.0f);
-        return LPT_OK;
-    }
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    DevMem du, dd, dp, dr;
-    TRY(env_alloc(du, sizeof(float) * 6 * (size_t)n));
-    TRY(env_alloc(dd, sizeof(float) * 3 * (size_t)n));
-    TRY(env_alloc(dp, sizeof(float) * (size_t)n));
-    TRY(env_alloc(dr, sizeof(float) * 3 * (size_t)n));
-    HIP_TRY(hipMemcpy(du.get(), u, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_env_sample, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, probe->d, probe->env, as<const float>(du), n,
-                       as<float>(dd), as<float>(dp), as<float>(dr));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(dev->stream));
-    HIP_TRY(hipMemcpy(dirs, dd.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(pdf_s, dp.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(radiance, dr.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
-    return LPT_OK;
-}
-
-int lpt_probe_pdf(lpt_device *dev, lpt_probe *probe, const float *dirs, uint32_t n, float *pdf_e) {
-    if (!dev || !probe || (n && (!dirs || !pdf_e))) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_pdf: null");
-    if (probe->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_pdf: the probe belongs to another device");
-    if (!n) return LPT_OK;
-    bool has = false;
-    TRY(probe_env(probe, has));
-    if (!has) { std::fill(pdf_e, pdf_e + n, 0.0f); return LPT_OK; }
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    DevMem dd, dp;
-    TRY(env_alloc(dd, sizeof(float) * 3 * (size_t)n));
-    TRY(env_alloc(dp, sizeof(float) * (size_t)n));
-    HIP_TRY(hipMemcpy(dd.get(), dirs, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_env_pdf, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, probe->env, as<const float>(dd), n, as<float>(dp));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(dev->stream));
-    HIP_TRY(hipMemcpy(pdf_e, dp.get(), sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    return LPT_OK;
-}
-
-// SPEC §9: env_lookup over caller-supplied directions (needs no distribution: any probe answers)
-int lpt_probe_lookup(lpt_device *dev, lpt_probe *probe, const float *dirs, uint32_t n, float *radiance) {
-    if (!dev || !probe || (n && (!dirs || !radiance))) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_lookup: null");
-    if (probe->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_lookup: the probe belongs to another device");
-    if (!n) return LPT_OK;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    DevMem dd, dr;
-    TRY(env_alloc(dd, sizeof(float) * 3 * (size_t)n));
-    TRY(env_alloc(dr, sizeof(float) * 3 * (size_t)n));
-    HIP_TRY(hipMemcpy(dd.get(), dirs, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_env_lookup, dim3(div_up(n, (uint32_t)kBlock)), dim3(kBlock), 0, dev->stream, probe->d, as<const float>(dd), n, as<float>(dr));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(dev->stream));
-    HIP_TRY(hipMemcpy(radiance, dr.get(), sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost));
-    return LPT_OK;
-}
-
 int lpt_probe_destroy(lpt_probe *p) {
     if (!p) return LPT_OK;
     hipSetDevice(p->dev->ordinal);
@@ -1343,62 +1158,164 @@ int lpt_probe_destroy(lpt_probe *p) {
     return LPT_OK;
 }
 
-// ============================================================================ ray queries
+// ============================================================================ per-element probes
+// One device function of the shading or traversal kernels over n caller-supplied elements, for tests and tools.  The kernels and their rows are probe_kernels.h's and
+// the upload / launch / read-back is run_probe's (n == 0 returns there, before the device is touched); what is left here is what each call checks and how the ABI's
+// arrays become rows and back.
+constexpr size_t kF1 = sizeof(float), kF3 = sizeof(float[3]);
+static_assert(sizeof(lpt_hit) == sizeof(float4), "k_query_closest writes lpt_hit as one float4");
+
+// SPEC §19: punctual_sample of light `light_index`, once per point
+int lpt_scene_gpu_sample_punctual(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t light_index, const float *points, uint32_t n, float *wi, float *dist, float *E) {
+    if (!dev || !sg || (n && (!points || !wi || !dist || !E))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_punctual: null");
+    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_punctual: the scene belongs to another device");
+    if (light_index >= sg->d.n_punctual) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_punctual: light %u of %u", light_index, sg->d.n_punctual);
+    return run_probe(dev, n, kBlock, {{points, kF3}}, {{wi, kF3}, {dist, kF1}, {E, kF3}}, [&](dim3 grid, const DevMem *d) {
+        hipLaunchKernelGGL(k_punctual_sample, grid, dim3(kBlock), 0, dev->stream, sg->d, light_index, as<const float>(d[0]), n, as<float>(d[1]), as<float>(d[2]), as<float>(d[3]));
+    });
+}
+
+// SPEC §23: emitter_sample, once per point with its (ra, rb, r1, r2)
+int lpt_scene_gpu_sample_emitter(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const float *points, const float *rands, uint32_t *prim, uint32_t *sampled, float *y,
+                                 float *wi, float *dist, float *cl, float *p_a, float *E) {
+    if (!dev || !sg || (n && (!points || !rands || !prim || !sampled || !y || !wi || !dist || !cl || !p_a || !E))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_emitter: null");
+    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_emitter: the scene belongs to another device");
+    if (!sg->d.n_emit) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_emitter: the scene has no emitter distribution");
+    std::vector<EmitterRow> rows(n);
+    TRY((run_probe(dev, n, kBlock, {{points, kF3}, {rands, sizeof(float[4])}}, {{rows.data(), sizeof(EmitterRow)}}, [&](dim3 grid, const DevMem *d) {
+        hipLaunchKernelGGL(k_emitter_sample, grid, dim3(kBlock), 0, dev->stream, sg->d, as<const float>(d[0]), as<const float>(d[1]), n, as<EmitterRow>(d[2]));
+    })));
+    for (size_t i = 0; i < n; ++i) {
+        const EmitterRow &r = rows[i];
+        prim[i] = r.prim; sampled[i] = r.sampled; dist[i] = r.dist; cl[i] = r.cl; p_a[i] = r.p_a;
+        memcpy(y + 3u * i, r.y, kF3); memcpy(wi + 3u * i, r.wi, kF3); memcpy(E + 3u * i, r.E, kF3);
+    }
+    return LPT_OK;
+}
+
+// SPEC §24: the shading normal of a hit (§12's, through normal_map where the triangle has a map), once per (prim, bary, direction)
+int lpt_scene_gpu_shading_normal(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, const float *dirs, float *ns_out, uint32_t *mapped_out) {
+    if (!dev || !sg || (n && (!prim || !bary || !dirs || !ns_out || !mapped_out))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_shading_normal: null");
+    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_shading_normal: the scene belongs to another device");
+    TRY(check_prims("lpt_scene_gpu_shading_normal", sg->d, prim, n));
+    std::vector<NormalRow> rows(n);
+    TRY((run_probe(dev, n, kBlock, {{prim, sizeof(uint32_t)}, {bary, sizeof(float[2])}, {dirs, kF3}}, {{rows.data(), sizeof(NormalRow)}}, [&](dim3 grid, const DevMem *d) {
+        hipLaunchKernelGGL(k_shading_normal, grid, dim3(kBlock), 0, dev->stream, sg->d, as<const uint32_t>(d[0]), as<const float>(d[1]), as<const float>(d[2]), n, as<NormalRow>(d[3]));
+    })));
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(ns_out + 3u * i, rows[i].Ns, kF3);
+        mapped_out[i] = rows[i].mapped;
+    }
+    return LPT_OK;
+}
+
+// SPEC §9: what a hit reads from its textures (shade_hit's dispatch over texture_lookup / texture_lookup_pair / alpha_rejects), once per (prim, bary).  out[n] is the row
+int lpt_scene_gpu_sample_textures(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, float *out) {
+    if (!dev || !sg || (n && (!prim || !bary || !out))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_textures: null");
+    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_sample_textures: the scene belongs to another device");
+    TRY(check_prims("lpt_scene_gpu_sample_textures", sg->d, prim, n));
+    return run_probe(dev, n, kBlock, {{prim, sizeof(uint32_t)}, {bary, sizeof(float[2])}}, {{out, sizeof(TextureRow)}}, [&](dim3 grid, const DevMem *d) {
+        hipLaunchKernelGGL(k_sample_textures, grid, dim3(kBlock), 0, dev->stream, sg->d, as<const uint32_t>(d[0]), as<const float>(d[1]), n, as<TextureRow>(d[2]));
+    });
+}
+
+// SPEC §21: interface_sample, once per element
+int lpt_interface_sample(lpt_device *dev, uint32_t n, const float *dirs, const float *ns, const float *ngf, const uint32_t *entering, const float *base, const float *ior,
+                         const uint32_t *thin, const float *r4, float *wi, float *weight, uint32_t *kind) {
+    if (!dev || (n && (!dirs || !ns || !ngf || !entering || !base || !ior || !thin || !r4 || !wi || !weight || !kind))) return fail(LPT_ERR_INVALID_ARG, "lpt_interface_sample: null");
+    std::vector<InterfaceRowIn> in(n);
+    for (size_t i = 0; i < n; ++i) {
+        InterfaceRowIn &e = in[i];
+        memcpy(e.d, dirs + 3u * i, kF3); memcpy(e.Ns, ns + 3u * i, kF3); memcpy(e.Ngf, ngf + 3u * i, kF3); memcpy(e.base, base + 3u * i, kF3);
+        e.ior = ior[i]; e.r4 = r4[i];
+        e.entering = entering[i] ? 1u : 0u; e.thin = thin[i] ? 1u : 0u;
+    }
+    std::vector<InterfaceRowOut> res(n);
+    TRY((run_probe(dev, n, kBlock, {{in.data(), sizeof(InterfaceRowIn)}}, {{res.data(), sizeof(InterfaceRowOut)}}, [&](dim3 grid, const DevMem *d) {
+        hipLaunchKernelGGL(k_interface_sample, grid, dim3(kBlock), 0, dev->stream, as<const InterfaceRowIn>(d[0]), n, as<InterfaceRowOut>(d[1]));
+    })));
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(wi + 3u * i, res[i].wi, kF3); memcpy(weight + 3u * i, res[i].weight, kF3);
+        kind[i] = res[i].kind;
+    }
+    return LPT_OK;
+}
+
+// SPEC §10: the BSDF as shade_hit sets it up (device_math.h make_surface, spec_probability, bsdf_eval, bsdf_sample), once per element.  in[n] is the row;
+// out[n] = {pspec, f, pdf}, then {L_s, weight, pdf_s}: the row without its `ok`
+int lpt_bsdf_probe(lpt_device *dev, uint32_t n, const float *in, float *out, uint32_t *ok) {
+    if (!dev || (n && (!in || !out || !ok))) return fail(LPT_ERR_INVALID_ARG, "lpt_bsdf_probe: null");
+    std::vector<BsdfRowOut> res(n);
+    TRY((run_probe(dev, n, kBlock, {{in, sizeof(BsdfRowIn)}}, {{res.data(), sizeof(BsdfRowOut)}}, [&](dim3 grid, const DevMem *d) {
+        hipLaunchKernelGGL(k_bsdf_probe, grid, dim3(kBlock), 0, dev->stream, as<const BsdfRowIn>(d[0]), n, as<BsdfRowOut>(d[1]));
+    })));
+    for (size_t i = 0; i < n; ++i) {
+        const BsdfAbiOut o{res[i].eval, res[i].sampled};
+        memcpy(out + 12u * i, &o, sizeof o);
+        ok[i] = res[i].ok;
+    }
+    return LPT_OK;
+}
+
+// SPEC §18: env_sample (and env_lookup along the sample), once per draw u = (r6, r7, r8, r9, r1, r2); all zero for a probe without a distribution
+int lpt_probe_sample(lpt_device *dev, lpt_probe *probe, const float *u, uint32_t n, float *dirs, float *pdf_s, float *radiance) {
+    if (!dev || !probe || (n && (!u || !dirs || !pdf_s || !radiance))) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_sample: null");
+    if (probe->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_sample: the probe belongs to another device");
+    if (!n) return LPT_OK;   // (before probe_env: it reads the probe back)
+    bool has = false;
+    TRY(probe_env(probe, has));
+    if (!has) {
+        std::fill(dirs, dirs + 3 * (size_t)n, 0.0f); std::fill(pdf_s, pdf_s + n, 0.0f); std::fill(radiance, radiance + 3 * (size_t)n, 0.0f);
+        return LPT_OK;
+    }
+    return run_probe(dev, n, kBlock, {{u, sizeof(float[6])}}, {{dirs, kF3}, {pdf_s, kF1}, {radiance, kF3}}, [&](dim3 grid, const DevMem *d) {
+        hipLaunchKernelGGL(k_env_sample, grid, dim3(kBlock), 0, dev->stream, probe->d, probe->env, as<const float>(d[0]), n, as<float>(d[1]), as<float>(d[2]), as<float>(d[3]));
+    });
+}
+
+// SPEC §18: env_pdf, once per direction; zero for a probe without a distribution
+int lpt_probe_pdf(lpt_device *dev, lpt_probe *probe, const float *dirs, uint32_t n, float *pdf_e) {
+    if (!dev || !probe || (n && (!dirs || !pdf_e))) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_pdf: null");
+    if (probe->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_pdf: the probe belongs to another device");
+    if (!n) return LPT_OK;   // (before probe_env, as above)
+    bool has = false;
+    TRY(probe_env(probe, has));
+    if (!has) { std::fill(pdf_e, pdf_e + n, 0.0f); return LPT_OK; }
+    return run_probe(dev, n, kBlock, {{dirs, kF3}}, {{pdf_e, kF1}}, [&](dim3 grid, const DevMem *d) {
+        hipLaunchKernelGGL(k_env_pdf, grid, dim3(kBlock), 0, dev->stream, probe->env, as<const float>(d[0]), n, as<float>(d[1]));
+    });
+}
+
+// SPEC §9: env_lookup, once per direction (needs no distribution: any probe answers)
+int lpt_probe_lookup(lpt_device *dev, lpt_probe *probe, const float *dirs, uint32_t n, float *radiance) {
+    if (!dev || !probe || (n && (!dirs || !radiance))) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_lookup: null");
+    if (probe->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_lookup: the probe belongs to another device");
+    return run_probe(dev, n, kBlock, {{dirs, kF3}}, {{radiance, kF3}}, [&](dim3 grid, const DevMem *d) {
+        hipLaunchKernelGGL(k_env_lookup, grid, dim3(kBlock), 0, dev->stream, probe->d, as<const float>(d[0]), n, as<float>(d[1]));
+    });
+}
+
+// the ray queries: traverse (and intersect_lights behind a closest hit), one ray per lane of a traversal block; MASK where the scene has alpha masks (SPEC §20)
 int lpt_trace_closest(lpt_device *dev, const lpt_scene_gpu *sg, const float *origins, const float *dirs, uint32_t n, lpt_hit *out) {
     if (!dev || !sg || (n && (!origins || !dirs || !out))) return fail(LPT_ERR_INVALID_ARG, "lpt_trace_closest: null");
-    if (!n) return LPT_OK;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    std::vector<float4> o(n), d(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        o[i] = make_float4(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], 0.f);
-        d[i] = make_float4(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], -1.f);
-    }
-    float4 *dO = nullptr, *dD = nullptr, *dH = nullptr;
-    int st = LPT_OK;
-    hipError_t e = hipMalloc(&dO, sizeof(float4) * n);
-    if (e == hipSuccess) e = hipMalloc(&dD, sizeof(float4) * n);
-    if (e == hipSuccess) e = hipMalloc(&dH, sizeof(float4) * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(dO, o.data(), sizeof(float4) * n, hipMemcpyHostToDevice, dev->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dD, d.data(), sizeof(float4) * n, hipMemcpyHostToDevice, dev->stream);
-    if (e == hipSuccess) {
-        if (sg->d.n_alpha) hipLaunchKernelGGL(k_query_closest<true>, dim3(div_up(n, kTraceBlock)), dim3(kTraceBlock), stack_bytes(sg->d), dev->stream, sg->d, dO, dD, dH, n);   // SPEC §20
-        else hipLaunchKernelGGL(k_query_closest<false>, dim3(div_up(n, kTraceBlock)), dim3(kTraceBlock), stack_bytes(sg->d), dev->stream, sg->d, dO, dD, dH, n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dH, sizeof(float4) * n, hipMemcpyDeviceToHost, dev->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
-    if (e != hipSuccess) st = fail(LPT_ERR_HIP, "lpt_trace_closest: %s", hipGetErrorString(e));
-    hipFree(dO); hipFree(dD); hipFree(dH);
-    return st;
+    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_trace_closest: the scene belongs to another device");
+    std::vector<float4> o, d;
+    pack_rays(origins, dirs, nullptr, n, o, d);
+    return run_probe(dev, n, kTraceBlock, {{o.data(), sizeof(float4)}, {d.data(), sizeof(float4)}}, {{out, sizeof(lpt_hit)}}, [&](dim3 grid, const DevMem *m) {
+        const auto k = sg->d.n_alpha ? k_query_closest<true> : k_query_closest<false>;
+        hipLaunchKernelGGL(k, grid, dim3(kTraceBlock), stack_bytes(sg->d), dev->stream, sg->d, as<const float4>(m[0]), as<const float4>(m[1]), as<float4>(m[2]), n);
+    });
 }
 
 int lpt_trace_occluded(lpt_device *dev, const lpt_scene_gpu *sg, const float *origins, const float *dirs, const float *tmax, uint32_t n, uint8_t *out) {
     if (!dev || !sg || (n && (!origins || !dirs || !tmax || !out))) return fail(LPT_ERR_INVALID_ARG, "lpt_trace_occluded: null");
-    if (!n) return LPT_OK;
-    HIP_TRY(hipSetDevice(dev->ordinal));
-    std::vector<float4> o(n), d(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        o[i] = make_float4(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], tmax[i]);
-        d[i] = make_float4(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], 0.f);
-    }
-    float4 *dO = nullptr, *dD = nullptr;
-    uint8_t *dR = nullptr;
-    int st = LPT_OK;
-    hipError_t e = hipMalloc(&dO, sizeof(float4) * n);
-    if (e == hipSuccess) e = hipMalloc(&dD, sizeof(float4) * n);
-    if (e == hipSuccess) e = hipMalloc(&dR, n);
-    if (e == hipSuccess) e = hipMemcpyAsync(dO, o.data(), sizeof(float4) * n, hipMemcpyHostToDevice, dev->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dD, d.data(), sizeof(float4) * n, hipMemcpyHostToDevice, dev->stream);
-    if (e == hipSuccess) {
-        if (sg->d.n_alpha) hipLaunchKernelGGL(k_query_occluded<true>, dim3(div_up(n, kTraceBlock)), dim3(kTraceBlock), stack_bytes(sg->d), dev->stream, sg->d, dO, dD, dR, n);   // SPEC §20
-        else hipLaunchKernelGGL(k_query_occluded<false>, dim3(div_up(n, kTraceBlock)), dim3(kTraceBlock), stack_bytes(sg->d), dev->stream, sg->d, dO, dD, dR, n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dR, n, hipMemcpyDeviceToHost, dev->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
-    if (e != hipSuccess) st = fail(LPT_ERR_HIP, "lpt_trace_occluded: %s", hipGetErrorString(e));
-    hipFree(dO); hipFree(dD); hipFree(dR);
-    return st;
+    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_trace_occluded: the scene belongs to another device");
+    std::vector<float4> o, d;
+    pack_rays(origins, dirs, tmax, n, o, d);
+    return run_probe(dev, n, kTraceBlock, {{o.data(), sizeof(float4)}, {d.data(), sizeof(float4)}}, {{out, sizeof(uint8_t)}}, [&](dim3 grid, const DevMem *m) {
+        const auto k = sg->d.n_alpha ? k_query_occluded<true> : k_query_occluded<false>;
+        hipLaunchKernelGGL(k, grid, dim3(kTraceBlock), stack_bytes(sg->d), dev->stream, sg->d, as<const float4>(m[0]), as<const float4>(m[1]), as<uint8_t>(m[2]), n);
+    });
 }
 
 // ============================================================================ Renderer

@@ -89,7 +89,7 @@ struct DScene {
     float grid_lo[3], grid_step[3];   // the scene grid of the node origins (common.h scene_grid): origin = grid_lo + o * grid_step
     float pad_abs;               // the scene-wide part of the triangle padding (refit / LBVH; bvh.cpp padded_box): kScenePad x the scene's largest |coordinate|
     // SPEC §19: punctual lights, four float4 per light (lpt_punctual_light verbatim).  Read only by the PUNCT instantiations of shade_hit / k_shade / k_path
-    // (the ones that run while n_punctual != 0) and by k_punctual_sample
+    // (the ones that run while n_punctual != 0) and by k_punctual_sample (probe_kernels.h)
     const float4 *punctual;
     uint32_t n_punctual;
     // SPEC §20: alpha-masked materials.  alpha_tri[prim] = 0 for an opaque triangle, else 1 + the index of its record {cutoff, color.w, bits of the PLAIN image index
@@ -110,12 +110,12 @@ struct DScene {
     uint32_t n_emis;
     // SPEC §23: the emitter distribution, one entry per emissive triangle of non-zero area in prim-id order: {q, bits of the alias slot, bits of the slot's own prim,
     // bits of the alias slot's prim} — the column of a Vose alias table with both outcomes' triangles in it, so a pick is ONE dependent load.  emit_inv_W = float(1 / sum of
-    // the weights area x lum(Le)).  Null / 0 without a distribution; read only by the ESAMP instantiations of shade_hit / k_shade and by k_emitter_sample
+    // the weights area x lum(Le)).  Null / 0 without a distribution; read only by the ESAMP instantiations of shade_hit / k_shade and by k_emitter_sample (probe_kernels.h)
     const float4 *emit_tab;
     uint32_t n_emit;
     float emit_inv_W;
     // SPEC §24: normal-mapped materials.  nmap_tri[prim] = 0 for a triangle without a normal map, else 1 + the index of its record {bits of the PLAIN image index, scale, 0, 0}.
-    // Null / 0 for a scene without a normal-mapped material in use; read only by the NMAP instantiations of shade_hit / k_shade and by k_shading_normal
+    // Null / 0 for a scene without a normal-mapped material in use; read only by the NMAP instantiations of shade_hit / k_shade and by k_shading_normal (probe_kernels.h)
     const uint32_t *nmap_tri;
     const float4 *nmap_recs;
     uint32_t n_nmap;
@@ -1420,21 +1420,6 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8))
     }
 }
 
-// stand-alone closest-hit query (lpt_trace_closest): one ray per lane, no refill
-template <bool MASK = false>
-__global__ __launch_bounds__(kTraceBlock) void k_query_closest(DScene sc, const float4 *o, const float4 *d, float4 *hits, uint32_t n) {
-    uint2 *stack = reinterpret_cast<uint2 *>(lds_dyn) + threadIdx.x;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 o4 = o[i], d4 = d[i];
-    const f3 oo = mk3(o4.x, o4.y, o4.z), dd = mk3(d4.x, d4.y, d4.z);
-    Hit h;
-    uint32_t a = 0, b = 0;
-    traverse<false, false, MASK>(sc, oo, dd, LPT_T_INF, stack, h, a, b);
-    intersect_lights(sc, oo, dd, h);
-    hits[i] = make_float4(h.t, h.u, h.v, __uint_as_float(h.prim));
-}
-
 // ------------------------------------------------------------------ SPEC §9 textures / environment
 __device__ __forceinline__ int wrap_i(int x, int n) {
     if ((n & (n - 1)) == 0) return x & (n - 1);  // power-of-two sizes (the usual case): same value, no division
@@ -1586,33 +1571,6 @@ __device__ __forceinline__ float env_pdf(const DEnv &ev, f3 d) {
     if (!(s > 0.0f)) return 0.0f;
     return ev.cols[(size_t)cy * W + cx].z / (kTwoPiSq * s);
 }
-// lpt_probe_sample / lpt_probe_pdf: the functions shade_hit runs, one direction per thread.  u: n x {r6, r7, r8, r9, r1, r2};
-// a draw without a sample gives direction 0, density 0, radiance 0
-__global__ __launch_bounds__(kBlock) void k_env_sample(DProbe probe, DEnv ev, const float *u, uint32_t n, float *dirs, float *pdf_s, float *radiance) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float *r = u + 6u * (size_t)i;
-    f3 d;
-    float ps = 0.0f;
-    f3 Le = mk3(0.f, 0.f, 0.f);
-    if (env_sample(ev, r[0], r[1], r[2], r[3], r[4], r[5], d, ps)) Le = env_lookup(probe, d);
-    else { d = mk3(0.f, 0.f, 0.f); ps = 0.0f; }
-    dirs[3u * (size_t)i] = d.x; dirs[3u * (size_t)i + 1u] = d.y; dirs[3u * (size_t)i + 2u] = d.z;
-    pdf_s[i] = ps;
-    radiance[3u * (size_t)i] = Le.x; radiance[3u * (size_t)i + 1u] = Le.y; radiance[3u * (size_t)i + 2u] = Le.z;
-}
-__global__ __launch_bounds__(kBlock) void k_env_pdf(DEnv ev, const float *dirs, uint32_t n, float *pdf_e) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    pdf_e[i] = env_pdf(ev, mk3(dirs[3u * (size_t)i], dirs[3u * (size_t)i + 1u], dirs[3u * (size_t)i + 2u]));
-}
-// lpt_probe_lookup: SPEC §9's env_lookup, the function a miss and every environment sample run, one direction per thread
-__global__ __launch_bounds__(kBlock) void k_env_lookup(DProbe probe, const float *dirs, uint32_t n, float *radiance) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const f3 Le = env_lookup(probe, mk3(dirs[3u * (size_t)i], dirs[3u * (size_t)i + 1u], dirs[3u * (size_t)i + 2u]));
-    radiance[3u * (size_t)i] = Le.x; radiance[3u * (size_t)i + 1u] = Le.y; radiance[3u * (size_t)i + 2u] = Le.z;
-}
 
 // ------------------------------------------------------------------ punctual lights (SPEC §19)
 // One sample of punctual light `l` seen from Po: the unit direction towards it, the distance (LPT_T_INF: directional) and the incident term E = colour x intensity x
@@ -1637,18 +1595,6 @@ __device__ __forceinline__ bool punctual_sample(const DScene &sc, const uint32_t
     const float g = (att * wr) * (s * s);
     E = mk3(col.x * g, col.y * g, col.z * g);
     return true;
-}
-// lpt_scene_gpu_sample_punctual: the function shade_hit runs, one point per thread; a point without a sample gives zeros
-__global__ __launch_bounds__(kBlock) void k_punctual_sample(DScene sc, uint32_t l, const float *points, uint32_t n, float *wi_out, float *dist_out, float *E_out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const size_t j = 3u * (size_t)i;
-    f3 wi, E;
-    float dist;
-    if (!punctual_sample(sc, l, mk3(points[j], points[j + 1u], points[j + 2u]), wi, dist, E)) { wi = mk3(0.f, 0.f, 0.f); E = wi; dist = 0.0f; }
-    wi_out[j] = wi.x; wi_out[j + 1u] = wi.y; wi_out[j + 2u] = wi.z;
-    dist_out[i] = dist;
-    E_out[j] = E.x; E_out[j + 1u] = E.y; E_out[j + 2u] = E.z;
 }
 
 // ------------------------------------------------------------------ emitter sampling (SPEC §23)
@@ -1698,27 +1644,6 @@ __device__ __forceinline__ bool emitter_sample(const DScene &sc, const float *s_
     }
     return true;
 }
-// lpt_scene_gpu_sample_emitter: the function shade_hit runs, one point per thread.  rands: (ra, rb, r1, r2) per point; out: 16 words per point
-// {prim, sampled (1 / 0), y, wi, dist, cl, p_A, E, 0}; a point without a sample keeps its prim and gives zeros
-__global__ __launch_bounds__(kBlock) void k_emitter_sample(DScene sc, const float *points, const float *rands, uint32_t n, uint32_t *out) {
-    __shared__ float s_lut[256];
-    s_lut[threadIdx.x] = sc.srgb_lut[threadIdx.x];  // kBlock == 256
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float *pt = points + 3u * (size_t)i, *r = rands + 4u * (size_t)i;
-    EmitterSample es;
-    const bool ok = emitter_sample(sc, s_lut, r[0], r[1], r[2], r[3], mk3(pt[0], pt[1], pt[2]), es);
-    uint32_t *o = out + 16u * (size_t)i;
-    for (uint32_t k = 0; k < 16u; ++k) o[k] = 0u;
-    o[0] = es.prim; o[1] = ok ? 1u : 0u;
-    if (ok) {
-        o[2] = __float_as_uint(es.y.x); o[3] = __float_as_uint(es.y.y); o[4] = __float_as_uint(es.y.z);
-        o[5] = __float_as_uint(es.wi.x); o[6] = __float_as_uint(es.wi.y); o[7] = __float_as_uint(es.wi.z);
-        o[8] = __float_as_uint(es.dist); o[9] = __float_as_uint(es.cl); o[10] = __float_as_uint(es.pA);
-        o[11] = __float_as_uint(es.E.x); o[12] = __float_as_uint(es.E.y); o[13] = __float_as_uint(es.E.z);
-    }
-}
 
 // ------------------------------------------------------------------ normal maps (SPEC §24)
 // §24's arithmetic once: nm = 1 + the triangle's record, Nv §12's interpolated normal before either flip, Ngf the geometric normal flipped against d, flip = §12's own
@@ -1747,97 +1672,6 @@ __device__ __forceinline__ bool normal_map(const DScene &sc, const float *s_lut,
     if (!(dot(Nm, Ngf) > 0.0f)) return false;   // the map pushed the normal under the surface
     Ns = Nm;
     return true;
-}
-// lpt_scene_gpu_shading_normal: §12's shading normal of a hit (prim, bary) seen along d, through normal_map where the triangle has a map; one element per thread.
-// out: 4 words per element {Ns, mapped (1 / 0)}; a degenerate triangle (l2 = 0) gives zeros
-__global__ __launch_bounds__(kBlock) void k_shading_normal(DScene sc, const uint32_t *prims, const float *bary, const float *dirs, uint32_t n, uint32_t *out) {
-    __shared__ float s_lut[256];
-    s_lut[threadIdx.x] = sc.srgb_lut[threadIdx.x];  // kBlock == 256
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t prim = prims[i];
-    const float hu = bary[2u * (size_t)i], hv = bary[2u * (size_t)i + 1u];
-    const f3 d = mk3(dirs[3u * (size_t)i], dirs[3u * (size_t)i + 1u], dirs[3u * (size_t)i + 2u]);
-    const float4 *tv = sc.tri_verts + kTriRec * (size_t)prim;
-    const float4 P0 = tv[0], N0 = tv[1], P1 = tv[2], N1 = tv[3], P2 = tv[4], N2 = tv[5];
-    const uint32_t nm = sc.n_nmap ? sc.nmap_tri[prim] : 0u;
-    const float bw = (1.0f - hu) - hv;
-    const f3 p0 = mk3(P0.x, P0.y, P0.z), p1 = mk3(P1.x, P1.y, P1.z), p2 = mk3(P2.x, P2.y, P2.z);
-    f3 Ng = cross(p1 - p0, p2 - p0);
-    const float l2 = dot(Ng, Ng);
-    f3 Ns = mk3(0.0f, 0.0f, 0.0f);
-    bool mapped = false;
-    if (l2 > 0.0f) {
-        Ng = Ng * (1.0f / sqrtf(l2));
-        Ns = mk3((N0.x * bw + N1.x * hu) + N2.x * hv, (N0.y * bw + N1.y * hu) + N2.y * hv, (N0.z * bw + N1.z * hu) + N2.z * hv);
-        const float n2 = dot(Ns, Ns);
-        Ns = n2 > 0.0f ? Ns * (1.0f / sqrtf(n2)) : Ng;
-        if (dot(Ng, d) > 0.0f) Ng = neg(Ng);
-        const f3 Nv = Ns;
-        const bool flip = dot(Ns, Ng) < 0.0f;
-        if (flip) Ns = neg(Ns);
-        const float tu = (P0.w * bw + P1.w * hu) + P2.w * hv;
-        const float tvv = (N0.w * bw + N1.w * hu) + N2.w * hv;
-        if (nm != 0u) mapped = normal_map(sc, s_lut, nm, Nv, Ng, flip, p1 - p0, p2 - p0, P1.w - P0.w, N1.w - N0.w, P2.w - P0.w, N2.w - N0.w, tu, tvv, Ns);
-    }
-    uint32_t *o = out + 4u * (size_t)i;
-    o[0] = __float_as_uint(Ns.x); o[1] = __float_as_uint(Ns.y); o[2] = __float_as_uint(Ns.z); o[3] = mapped ? 1u : 0u;
-}
-
-// lpt_scene_gpu_sample_textures: what a hit (prim, bary) reads from its textures (SPEC §9), through the functions and the dispatch of shade_hit (which is repeated
-// here, not shared: k_shade sits at its register limit), one element per thread.  out: 16 words per element {albedo rgb, mra g, mra b (1 without the texture),
-// emissive texel rgb (1 without one), normal-map texel xyz, raw (0 without one), alpha_rejects (1 / 0; 0 in a scene without masks), tu, tv, 0, 0}
-__global__ __launch_bounds__(kBlock) void k_sample_textures(DScene sc, const uint32_t *prims, const float *bary, uint32_t n, uint32_t *out) {
-    __shared__ float s_lut[256];
-    s_lut[threadIdx.x] = sc.srgb_lut[threadIdx.x];  // kBlock == 256
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t prim = prims[i];
-    const float hu = bary[2u * (size_t)i], hv = bary[2u * (size_t)i + 1u];
-    const float4 *tv = sc.tri_verts + kTriRec * (size_t)prim;
-    const float4 P0 = tv[0], N0 = tv[1], P1 = tv[2], N1 = tv[3], P2 = tv[4], N2 = tv[5];
-    const float4 mp = tv[7];
-    const uint32_t em = sc.n_emis ? sc.emis_tri[prim] : 0u;
-    const uint32_t nm = sc.n_nmap ? sc.nmap_tri[prim] : 0u;
-    const float bw = (1.0f - hu) - hv;
-    const float tu = (P0.w * bw + P1.w * hu) + P2.w * hv;
-    const float tvv = (N0.w * bw + N1.w * hu) + N2.w * hv;
-    f3 alb = mk3(1.0f, 1.0f, 1.0f), emi = mk3(1.0f, 1.0f, 1.0f), nrm = mk3(0.0f, 0.0f, 0.0f);
-    float mg = 1.0f, mb = 1.0f;
-    const uint32_t atex = __float_as_uint(mp.z), mtex = __float_as_uint(mp.w);
-    if ((atex >> 30) == 1u) {   // kPairedBit set, not LPT_INVALID_INDEX
-        texture_lookup_pair(sc, s_lut, atex & ~kPairedBit, mtex, tu, tvv, alb, mg, mb);
-    } else {
-        if (atex < sc.n_images) {
-            const float4 tex = texture_lookup(sc, s_lut, atex, tu, tvv, true);
-            alb = mk3(tex.x, tex.y, tex.z);
-        }
-        if (mtex < sc.n_images) {
-            const float4 tex = texture_lookup(sc, s_lut, mtex, tu, tvv, false);
-            mg = tex.y; mb = tex.z;
-        }
-    }
-    if (em != 0u) {
-        const uint32_t etex = __float_as_uint(sc.emis_recs[em - 1u].w);
-        if (etex < sc.n_images) {
-            const float4 tex = texture_lookup(sc, s_lut, etex, tu, tvv, true);
-            emi = mk3(tex.x, tex.y, tex.z);
-        }
-    }
-    if (nm != 0u) {
-        const float4 tex = texture_lookup(sc, s_lut, __float_as_uint(sc.nmap_recs[nm - 1u].x), tu, tvv, false);
-        nrm = mk3(tex.x, tex.y, tex.z);
-    }
-    const bool cut = sc.n_alpha != 0u && alpha_rejects(sc, prim, hu, hv);
-    uint32_t *o = out + 16u * (size_t)i;
-    o[0] = __float_as_uint(alb.x); o[1] = __float_as_uint(alb.y); o[2] = __float_as_uint(alb.z);
-    o[3] = __float_as_uint(mg); o[4] = __float_as_uint(mb);
-    o[5] = __float_as_uint(emi.x); o[6] = __float_as_uint(emi.y); o[7] = __float_as_uint(emi.z);
-    o[8] = __float_as_uint(nrm.x); o[9] = __float_as_uint(nrm.y); o[10] = __float_as_uint(nrm.z);
-    o[11] = cut ? 1u : 0u;
-    o[12] = __float_as_uint(tu); o[13] = __float_as_uint(tvv); o[14] = 0u; o[15] = 0u;
 }
 
 // ------------------------------------------------------------------ transmission (SPEC §21)
@@ -1871,42 +1705,6 @@ __device__ __forceinline__ InterfaceOut interface_sample(const f3 d, const f3 Ns
     if (!interface_once(d, N, Ngf, eta, thin, r4, io.wi, io.transmit)) interface_once(d, Ngf, Ngf, eta, thin, r4, io.wi, io.transmit);
     io.weight = io.transmit ? base : mk3(1.0f, 1.0f, 1.0f);
     return io;
-}
-// lpt_interface_sample: the function shade_hit runs, one element per thread.  in: 16 words per element {d, Ns, Ngf, base, ior, r4, entering, thin}; out: 7 words {wi, weight, kind}
-__global__ __launch_bounds__(kBlock) void k_interface_sample(const uint32_t *in, uint32_t n, uint32_t *out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t *e = in + 16u * (size_t)i;
-    auto f = [&](uint32_t k) { return __uint_as_float(e[k]); };
-    const InterfaceOut io = interface_sample(mk3(f(0), f(1), f(2)), mk3(f(3), f(4), f(5)), mk3(f(6), f(7), f(8)), e[14] != 0u, mk3(f(9), f(10), f(11)), f(12), e[15] != 0u, f(13));
-    uint32_t *o = out + 7u * (size_t)i;
-    o[0] = __float_as_uint(io.wi.x); o[1] = __float_as_uint(io.wi.y); o[2] = __float_as_uint(io.wi.z);
-    o[3] = __float_as_uint(io.weight.x); o[4] = __float_as_uint(io.weight.y); o[5] = __float_as_uint(io.weight.z);
-    o[6] = io.transmit ? 1u : 0u;
-}
-// lpt_bsdf_probe: §10 as shade_hit sets it up (make_surface, the clamped NoV, spec_probability), then bsdf_eval on L and bsdf_sample on (r3, r4, r5); one element per
-// thread.  in: 20 words per element {base, roughness, metallic, N, Ng, V, L, r3, r4, r5}; out: 13 words {pspec, f, pdf, ok, L_s, weight, pdf_s} (a failed sample: zeros)
-__global__ __launch_bounds__(kBlock) void k_bsdf_probe(const uint32_t *in, uint32_t n, uint32_t *out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t *e = in + 20u * (size_t)i;
-    auto g = [&](uint32_t k) { return __uint_as_float(e[k]); };
-    const f3 N = mk3(g(5), g(6), g(7)), Ng = mk3(g(8), g(9), g(10)), V = mk3(g(11), g(12), g(13));
-    const Surface sf = make_surface(mk3(g(0), g(1), g(2)), g(3), g(4));
-    const float NoV = max2(dot(N, V), LPT_MIN_NOV);
-    const float pspec = spec_probability(sf, NoV);
-    f3 f, Ls = mk3(0.0f, 0.0f, 0.0f), w = mk3(0.0f, 0.0f, 0.0f);
-    float pdf, pdf_s = 0.0f;
-    bsdf_eval(sf, N, Ng, V, NoV, pspec, mk3(g(14), g(15), g(16)), f, pdf);
-    const bool ok = bsdf_sample(sf, N, Ng, V, NoV, pspec, g(17), g(18), g(19), Ls, w, pdf_s);
-    uint32_t *o = out + 13u * (size_t)i;
-    o[0] = __float_as_uint(pspec);
-    o[1] = __float_as_uint(f.x); o[2] = __float_as_uint(f.y); o[3] = __float_as_uint(f.z);
-    o[4] = __float_as_uint(pdf);
-    o[5] = ok ? 1u : 0u;
-    o[6] = __float_as_uint(Ls.x); o[7] = __float_as_uint(Ls.y); o[8] = __float_as_uint(Ls.z);
-    o[9] = __float_as_uint(w.x); o[10] = __float_as_uint(w.y); o[11] = __float_as_uint(w.z);
-    o[12] = __float_as_uint(pdf_s);
 }
 
 // ------------------------------------------------------------------ SPEC §15 helpers (denoiser path)
@@ -2907,19 +2705,6 @@ __global__ __launch_bounds__(kBlock) void k_tonemap(const float4 *accum, uchar4 
     const bool ok = a.w > 0.0f;
     out[i] = make_uchar4(encode_srgb8(ok ? a.x / a.w : 0.f, thr), encode_srgb8(ok ? a.y / a.w : 0.f, thr), encode_srgb8(ok ? a.z / a.w : 0.f, thr), 255);
 }
-
-// stand-alone ray queries (lpt_trace_closest / lpt_trace_occluded)
-template <bool MASK = false>
-__global__ __launch_bounds__(kTraceBlock) void k_query_occluded(DScene sc, const float4 *o, const float4 *d, uint8_t *out, uint32_t n) {
-    uint2 *stack = reinterpret_cast<uint2 *>(lds_dyn) + threadIdx.x;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 o4 = o[i], d4 = d[i];
-    Hit h;
-    uint32_t a = 0, b = 0;
-    out[i] = traverse<true, false, MASK>(sc, mk3(o4.x, o4.y, o4.z), mk3(d4.x, d4.y, d4.z), o4.w, stack, h, a, b) ? 1 : 0;
-}
-
 
 // ------------------------------------------------------------------ refit (lpt_scene_gpu_update_instances)
 // The tree keeps its topology; every node's child boxes, grid origin and exponents are recomputed from the
