@@ -2146,10 +2146,10 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
                 const Queue qin = w->q[b & 1u], qout = w->q[(b + 1u) & 1u];
                 stage_begin(r, ST_SHADE, s, slot);            // :471-480, :502-508
                 // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); PUNCT / ENV as for k_path; TRANS: SPEC §21; EMIS: SPEC §22; ESAMP: SPEC §23, only with EMIS; NMAP: SPEC §24
-                with_flags([&](auto G, auto P, auto Tr, auto Em, auto Es, auto Nm) {
-                    auto launch = [&](auto... e) { hipLaunchKernelGGL((k_shade<decltype(G)::value, sizeof...(e) != 0, decltype(P)::value, decltype(Tr)::value, decltype(Em)::value, decltype(Em)::value && decltype(Es)::value, decltype(Nm)::value, decltype(e)...>), dim3(pl.shade_blocks), dim3(kBlock), 0, s, sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, sort_queues, e...); };
-                    if (f.env) launch(ev); else launch();
-                }, f.denoise && b == 0u, f.punct, f.trans, f.emis, esamp, f.nmap);
+                const ShadeKernargs ska{sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, sort_queues, ev};   // ev: read by the ENV forms alone
+                with_flags([&](auto G, auto E, auto P, auto Tr, auto Em, auto Es, auto Nm) {
+                    hipLaunchKernelGGL((k_shade<decltype(G)::value, decltype(E)::value, decltype(P)::value, decltype(Tr)::value, decltype(Em)::value, decltype(Em)::value && decltype(Es)::value, decltype(Nm)::value>), dim3(pl.shade_blocks), dim3(kBlock), 0, s, ska);
+                }, f.denoise && b == 0u, f.env, f.punct, f.trans, f.emis, esamp, f.nmap);
                 stage_end(r, s, slot);
                 if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
                 trace(b + 1u < nb ? (int)(b + 1u) : -1, (int)b);

@@ -276,14 +276,15 @@ __device__ __forceinline__ uint32_t wave_compact(bool valid, uint32_t *counter) 
 // block-aggregated stream compaction: ONE global atomic per 256-thread block and counter.
 // A single device-scope word sustains only ~88 returning atomics/us on MI355X, so a
 // per-wave atomic (32K of them for a 1080p queue) would cost more than the shading itself.
-// Must be called by every thread of the block (two barriers).  `lds` needs 8 uint32.
-__device__ __forceinline__ uint32_t block_compact(bool valid, uint32_t *counter, uint32_t *lds) {
+// Must be called by every thread of the block (two barriers).  `lds` needs 8 uint32.  `tid`: the thread's index in the block (k_shade hands in a copy the optimiser
+// cannot see through, so that the comparisons below are made where they are used and not kept as lane masks in SGPRs across the caller's loop).
+__device__ __forceinline__ uint32_t block_compact(bool valid, uint32_t *counter, uint32_t *lds, const uint32_t tid = threadIdx.x) {
     const unsigned long long mask = __ballot(valid);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
     const uint32_t n = (uint32_t)__popcll(mask);
     if (lane == 0) lds[wave] = n;
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (tid == 0) {
         const uint32_t n0 = lds[0], n1 = lds[1], n2 = lds[2], n3 = lds[3];
         const uint32_t total = n0 + n1 + n2 + n3;
         const uint32_t base = total ? atomicAdd(counter, total) : 0u;
@@ -300,8 +301,8 @@ __device__ __forceinline__ uint32_t block_compact(bool valid, uint32_t *counter,
 // traversal wave pulls share one or two octants instead of eight.  Per wave and key one ballot + popcount, the
 // (key, wave) counts are prefix-summed in LDS (key-major), still ONE global atomic per block and counter.
 // Results are keyed by pixel slot, so the order of a queue never changes them.  `lds` needs 72 uint32.
-__device__ __forceinline__ uint32_t block_compact_binned(bool valid, uint32_t key, uint32_t *counter, uint32_t *lds) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+__device__ __forceinline__ uint32_t block_compact_binned(bool valid, uint32_t key, uint32_t *counter, uint32_t *lds, const uint32_t tid = threadIdx.x) {
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
     unsigned long long mine = 0ull;
     uint32_t cnt_k = 0;  // lane k < 8 keeps this wave's count of key k
 #pragma unroll
@@ -312,17 +313,17 @@ __device__ __forceinline__ uint32_t block_compact_binned(bool valid, uint32_t ke
     }
     if (lane < 8u) lds[lane * 4u + wave] = cnt_k;   // [key][wave]
     __syncthreads();
-    if (threadIdx.x < 32u) {
+    if (tid < 32u) {
         // exclusive prefix over the 32 (key, wave) cells in key-major order: one wave32-style shuffle scan
-        const uint32_t c = lds[threadIdx.x];
+        const uint32_t c = lds[tid];
         uint32_t incl = c;
 #pragma unroll
         for (int off = 1; off < 32; off <<= 1) {
             const uint32_t v = __shfl_up(incl, off);
             if ((int)lane >= off) incl += v;
         }
-        lds[32u + threadIdx.x] = incl - c;
-        if (threadIdx.x == 31u) lds[64u] = incl ? atomicAdd(counter, incl) : 0u;
+        lds[32u + tid] = incl - c;
+        if (tid == 31u) lds[64u] = incl ? atomicAdd(counter, incl) : 0u;
     }
     __syncthreads();
     const uint32_t idx = lds[64u] + lds[32u + key * 4u + wave] + (uint32_t)__popcll(mine & ((1ull << lane) - 1ull));
@@ -1800,10 +1801,15 @@ __device__ __forceinline__ float light_rl(const float r0, const float p_env, con
     return rl;
 }
 // NMAP (SPEC §24): the scene has a normal-mapped material in use; a surface hit on such a triangle shades with normal_map's Ns — and changes nothing else of the hit.
-template <bool GBUF, bool ENV, bool PUNCT, bool TRANS = false, bool EMIS = false, bool ESAMP = false, bool NMAP = false, typename LoadO, typename AddL>
-__device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe, const DEnv &ev, const DNoise &nz, const FrameParams &p, const float *s_lut,
-                                          const uint32_t bounce, const bool last_bounce, const uint32_t seed_base, const float inv_nl, const PunctPick &pk, const GBufArgs &gb,
-                                          const float4 d4, const float4 T4, const float4 h4, LoadO load_o, AddL add_l, ShadeOut &out) {
+// `sc` is read for what a hit needs first (the shading record and the per-triangle words that go out with it); `cold()` hands out what a later part or only a branch of
+// the hit reads — the probe, the noise texture, the G-buffer, and the scene once more for its texture tables, its lights and the side tables of PUNCT / TRANS / EMIS /
+// ESAMP / NMAP — and is asked where that part begins: k_shade re-reads them from its argument segment there (ShadeKernargs), so that they hold no scalar register
+// across its loop; k_path hands out its own parameters.
+struct ShadeCold { const DScene &sc; const DProbe &probe; const DNoise &nz; const GBufArgs &gb; };
+template <bool GBUF, bool ENV, bool PUNCT, bool TRANS = false, bool EMIS = false, bool ESAMP = false, bool NMAP = false, typename LoadO, typename AddL, typename Cold>
+__device__ __forceinline__ void shade_hit(const DScene &sc, const DEnv &ev, const FrameParams &p, const float *s_lut,
+                                          const uint32_t bounce, const bool last_bounce, const uint32_t seed_base, const float inv_nl, const PunctPick &pk,
+                                          const float4 d4, const float4 T4, const float4 h4, LoadO load_o, AddL add_l, Cold cold, ShadeOut &out) {
     out.want_next = false; out.want_shadow = false; out.is_surface = false;
     const uint32_t pxy = __float_as_uint(T4.w);  // x | y << 13 | sample << 26 (k_raygen)
     const f3 d = mk3(d4.x, d4.y, d4.z);
@@ -1817,11 +1823,12 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
         g_P = mk3(fmaf(d.x, h4.x, o4.x), fmaf(d.y, h4.x, o4.y), fmaf(d.z, h4.x, o4.z));
     }
     if (prim == 0xFFFFFFFFu) {
-        f3 e = env_lookup(probe, d);
+        const ShadeCold c = cold();
+        f3 e = env_lookup(c.probe, d);
         if (ENV) {
             const float pdf_prev = load_o().w;
             if (pdf_prev >= 0.0f) {   // not a camera ray: the BSDF strategy's MIS weight against the probe's
-                const float pe = ((PUNCT || ESAMP || sc.n_lights) ? 0.5f : 1.0f) * env_pdf(ev, d);
+                const float pe = ((PUNCT || ESAMP || c.sc.n_lights) ? 0.5f : 1.0f) * env_pdf(ev, d);
                 const float pb2 = pdf_prev * pdf_prev;
                 const float w = pb2 / (pb2 + pe * pe);
                 e = mk3(e.x * w, e.y * w, e.z * w);
@@ -1829,7 +1836,7 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
         }
         add_l(T.x * e.x, T.y * e.y, T.z * e.z);
     } else if (prim & LPT_LIGHT_BIT) {
-        const float4 *Lt = reinterpret_cast<const float4 *>(sc.lights + (prim & ~LPT_LIGHT_BIT));
+        const float4 *Lt = reinterpret_cast<const float4 *>(cold().sc.lights + (prim & ~LPT_LIGHT_BIT));
         const float4 n4 = Lt[0], t4 = Lt[1], b4 = Lt[2], lo4 = Lt[3];
         const float Le = lo4.w;
         g_n = mk3(n4.x, n4.y, n4.z);
@@ -1872,28 +1879,30 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
             float tu = (P0.w * bw + P1.w * hu) + P2.w * hv;
             float tvv = (N0.w * bw + N1.w * hu) + N2.w * hv;
             // SPEC §24: behind the divergent branch, and before the material's own taps, so that the edges and the uv deltas are dead by then
-            if (NMAP && nm != 0u) normal_map(sc, s_lut, nm, Nv, Ng, flip, p1 - p0, p2 - p0, P1.w - P0.w, N1.w - N0.w, P2.w - P0.w, N2.w - N0.w, tu, tvv, Ns);
+            if (NMAP && nm != 0u) normal_map(cold().sc, s_lut, nm, Nv, Ng, flip, p1 - p0, p2 - p0, P1.w - P0.w, N1.w - N0.w, P2.w - P0.w, N2.w - N0.w, tu, tvv, Ns);
             f3 base = mk3(mc.x, mc.y, mc.z);
             float rough = mp.x, metal = mp.y;
             const uint32_t atex = __float_as_uint(mp.z), mtex = __float_as_uint(mp.w);
+            const DScene &ts = cold().sc;   // the texture tables
             if ((atex >> 30) == 1u) {   // kPairedBit set, not LPT_INVALID_INDEX: both textures of the material from one set of taps
                 f3 alb;
                 float mg, mb;
-                texture_lookup_pair(sc, s_lut, atex & ~kPairedBit, mtex, tu, tvv, alb, mg, mb);
+                texture_lookup_pair(ts, s_lut, atex & ~kPairedBit, mtex, tu, tvv, alb, mg, mb);
                 base.x *= alb.x; base.y *= alb.y; base.z *= alb.z;
                 rough *= mg; metal *= mb;
             } else {
-                if (atex < sc.n_images) {
-                    const float4 tex = texture_lookup(sc, s_lut, atex, tu, tvv, true);
+                if (atex < ts.n_images) {
+                    const float4 tex = texture_lookup(ts, s_lut, atex, tu, tvv, true);
                     base.x *= tex.x; base.y *= tex.y; base.z *= tex.z;
                 }
-                if (mtex < sc.n_images) {
-                    const float4 tex = texture_lookup(sc, s_lut, mtex, tu, tvv, false);
+                if (mtex < ts.n_images) {
+                    const float4 tex = texture_lookup(ts, s_lut, mtex, tu, tvv, false);
                     rough *= tex.y; metal *= tex.z;
                 }
             }
             if (EMIS && em != 0u) {   // SPEC §22: weight 1 whatever the ray's pdf, both sides (the flipped Ng plays no part), the last bounce included
-                const float4 er = sc.emis_recs[em - 1u];
+                const DScene &cs = cold().sc;
+                const float4 er = cs.emis_recs[em - 1u];
                 f3 E = mk3(er.x, er.y, er.z);
                 const uint32_t etex = __float_as_uint(er.w);
                 if (etex < sc.n_images) {
@@ -1904,8 +1913,8 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
                     const float pdf_prev = load_o().w;
                     if (pdf_prev >= 0.0f) {
                         const float cl = fabsf(dot(Ng, d));
-                        const float pA = lum(mk3(er.x, er.y, er.z)) * sc.emit_inv_W;
-                        const float p_sel = (ENV ? 0.5f : 1.0f) * ((PUNCT || sc.n_lights) ? 0.5f : 1.0f);
+                        const float pA = lum(mk3(er.x, er.y, er.z)) * cs.emit_inv_W;
+                        const float p_sel = (ENV ? 0.5f : 1.0f) * ((PUNCT || cs.n_lights) ? 0.5f : 1.0f);
                         const float pl = (((h4.x * h4.x) / cl) * pA) * p_sel;
                         const float pb2 = pdf_prev * pdf_prev;
                         const float w = pb2 / (pb2 + pl * pl);
@@ -1926,21 +1935,23 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
             Rng rg = rng_init(pixel, stage_seed(p.user_seed, seed_counter), LPT_TAG_SHADE);
             float r0 = rng_next(rg), r1 = rng_next(rg), r2 = rng_next(rg);
             float r3 = rng_next(rg), r4 = rng_next(rg), r5 = rng_next(rg);
-            noise_shift(nz, x, y, seed_counter, r4, r5);
+            const ShadeCold c = cold();   // the noise texture here, the lights and the side tables in next-event estimation below
+            const DScene &cs = c.sc;
+            noise_shift(c.nz, x, y, seed_counter, r4, r5);
             float r6 = 0.0f, r7 = 0.0f, r8 = 0.0f, r9 = 0.0f;
             if (ENV) { r6 = rng_next(rg); r7 = rng_next(rg); r8 = rng_next(rg); r9 = rng_next(rg); }
             float ra = 0.0f, rb = 0.0f;   // ESAMP: the alias pick, behind every draw the other modes make
             if (ESAMP) { ra = rng_next(rg); rb = rng_next(rg); }
-            const float p_env = (PUNCT || ESAMP || sc.n_lights) ? 0.5f : 1.0f;   // ENV: the probe's share of the light samples
-            const float p_m = (PUNCT || sc.n_lights) ? 0.5f : 1.0f;   // ESAMP: the emitters' share of the non-probe light samples
+            const float p_env = (PUNCT || ESAMP || cs.n_lights) ? 0.5f : 1.0f;   // ENV: the probe's share of the light samples
+            const float p_m = (PUNCT || cs.n_lights) ? 0.5f : 1.0f;   // ESAMP: the emitters' share of the non-probe light samples
             float am = max2(max2(fabsf(P.x), fabsf(P.y)), fabsf(P.z));
             float eps = 1.0e-4f * (1.0f + am);
             const f3 Po = mk3(P.x + Ng.x * eps, P.y + Ng.y * eps, P.z + Ng.z * eps);
             bool glass = false;   // TRANS: this hit is an interface event (SPEC §21)
             if (TRANS) {
-                const uint32_t te = sc.trans_tri[prim];
+                const uint32_t te = cs.trans_tri[prim];
                 if (te != 0u) {
-                    const float4 tr = sc.trans_recs[te - 1u];   // transmission, ior, thin
+                    const float4 tr = cs.trans_recs[te - 1u];   // transmission, ior, thin
                     const float pt = tr.x * (1.0f - clampf(metal, 0.0f, 1.0f));
                     if (r3 < pt) {
                         glass = true;
@@ -1968,13 +1979,13 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
                 if (env_sample(ev, r6, r7, r8, r9, r1, r2, wi, ps)) {
                     Hit hl;
                     hl.t = LPT_T_INF; hl.u = 0.f; hl.v = 0.f; hl.prim = 0xFFFFFFFFu;
-                    intersect_lights(sc, Po, wi, hl);   // a BSDF ray this way would stop at the light's front: not the probe's direction
+                    intersect_lights(cs, Po, wi, hl);   // a BSDF ray this way would stop at the light's front: not the probe's direction
                     if (hl.prim == 0xFFFFFFFFu) {
                         f3 f;
                         float pb;
                         bsdf_eval(sf, Ns, Ng, V, NoV, pspec, wi, f, pb);
                         if (pb > 0.0f) {
-                            const f3 Le = env_lookup(probe, wi);
+                            const f3 Le = env_lookup(c.probe, wi);
                             const float pe = p_env * env_pdf(ev, wi);
                             const float pe2 = pe * pe;
                             const float wm = last_bounce ? 1.0f : pe2 / (pe2 + pb * pb);   // the last bounce: no BSDF ray carries the other half
@@ -1993,10 +2004,10 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
             } else if (ESAMP && light_rl<ENV, false>(r0, p_env, p_m) < p_m) {   // the emissive triangles (SPEC §23)
                 // the last bounce draws none: a sample there would stand for emission one bounce deeper than §22 adds
                 EmitterSample es;
-                if (!last_bounce && emitter_sample(sc, s_lut, ra, rb, r1, r2, Po, es)) {
+                if (!last_bounce && emitter_sample(cs, s_lut, ra, rb, r1, r2, Po, es)) {
                     Hit hl;
                     hl.t = es.dist; hl.u = 0.f; hl.v = 0.f; hl.prim = 0xFFFFFFFFu;
-                    intersect_lights(sc, Po, es.wi, hl);   // §19's rule: a rectangle light's front on the segment
+                    intersect_lights(cs, Po, es.wi, hl);   // §19's rule: a rectangle light's front on the segment
                     if (hl.prim == 0xFFFFFFFFu) {
                         f3 f;
                         float pb;
@@ -2018,14 +2029,14 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
                 }
             } else if (PUNCT && light_rl<ENV, ESAMP>(r0, p_env, p_m) < pk.p_p) {   // a punctual light (SPEC §19): a delta light, so MIS weight 1 and no draw beyond r0
                 const float rl = light_rl<ENV, ESAMP>(r0, p_env, p_m);
-                uint32_t li = (uint32_t)((rl / pk.p_p) * (float)sc.n_punctual);
-                if (li > sc.n_punctual - 1u) li = sc.n_punctual - 1u;
+                uint32_t li = (uint32_t)((rl / pk.p_p) * (float)cs.n_punctual);
+                if (li > cs.n_punctual - 1u) li = cs.n_punctual - 1u;
                 f3 wi, E;
                 float dist;
-                if (punctual_sample(sc, li, Po, wi, dist, E)) {
+                if (punctual_sample(cs, li, Po, wi, dist, E)) {
                     Hit hl;
                     hl.t = dist; hl.u = 0.f; hl.v = 0.f; hl.prim = 0xFFFFFFFFu;
-                    intersect_lights(sc, Po, wi, hl);   // a rectangle light's front on the segment: shadow rays test triangles only, and it would stop a BSDF ray too
+                    intersect_lights(cs, Po, wi, hl);   // a rectangle light's front on the segment: shadow rays test triangles only, and it would stop a BSDF ray too
                     if (hl.prim == 0xFFFFFFFFu) {
                         f3 f;
                         float pb;
@@ -2042,12 +2053,12 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
                         }
                     }
                 }
-            } else if (sc.n_lights) {
+            } else if (cs.n_lights) {
                 float rl = light_rl<ENV, ESAMP>(r0, p_env, p_m);
                 if (PUNCT) rl = (rl - pk.p_p) / (1.0f - pk.p_p);
-                uint32_t li = (uint32_t)(rl * (float)sc.n_lights);
-                if (li > sc.n_lights - 1u) li = sc.n_lights - 1u;
-                const float4 *Lt = reinterpret_cast<const float4 *>(sc.lights + li);
+                uint32_t li = (uint32_t)(rl * (float)cs.n_lights);
+                if (li > cs.n_lights - 1u) li = cs.n_lights - 1u;
+                const float4 *Lt = reinterpret_cast<const float4 *>(cs.lights + li);
                 const float4 n4 = Lt[0], t4 = Lt[1], b4 = Lt[2], lo4 = Lt[3];
                 const float Le = lo4.w, hw = t4.w, hh = b4.w;
                 float a = (2.0f * r1 - 1.0f) * hw, bq = (2.0f * r2 - 1.0f) * hh;
@@ -2097,6 +2108,7 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
         }
     }
     if (GBUF && bounce == 0) {
+        const GBufArgs &gb = cold().gb;
         const uint32_t gx = pxy & 0x1FFFu, gy = (pxy >> 13) & 0x1FFFu;
         const size_t px = (size_t)gy * p.width + gx;
         gb.gbuf[px] = make_uint4(prim, __float_as_uint(h4.x), oct_encode(g_n), pack_albedo(g_alb));
@@ -2106,8 +2118,25 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
     }
 }
 
-// ENV (SPEC §18): `env...` is the probe's distribution, one DEnv; the default instantiations take no such argument.  The ENV ones
+// k_shade's arguments: ONE struct, so that the kernel-argument segment IS this struct (as TraceKernargs for k_trace).  The per-hit loop is deeply divergent — every
+// nesting level holds an exec mask in two SGPRs — and whatever the kernel takes from the parameter stays in SGPRs across the whole loop: with everything taken from there
+// the bench form ran out of them and moved 61 scalars through VGPR lanes, 202 v_readlane / v_writelane in the loop body.  So only what a hit reads first is
+// taken from the parameter: qin.d / qin.T / hits, the shading records of `sc`, the counts and seeds.  The rest — qin.o (emitter hits), qout / sq / ctr (the reservation and
+// the stores), Lsum (misses, emitters), probe, nz, gb, the texture tables, the lights and the side tables (ShadeCold) — is re-read from the segment where it is used,
+// through a pointer the optimiser cannot see through and so cannot hoist the loads from.  (The texture tables too: kept with the parameter they were re-loaded inside
+// the loop anyway, and the allocator's attempt to keep them left a dead spill slot — a private segment for nothing.)
+// ENV (SPEC §18): `ev` is the probe's distribution, read by the ENV instantiations only.  The ENV ones
 // need more than 128 VGPRs and run at 3 waves per SIMD (168), where they do not spill
+struct ShadeKernargs {
+    DScene sc; DProbe probe; DNoise nz; FrameParams p; Queue qin; const float4 *hits; Queue qout; ShadowQueue sq; float4 *Lsum; FrameCounters *ctr;
+    int bounce; uint32_t seed_base; GBufArgs gb; int sorted; DEnv ev;
+};
+typedef const __attribute__((address_space(4))) ShadeKernargs *ShadeKernargsPtr;
+__device__ __forceinline__ ShadeKernargsPtr shade_kernargs() {
+    ShadeKernargsPtr ka = (ShadeKernargsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    return ka;
+}
 // PUNCT (SPEC §19): the instantiations that run while the scene has punctual lights; LPT_SHADE_WAVES from the compiler's register report
 #ifndef LPT_SHADE_WAVES
 #define LPT_SHADE_WAVES(ENV, PUNCT) (((ENV) || (PUNCT)) ? 3 : 4)
@@ -2128,13 +2157,15 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DProbe &probe,
 #ifndef LPT_SHADE_WAVES_NMAP
 #define LPT_SHADE_WAVES_NMAP(ENV, PUNCT, TRANS, EMIS, ESAMP) 3
 #endif
-template <bool GBUF, bool ENV = false, bool PUNCT = false, bool TRANS = false, bool EMIS = false, bool ESAMP = false, bool NMAP = false, typename... Env>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NMAP ? LPT_SHADE_WAVES_NMAP(ENV, PUNCT, TRANS, EMIS, ESAMP) : ESAMP ? LPT_SHADE_WAVES_ESAMP(ENV, PUNCT, TRANS) : EMIS ? LPT_SHADE_WAVES_EMIS(ENV, PUNCT, TRANS) : TRANS ? LPT_SHADE_WAVES_TRANS(ENV, PUNCT) : LPT_SHADE_WAVES(ENV, PUNCT)))) void k_shade(DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue qin, const float4 *hits,
-                                                  Queue qout, ShadowQueue sq, float4 *Lsum, FrameCounters *ctr, int bounce,
-                                                  uint32_t seed_base, GBufArgs gb, int sorted, Env... env) {
-    static_assert(sizeof...(Env) == (ENV ? 1u : 0u), "the ENV instantiations take the distribution, the others nothing");
+template <bool GBUF, bool ENV = false, bool PUNCT = false, bool TRANS = false, bool EMIS = false, bool ESAMP = false, bool NMAP = false>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NMAP ? LPT_SHADE_WAVES_NMAP(ENV, PUNCT, TRANS, EMIS, ESAMP) : ESAMP ? LPT_SHADE_WAVES_ESAMP(ENV, PUNCT, TRANS) : EMIS ? LPT_SHADE_WAVES_EMIS(ENV, PUNCT, TRANS) : TRANS ? LPT_SHADE_WAVES_TRANS(ENV, PUNCT) : LPT_SHADE_WAVES(ENV, PUNCT)))) void k_shade(const ShadeKernargs a) {
     static_assert(EMIS || !ESAMP, "emitter sampling (SPEC §23) exists only for a scene with an emissive material in use");
-    const DEnv ev = env_arg(env...);
+    // the hot arguments, from the parameter; the cold ones are re-read where they are used (ShadeKernargs)
+    const DScene &sc = a.sc;
+    const FrameParams &p = a.p;
+    const float4 *const qin_d = a.qin.d, *const qin_T = a.qin.T, *const hits = a.hits;
+    const int bounce = a.bounce, sorted = a.sorted;
+    const uint32_t seed_base = a.seed_base;
     __shared__ uint32_t lds[72];
     __shared__ float s_lut[256];
     // ONE RESERVATION FOR TWO ITERATIONS (round 6, log N).  A block reserves its slots in both outgoing queues with one returning atomic — on ONE word for the whole grid:
@@ -2147,7 +2178,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NMAP ? L
     s_lut[threadIdx.x] = sc.srgb_lut[threadIdx.x];  // kBlock == 256
     __syncthreads();
     bool parked = false;                   // block-uniform: the previous iteration's rows are waiting in s_park (its per-wave counts in lds[16..19])
-    const uint32_t count = QC(ctr, bounce);
+    const uint32_t count = QC(a.ctr, bounce);
     const uint32_t stride = gridDim.x * blockDim.x;
     const uint32_t rounded = (count + 255u) & ~255u;  // keep whole blocks in the loop for the barriers
     uint32_t n_surface = 0;
@@ -2159,15 +2190,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NMAP ? L
         so.want_next = false; so.want_shadow = false; so.is_surface = false;
         const uint32_t i = i0;
         if (i < count) {
-            const float4 d4 = ld_nt(qin.d + i), T4 = ld_nt(qin.T + i), h4 = ld_nt(hits + i);
+            const float4 d4 = ld_nt(qin_d + i), T4 = ld_nt(qin_T + i), h4 = ld_nt(hits + i);
             const uint32_t slot = __float_as_uint(d4.w);
-            shade_hit<GBUF, ENV, PUNCT, TRANS, EMIS, ESAMP, NMAP>(sc, probe, ev, nz, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, gb, d4, T4, h4,
-                            [&]() { return ld_nt(qin.o + i); },
+            shade_hit<GBUF, ENV, PUNCT, TRANS, EMIS, ESAMP, NMAP>(sc, a.ev, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, d4, T4, h4,
+                            [&]() { return ld_nt(shade_kernargs()->qin.o + i); },
                             [&](float r, float g, float b) {
+                                float4 *const Lsum = shade_kernargs()->Lsum;
                                 float4 L = Lsum[slot];
                                 L.x = L.x + r; L.y = L.y + g; L.z = L.z + b;
                                 Lsum[slot] = L;
-                            }, so);
+                            },
+                            []() { const ShadeKernargs *k = (const ShadeKernargs *)shade_kernargs(); return ShadeCold{k->sc, k->probe, k->nz, k->gb}; }, so);
         }
         // `sorted` (wave-uniform; bit 0: next-bounce queue, bit 1: shadow queue): the queue leaves the block ordered by direction octant
         if (!(sorted & 3)) {   // the default: both queues' slots with one atomic (the last bounce emits no next ray: its word gets + 0) per TWO iterations
@@ -2184,6 +2217,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NMAP ? L
                 if (vb) { s_park[3 * kBlock + threadIdx.x] = so.no4; s_park[4 * kBlock + threadIdx.x] = so.nd4; s_park[5 * kBlock + threadIdx.x] = so.nT4; }
                 parked = true;
             } else {
+                // where the rows go, re-read in one batch (ShadeKernargs)
+                ShadeKernargsPtr ka = shade_kernargs();
+                FrameCounters *const ctr = ka->ctr;
+                const int bounce = ka->bounce;   // (the loop's own copy: not kept, as an offset into ctr, for this arm)
+                Queue qout; qout.o = ka->qout.o; qout.d = ka->qout.d; qout.T = ka->qout.T;
+                ShadowQueue sq; sq.o = ka->sq.o; sq.d = ka->sq.d; sq.c = ka->sq.c;
                 if (lane == 0) lds[wave] = (uint32_t)__popcll(ma) | ((uint32_t)__popcll(mb) << 16);
                 __syncthreads();
                 if (threadIdx.x == 0) {
@@ -2216,12 +2255,19 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NMAP ? L
                 parked = false;
             }
         } else {
-            const uint32_t si = (sorted & 2) ? block_compact_binned(so.want_shadow, so.want_shadow ? dir_octant(so.sd4.x, so.sd4.y, so.sd4.z) : 0u, &SC(ctr, bounce), lds)
-                                       : block_compact(so.want_shadow, &SC(ctr, bounce), lds);
+            ShadeKernargsPtr ka = shade_kernargs();
+            FrameCounters *const ctr = ka->ctr;
+            Queue qout; qout.o = ka->qout.o; qout.d = ka->qout.d; qout.T = ka->qout.T;
+            ShadowQueue sq; sq.o = ka->sq.o; sq.d = ka->sq.d; sq.c = ka->sq.c;
+            const int bounce = ka->bounce, sorted = ka->sorted;   // (the loop's own copies: not kept for this arm)
+            uint32_t tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));   // (block_compact: no lane masks hoisted out of the loop)
+            const uint32_t si = (sorted & 2) ? block_compact_binned(so.want_shadow, so.want_shadow ? dir_octant(so.sd4.x, so.sd4.y, so.sd4.z) : 0u, &SC(ctr, bounce), lds, tid)
+                                       : block_compact(so.want_shadow, &SC(ctr, bounce), lds, tid);
             if (so.want_shadow) { st_nt(sq.o + si, so.so4); st_nt(sq.d + si, so.sd4); st_nt(sq.c + si, so.sc4); }
             if (!last_bounce) {
-                const uint32_t ni = (sorted & 1) ? block_compact_binned(so.want_next, so.want_next ? dir_octant(so.nd4.x, so.nd4.y, so.nd4.z) : 0u, &QC(ctr, bounce + 1), lds)
-                                           : block_compact(so.want_next, &QC(ctr, bounce + 1), lds);
+                const uint32_t ni = (sorted & 1) ? block_compact_binned(so.want_next, so.want_next ? dir_octant(so.nd4.x, so.nd4.y, so.nd4.z) : 0u, &QC(ctr, bounce + 1), lds, tid)
+                                           : block_compact(so.want_next, &QC(ctr, bounce + 1), lds, tid);
                 if (so.want_next) { st_nt(qout.o + ni, so.no4); st_nt(qout.d + ni, so.nd4); st_nt(qout.T + ni, so.nT4); }
             }
         }
@@ -2233,7 +2279,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NMAP ? L
     __syncthreads();
     if (threadIdx.x == 0) {
         const uint32_t total = (lds[0] + lds[1]) + (lds[2] + lds[3]);
-        if (total) atomicAdd(&ctr->shaded_part[((uint32_t)bounce * 8u + (blockIdx.x & 7u)) * 32u], total);
+        if (total) atomicAdd(&shade_kernargs()->ctr->shaded_part[((uint32_t)bounce * 8u + (blockIdx.x & 7u)) * 32u], total);
     }
 }
 
@@ -2333,9 +2379,10 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(LPT
                 const float4 d4 = make_float4(rs.d.x, rs.d.y, rs.d.z, __uint_as_float(vslot));
                 const float4 T4 = make_float4(T.x, T.y, T.z, __uint_as_float(pxy));
                 const float4 h4 = make_float4(rs.best.t, rs.best.u, rs.best.v, __uint_as_float(rs.best.prim));
-                shade_hit<GBUF, ENV, PUNCT>(sc, probe, ev, nz, p, s_lut, bounce, bounce + 1u >= nb, seed0 + bounce + 1u, inv_nl, pk, gb, d4, T4, h4,
+                shade_hit<GBUF, ENV, PUNCT>(sc, ev, p, s_lut, bounce, bounce + 1u >= nb, seed0 + bounce + 1u, inv_nl, pk, d4, T4, h4,
                                 [&]() { return make_float4(rs.o.x, rs.o.y, rs.o.z, pdf); },
-                                [&](float r, float g, float b) { L.x = L.x + r; L.y = L.y + g; L.z = L.z + b; }, so);
+                                [&](float r, float g, float b) { L.x = L.x + r; L.y = L.y + g; L.z = L.z + b; },
+                                [&]() { return ShadeCold{sc, probe, nz, gb}; }, so);
                 if (so.is_surface) atomicAdd(&s_cnt[128u + bounce], 1u);
                 if (so.want_shadow) atomicAdd(&s_cnt[64u + bounce], 1u);
                 if (so.want_next) {
