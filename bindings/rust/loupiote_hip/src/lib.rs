@@ -125,6 +125,10 @@ impl Scene {
     pub fn set_material_alpha(&mut self, material: u32, mode: u32, cutoff: f32, alpha_image: u32) -> Result<(), Error> {
         check(unsafe { ffi::lpt_scene_set_material_alpha(self.h, material, mode, cutoff, alpha_image) })
     }
+    /// SPEC.md §26: alpha-blended (stochastic coverage); `material_alpha` then reports `ffi::LPT_ALPHA_BLEND`, `set_material_alpha` with mode 0 or 1 changes it back
+    pub fn set_material_alpha_blend(&mut self, material: u32, alpha_image: u32) -> Result<(), Error> {
+        check(unsafe { ffi::lpt_scene_set_material_alpha_blend(self.h, material, alpha_image) })
+    }
     /// -> (mode, cutoff, alpha_image)
     pub fn material_alpha(&self, material: u32) -> Result<(u32, f32, u32), Error> {
         let (mut mode, mut cutoff, mut image) = (0u32, 0f32, 0u32);
@@ -201,6 +205,10 @@ pub mod loaders {
     /// reference `crates/lib/src/loaders/gltf.rs:46`: appends to `scene`
     pub fn load_gltf(data: &[u8], scene: &mut Scene) -> Result<(), Error> {
         check(unsafe { ffi::lpt_load_gltf(scene.h, data.as_ptr(), data.len()) })
+    }
+    /// `flags`: `ffi::LPT_GLTF_READ_BLEND` marks `alphaMode: "BLEND"` materials blended (SPEC.md §26) instead of loading them as opaque; 0 is `load_gltf`
+    pub fn load_gltf_ex(data: &[u8], scene: &mut Scene, flags: u32) -> Result<(), Error> {
+        check(unsafe { ffi::lpt_load_gltf_ex(scene.h, data.as_ptr(), data.len(), flags) })
     }
 }
 

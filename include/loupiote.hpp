@@ -87,6 +87,8 @@ class Scene {  // scene.rs:30-54
     void set_material_alpha(uint32_t material, uint32_t mode, float cutoff = 0.5f, uint32_t alpha_image = LPT_INVALID_INDEX) {
         check(lpt_scene_set_material_alpha(h_, material, mode, cutoff, alpha_image));
     }
+    // SPEC.md §26: alpha-blended (stochastic coverage); material_alpha then reports LPT_ALPHA_BLEND, set_material_alpha with mode 0 or 1 changes it back
+    void set_material_alpha_blend(uint32_t material, uint32_t alpha_image = LPT_INVALID_INDEX) { check(lpt_scene_set_material_alpha_blend(h_, material, alpha_image)); }
     MaterialAlpha material_alpha(uint32_t material) const {
         MaterialAlpha a{};
         check(lpt_scene_get_material_alpha(h_, material, &a.mode, &a.cutoff, &a.alpha_image));
@@ -165,6 +167,9 @@ inline lpt_punctual_light directional_light(const Vec3 &direction, const Vec3 &c
 namespace loaders {  // loaders/gltf.rs:46-161
 inline void load_gltf(const uint8_t *data, size_t size, Scene &scene) { check(lpt_load_gltf(scene.handle(), data, size)); }
 inline void load_gltf_path(const std::string &path, Scene &scene) { check(lpt_load_gltf_path(scene.handle(), path.c_str())); }
+// flags: LPT_GLTF_READ_BLEND marks alphaMode "BLEND" materials blended (SPEC.md §26) instead of loading them as opaque; 0 is the loaders above
+inline void load_gltf(const uint8_t *data, size_t size, Scene &scene, uint32_t flags) { check(lpt_load_gltf_ex(scene.handle(), data, size, flags)); }
+inline void load_gltf_path(const std::string &path, Scene &scene, uint32_t flags) { check(lpt_load_gltf_path_ex(scene.handle(), path.c_str(), flags)); }
 /// the decoding half of ApplicationContext::load_env (app.rs:138-155): Radiance .hdr bytes -> RGBE8 pixels for ProbeGPU
 inline std::vector<uint8_t> load_env(const uint8_t *data, size_t size, uint32_t &width, uint32_t &height) {
     check(lpt_decode_hdr(data, size, nullptr, 0, &width, &height));

@@ -275,6 +275,14 @@ int lpt_punctual_light_make(uint32_t type, const float *position, const float *d
 #define LPT_ALPHA_MASK 1u
 int lpt_scene_set_material_alpha(lpt_scene *scene, uint32_t material_index, uint32_t mode, float cutoff, uint32_t alpha_image);
 int lpt_scene_get_material_alpha(const lpt_scene *scene, uint32_t material_index, uint32_t *mode, float *cutoff, uint32_t *alpha_image);
+/* build-only extension (SPEC.md §26): alpha-blended materials as stochastic coverage.  A third state of the same side table, reported by
+ * lpt_scene_get_material_alpha as mode LPT_ALPHA_BLEND: a triangle hit counts iff the same alpha `a` > xi, where xi in [0, 1) is a hash of
+ * the hit's own (prim, u, v) — so a surface of alpha `a` is seen, and shadows, with probability `a` over the samples of a pixel.  BLEND has
+ * no cutoff, hence a setter of its own: the stored cutoff returns to 0.5 and is not read.  LPT_ERR_INVALID_ARG, and nothing changed, for
+ * a material or image index out of range.  lpt_scene_set_material_alpha with mode 0 or 1 changes a blended material back; its mode 2
+ * stays LPT_ERR_INVALID_ARG. */
+#define LPT_ALPHA_BLEND 2u
+int lpt_scene_set_material_alpha_blend(lpt_scene *scene, uint32_t material_index, uint32_t alpha_image);
 
 /* build-only extension (SPEC.md §21; the reference's loader reads no KHR_materials_transmission): transmissive materials.  A second
  * side table beside the 32-byte lpt_material, opaque (factor 0) by default.  With factor tr in (0, 1] a hit on the material is, with
@@ -323,6 +331,13 @@ int lpt_scene_get_image(const lpt_scene *s, uint32_t index, uint32_t *width, uin
 int lpt_load_gltf(lpt_scene *scene, const uint8_t *data, size_t size);
 /* replaces: loaders::load_gltf_path (gltf.rs:158-161) */
 int lpt_load_gltf_path(lpt_scene *scene, const char *path);
+/* build-only extension (SPEC.md §14 (7), §26): the two loaders with `flags`.  flags = 0 is lpt_load_gltf / lpt_load_gltf_path byte for
+ * byte.  LPT_GLTF_READ_BLEND: a material with alphaMode "BLEND" is marked blended (lpt_scene_set_material_alpha_blend) instead of
+ * loading as opaque; its alpha image is chosen as a MASK material's is, and its alphaCutoff is validated and ignored.
+ * LPT_ERR_INVALID_ARG, and an untouched scene, for an unknown flag bit; every other rejection as lpt_load_gltf. */
+#define LPT_GLTF_READ_BLEND 1u
+int lpt_load_gltf_ex(lpt_scene *scene, const uint8_t *data, size_t size, uint32_t flags);
+int lpt_load_gltf_path_ex(lpt_scene *scene, const char *path, uint32_t flags);
 
 /* replaces: the `image::ImageBuffer::save` half of ApplicationContext::save_screenshot
  * (crates/standalone/src/app.rs:172-187): writes RGBA8 rows (e.g. from lpt_renderer_read_pixels) as a PNG. */
@@ -414,7 +429,7 @@ int lpt_scene_gpu_shading_normal(lpt_device *dev, const lpt_scene_gpu *sg, uint3
 /* build-only extension (SPEC.md §9), for tests and tools in the manner of lpt_scene_gpu_shading_normal: what a hit of baked triangle
  * prim[i] at barycentrics bary[i] = (u, v) reads from its textures, through the shading kernels' own lookups and dispatch.
  * out[n][16] = {albedo rgb (sRGB-decoded), mra g, mra b (1 where the material has no such texture), the emissive image's texel rgb
- * (1 without one), the normal map's texel xyz as stored in [0, 1] (0 without one), 1 where §20's alpha mask cuts the hit away else 0
+ * (1 without one), the normal map's texel xyz as stored in [0, 1] (0 without one), 1 where §20's alpha mask (§26's coverage test for a blended material) cuts the hit away else 0
  * (0 in a scene without masks), the interpolated texture coordinate (tu, tv), 0, 0}.  LPT_ERR_INVALID_ARG for a prim at or beyond the
  * scene's baked triangle count.  Blocking; host arrays. */
 int lpt_scene_gpu_sample_textures(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, float *out);

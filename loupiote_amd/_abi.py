@@ -39,6 +39,8 @@ LIGHT_DT = np.dtype([("normal", "<f4", 4), ("tangent", "<f4", 4), ("bitangent", 
 PUNCTUAL_DT = np.dtype([("position", "<f4", 4), ("direction", "<f4", 4), ("color", "<f4", 4), ("cone", "<f4", 4)])   # lpt_punctual_light (SPEC §19)
 PUNCTUAL_POINT, PUNCTUAL_SPOT, PUNCTUAL_DIRECTIONAL = 0, 1, 2
 ALPHA_OPAQUE, ALPHA_MASK = 0, 1   # lpt_scene_set_material_alpha's mode (SPEC §20)
+ALPHA_BLEND = 2                   # reported by lpt_scene_get_material_alpha, set by lpt_scene_set_material_alpha_blend (SPEC §26)
+GLTF_READ_BLEND = 1               # lpt_load_gltf_ex's flag: alphaMode BLEND marks the material blended (SPEC §14 (7))
 INSTANCE_DT = np.dtype([("model_to_world", "<f4", 16), ("blas_index", "<u4"), ("material_index", "<u4"),
                         ("pad", "<u4", 2)])
 ENTRY_DT = np.dtype([("vertex_offset", "<u4"), ("vertex_count", "<u4"), ("index_offset", "<u4"),
@@ -99,6 +101,7 @@ SIGNATURES = {
     "lpt_punctual_light_make": (_i, [_u32, _vp, _vp, _vp, _f, _f, _f, _f, _vp]),
     "lpt_scene_set_material_alpha": (_i, [_vp, _u32, _u32, _f, _u32]),
     "lpt_scene_get_material_alpha": (_i, [_vp, _u32, _pu32, C.POINTER(_f), _pu32]),
+    "lpt_scene_set_material_alpha_blend": (_i, [_vp, _u32, _u32]),
     "lpt_scene_set_material_transmission": (_i, [_vp, _u32, _f, _f, _u32]),
     "lpt_scene_get_material_transmission": (_i, [_vp, _u32, C.POINTER(_f), C.POINTER(_f), _pu32]),
     "lpt_scene_set_material_emission": (_i, [_vp, _u32, _vp, _f, _u32]),
@@ -114,6 +117,8 @@ SIGNATURES = {
     "lpt_scene_get_image": (_i, [_vp, _u32, _pu32, _pu32, _vp]),
     "lpt_load_gltf": (_i, [_vp, _vp, _sz]),
     "lpt_load_gltf_path": (_i, [_vp, C.c_char_p]),
+    "lpt_load_gltf_ex": (_i, [_vp, _vp, _sz, _u32]),
+    "lpt_load_gltf_path_ex": (_i, [_vp, C.c_char_p, _u32]),
     "lpt_decode_hdr": (_i, [_vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "lpt_decode_image": (_i, [_vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "lpt_write_hdr": (_i, [C.c_char_p, _vp, _u32, _u32, _sz]),

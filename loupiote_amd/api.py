@@ -225,10 +225,15 @@ class Scene:
     def punctual_lights(self):
         return self._get(A.lib().lpt_scene_get_punctual_lights, A.PUNCTUAL_DT, self.punctual_count())
 
-    # SPEC §20: alpha-masked (cutout) materials; a side table of the materials, opaque by default
+    # SPEC §20, §26: alpha-masked (cutout) and alpha-blended materials; a side table of the materials, opaque by default
     def set_material_alpha(self, material_index, mode, cutoff=0.5, alpha_image=A.INVALID_INDEX):
         """mode: A.ALPHA_OPAQUE / A.ALPHA_MASK (or "OPAQUE" / "MASK"); a hit on a masked material counts iff color.w (x the bilinear
-        alpha of image `alpha_image`, if any) >= cutoff, for closest-hit and shadow rays alike"""
+        alpha of image `alpha_image`, if any) >= cutoff, for closest-hit and shadow rays alike.  "BLEND" (the string; it has a setter of its
+        own in the C ABI, and no cutoff): the hit counts iff that alpha > a hash of the hit's own (prim, u, v) in [0, 1) — coverage alpha
+        over a pixel's samples; material_alpha then reports A.ALPHA_BLEND"""
+        if mode == "BLEND":
+            _check(A.lib().lpt_scene_set_material_alpha_blend(self._h, int(material_index), int(alpha_image)))
+            return
         if isinstance(mode, str):
             mode = {"OPAQUE": A.ALPHA_OPAQUE, "MASK": A.ALPHA_MASK}[mode]
         _check(A.lib().lpt_scene_set_material_alpha(self._h, int(material_index), int(mode), float(cutoff), int(alpha_image)))
@@ -884,13 +889,20 @@ class loaders:
     """crates/lib/src/loaders/mod.rs"""
 
     @staticmethod
-    def load_gltf(data, scene):
+    def load_gltf(data, scene, blend=False):
+        """blend: alphaMode "BLEND" marks the material blended (SPEC §26) instead of loading as opaque (SPEC §14 (7))"""
         buf = np.frombuffer(bytes(data), np.uint8)
-        _check(A.lib().lpt_load_gltf(scene._h, A.ptr(buf), buf.size))
+        if blend:
+            _check(A.lib().lpt_load_gltf_ex(scene._h, A.ptr(buf), buf.size, A.GLTF_READ_BLEND))
+        else:
+            _check(A.lib().lpt_load_gltf(scene._h, A.ptr(buf), buf.size))
 
     @staticmethod
-    def load_gltf_path(path, scene):
-        _check(A.lib().lpt_load_gltf_path(scene._h, str(path).encode()))
+    def load_gltf_path(path, scene, blend=False):
+        if blend:
+            _check(A.lib().lpt_load_gltf_path_ex(scene._h, str(path).encode(), A.GLTF_READ_BLEND))
+        else:
+            _check(A.lib().lpt_load_gltf_path(scene._h, str(path).encode()))
 
 
 def env_distribution(rgbe):

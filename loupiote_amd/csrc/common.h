@@ -23,9 +23,9 @@ struct Image {
     bool has_alpha = false;   // the file carried an alpha channel that rgba8's fourth byte holds (decode_png; SPEC §20: only then a MASK material reads it)
 };
 
-// SPEC §20: a material's alpha state (the 32-byte lpt_material keeps the reference's layout, so this rides beside it)
+// SPEC §20, §26: a material's alpha state (the 32-byte lpt_material keeps the reference's layout, so this rides beside it)
 struct MaterialAlpha {
-    uint32_t mode = LPT_ALPHA_OPAQUE;
+    uint32_t mode = LPT_ALPHA_OPAQUE;   // LPT_ALPHA_OPAQUE / _MASK / _BLEND (blended: the cutoff is not read)
     float cutoff = 0.5f;
     uint32_t image = LPT_INVALID_INDEX;
 };

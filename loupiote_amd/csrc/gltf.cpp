@@ -208,7 +208,7 @@ void decode_image(const Doc &d, const Json &img, Image &out) {
     if (!decode_png(p, n, out) && !decode_jpeg(p, n, out)) bad("image is neither a decodable PNG nor a baseline JPEG");
 }
 
-void load(lpt_scene *scene, const uint8_t *data, size_t size) {
+void load(lpt_scene *scene, const uint8_t *data, size_t size, uint32_t flags) {
     Doc d;
     split(data, size, d);
     // work on a copy so a failure leaves the scene untouched
@@ -281,7 +281,7 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
         return texture_offset + (uint32_t)si;
     };
     const Json &mats = d.js.at("materials");
-    struct Mask { uint32_t material; float cutoff; uint32_t image; };
+    struct Mask { uint32_t material; float cutoff; uint32_t image; bool blend; };
     std::vector<Mask> masks;
     struct Glass { uint32_t material; float factor, ior; uint32_t thin; };
     std::vector<Glass> glasses;
@@ -299,8 +299,8 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
         m.albedo_texture = tex_id(pbr.at("baseColorTexture"));
         m.mra_texture = tex_id(pbr.at("metallicRoughnessTexture"));
         tmp.materials.push_back(m);
-        // alphaMode / alphaCutoff (SPEC §20, §14(7)): MASK sets the side table once the images are decoded (below); BLEND loads as opaque.
-        // A file that states neither touches nothing
+        // alphaMode / alphaCutoff (SPEC §20, §26, §14(7)): MASK sets the side table once the images are decoded (below); BLEND loads as opaque unless the caller
+        // asked for LPT_GLTF_READ_BLEND, and then likewise (its cutoff is checked and ignored).  A file that states neither touches nothing
         const Json *jmode = mats[i].find("alphaMode"), *jcut = mats[i].find("alphaCutoff");
         float cutoff = 0.5f;
         if (jcut) {
@@ -309,7 +309,8 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
         }
         if (jmode) {
             if (!jmode->is_str() || !(jmode->str == "OPAQUE" || jmode->str == "MASK" || jmode->str == "BLEND")) bad("unknown alphaMode");
-            if (jmode->str == "MASK") masks.push_back(Mask{(uint32_t)tmp.materials.size() - 1u, cutoff, m.albedo_texture});
+            if (jmode->str == "MASK") masks.push_back(Mask{(uint32_t)tmp.materials.size() - 1u, cutoff, m.albedo_texture, false});
+            if (jmode->str == "BLEND" && (flags & LPT_GLTF_READ_BLEND)) masks.push_back(Mask{(uint32_t)tmp.materials.size() - 1u, cutoff, m.albedo_texture, true});
         }
         // KHR_materials_transmission / _ior / _volume (SPEC §21, §14(8)): a positive transmissionFactor sets the side table; thicknessFactor > 0 makes the
         // material the boundary of a solid, glTF's own rule.  The numbers are checked whatever the factor; a file without the extensions touches nothing
@@ -418,11 +419,12 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
         decode_image(d, images[i], im);
         tmp.images.push_back(std::move(im));
     }
-    // the alpha image of a MASK material is its base-colour image only if that file carried an alpha channel: §14(5) expands RGB with alpha 0,
+    // the alpha image of a MASK or BLEND material is its base-colour image only if that file carried an alpha channel: §14(5) expands RGB with alpha 0,
     // which must not cut everything away
     for (const Mask &k : masks) {
         const uint32_t image = (k.image < tmp.images.size() && tmp.images[k.image].has_alpha) ? k.image : LPT_INVALID_INDEX;
-        if (lpt_scene_set_material_alpha(&tmp, k.material, LPT_ALPHA_MASK, k.cutoff, image) != LPT_OK) bad(std::string("alphaMode MASK rejected: ") + lpt_last_error());
+        if ((k.blend ? lpt_scene_set_material_alpha_blend(&tmp, k.material, image) : lpt_scene_set_material_alpha(&tmp, k.material, LPT_ALPHA_MASK, k.cutoff, image)) != LPT_OK)
+            bad(std::string("alphaMode ") + (k.blend ? "BLEND" : "MASK") + " rejected: " + lpt_last_error());
     }
     for (const Glass &g : glasses)
         if (lpt_scene_set_material_transmission(&tmp, g.material, g.factor, g.ior, g.thin) != LPT_OK) bad(std::string("KHR_materials_transmission rejected: ") + lpt_last_error());
@@ -438,10 +440,11 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size) {
 
 extern "C" {
 
-int lpt_load_gltf(lpt_scene *scene, const uint8_t *data, size_t size) {
-    if (!scene || !data) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf: null");
+int lpt_load_gltf_ex(lpt_scene *scene, const uint8_t *data, size_t size, uint32_t flags) {
+    if (!scene || !data) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf_ex: null");
+    if (flags & ~LPT_GLTF_READ_BLEND) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf_ex: unknown flags 0x%x", flags);
     try {
-        lpt::load(scene, data, size);
+        lpt::load(scene, data, size, flags);
     } catch (const lpt::GltfError &e) {
         // reference maps every gltf::Error to Error::FileNotFound (gltf.rs:49-53)
         return lpt::fail(LPT_ERR_FILE_NOT_FOUND, "file not found: %s", e.what.c_str());
@@ -451,12 +454,23 @@ int lpt_load_gltf(lpt_scene *scene, const uint8_t *data, size_t size) {
     return LPT_OK;
 }
 
-int lpt_load_gltf_path(lpt_scene *scene, const char *path) {
-    if (!scene || !path) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf_path: null");
+int lpt_load_gltf(lpt_scene *scene, const uint8_t *data, size_t size) {
+    if (!scene || !data) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf: null");
+    return lpt_load_gltf_ex(scene, data, size, 0u);
+}
+
+int lpt_load_gltf_path_ex(lpt_scene *scene, const char *path, uint32_t flags) {
+    if (!scene || !path) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf_path_ex: null");
+    if (flags & ~LPT_GLTF_READ_BLEND) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf_path_ex: unknown flags 0x%x", flags);
     std::ifstream f(path, std::ios::binary);
     if (!f) return lpt::fail(LPT_ERR_FILE_NOT_FOUND, "file not found: %s", path);
     std::vector<uint8_t> bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-    return lpt_load_gltf(scene, bytes.data(), bytes.size());
+    return lpt_load_gltf_ex(scene, bytes.data(), bytes.size(), flags);
+}
+
+int lpt_load_gltf_path(lpt_scene *scene, const char *path) {
+    if (!scene || !path) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf_path: null");
+    return lpt_load_gltf_path_ex(scene, path, 0u);
 }
 
 }  // extern "C"

@@ -92,8 +92,8 @@ struct DScene {
     // (the ones that run while n_punctual != 0) and by k_punctual_sample (probe_kernels.h)
     const float4 *punctual;
     uint32_t n_punctual;
-    // SPEC §20: alpha-masked materials.  alpha_tri[prim] = 0 for an opaque triangle, else 1 + the index of its record {cutoff, color.w, bits of the PLAIN image index
-    // (LPT_INVALID_INDEX: no alpha image), 0}.  Null / 0 for a scene without masks; read only by the MASK instantiations of the traversal (alpha_rejects) and, behind
+    // SPEC §20, §26: alpha-masked and alpha-blended materials.  alpha_tri[prim] = 0 for an opaque triangle, else 1 + the index of its record {cutoff, color.w, bits of
+    // the PLAIN image index (LPT_INVALID_INDEX: no alpha image), mode: 0 masked, 1 blended}.  Null / 0 for a scene with neither; read only by the MASK instantiations of the traversal (alpha_rejects) and, behind
     // n_alpha != 0, by emitter_sample (SPEC §23)
     const uint32_t *alpha_tri;
     const float4 *alpha_recs;
@@ -551,7 +551,8 @@ __device__ __forceinline__ uint2 node_test(const DScene &sc, RayState &rs, const
 
 // SPEC §20: does the alpha mask cut the candidate hit (prim, u, v) away?  Called right behind an accepted Woop test, by the MASK instantiations only.  An opaque
 // triangle costs one 4-byte load; everything else sits behind that branch — divergent and rare —, at a point of the step where the node rows and the triangle's
-// Woop rows are dead, so none of it is live across the child tests (the step's register peak).  The decision is a pure function of (prim, u, v).
+// Woop rows are dead, so none of it is live across the child tests (the step's register peak).  The decision is a pure function of (prim, u, v) —
+// also for a blended material (SPEC §26; the record's fourth float), whose threshold is a hash of those three instead of the cutoff.
 __device__ __forceinline__ int wrap_i(int x, int n);
 __device__ __forceinline__ int wrap_next(int w, int n);
 __device__ __forceinline__ bool alpha_rejects(const DScene &sc, const uint32_t prim, const float hu, const float hv) {
@@ -583,6 +584,10 @@ __device__ __forceinline__ bool alpha_rejects(const DScene &sc, const uint32_t p
         const float c01 = (float)base[4u * (size_t)(r1 + c0)] * 0.003921568859368563f, c11 = (float)base[4u * (size_t)(r1 + c1)] * 0.003921568859368563f;
         const float top = c00 * (1.0f - tx) + c10 * tx, bot = c01 * (1.0f - tx) + c11 * tx;
         a = a * (top * (1.0f - ty) + bot * ty);
+    }
+    if (rec.w != 0.0f) {   // SPEC §26, blended: the hit counts iff a > xi, xi in [0, 1) hashed from the hit's own (prim, u, v) — no ray state, none of §4's streams
+        const uint32_t h = pcg_hash(pcg_hash(pcg_hash(prim) ^ __float_as_uint(hu)) ^ __float_as_uint(hv));
+        return !(a > (float)(h >> 8) * 5.9604644775390625e-8f);
     }
     return !(a >= rec.x);
 }

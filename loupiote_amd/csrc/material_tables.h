@@ -28,9 +28,10 @@ enum { MAT_ALPHA = 0, MAT_TRANS, MAT_EMIS, MAT_NMAP, MAT_KINDS };
 
 static inline bool alpha_state(const lpt_scene &scene, uint32_t mat, MaterialRec &rec, uint32_t &plain_image) {
     const MaterialAlpha a = scene.material_alpha(mat);
-    if (a.mode != LPT_ALPHA_MASK) return false;
+    if (a.mode != LPT_ALPHA_MASK && a.mode != LPT_ALPHA_BLEND) return false;
     plain_image = a.image < scene.images.size() ? a.image : LPT_INVALID_INDEX;
-    rec = MaterialRec{a.cutoff, scene.materials[mat].color[3], bits_as_float(plain_image), 0.0f};
+    // the fourth float is the mode alpha_rejects branches on: 0 masked (a >= cutoff, SPEC §20), 1 blended (a > xi, SPEC §26)
+    rec = MaterialRec{a.cutoff, scene.materials[mat].color[3], bits_as_float(plain_image), a.mode == LPT_ALPHA_BLEND ? 1.0f : 0.0f};
     return true;
 }
 static inline bool trans_state(const lpt_scene &scene, uint32_t mat, MaterialRec &rec, uint32_t &plain_image) {

@@ -199,6 +199,18 @@ int lpt_scene_set_material_alpha(lpt_scene *s, uint32_t material_index, uint32_t
     return LPT_OK;
 }
 
+// SPEC §26: the third state of the same table.  BLEND has no cutoff: the stored one returns to its default and is not read
+int lpt_scene_set_material_alpha_blend(lpt_scene *s, uint32_t material_index, uint32_t alpha_image) {
+    if (!s) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_alpha_blend: null");
+    if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_alpha_blend: material %u of %zu", material_index, s->materials.size());
+    if (alpha_image != LPT_INVALID_INDEX && alpha_image >= s->images.size())
+        return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_alpha_blend: image %u of %zu", alpha_image, s->images.size());
+    if (s->alpha.size() < s->materials.size()) s->alpha.resize(s->materials.size());
+    MaterialAlpha &a = s->alpha[material_index];
+    a.mode = LPT_ALPHA_BLEND; a.cutoff = MaterialAlpha().cutoff; a.image = alpha_image;
+    return LPT_OK;
+}
+
 int lpt_scene_get_material_alpha(const lpt_scene *s, uint32_t material_index, uint32_t *mode, float *cutoff, uint32_t *alpha_image) {
     if (!s) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_alpha: null");
     if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_alpha: material %u of %zu", material_index, s->materials.size());
