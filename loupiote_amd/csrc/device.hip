@@ -4,7 +4,7 @@
 // (reference crates/lib/src/renderer.rs:392-549): pass order, the seed / bounces /
 // frame_count protocol and the accumulate flag.  raytrace() RECORDS (the reference records into an encoder the app submits
 // once, app.rs:335-337); a submission point launches the recorded calls as wavefronts of several samples per pixel
-// (record_call / flush_pending / wavefront_trace + wavefront_finish).  A renderer enqueues on its own HIP stream (accumulation,
+// (record_call / flush_pending / wavefront_prepare + enqueue_stage + wavefront_finish).  A renderer enqueues on its own HIP stream (accumulation,
 // filter passes, reads, the frame exchange: in call order) and on the streams of its wavefront lanes (the
 // traversal / shading of consecutive wavefronts, overlapped); nothing here waits for the GPU except the
 // read-back calls (the reference's only blocking point is read_pixels, :791) and scene edits.
@@ -19,7 +19,6 @@
 #include <map>
 #include <memory>
 #include <cstdlib>
-#include <functional>
 #include <mutex>
 #include <new>
 #include <numeric>
@@ -32,6 +31,7 @@
 #include "probe_kernels.h"
 #include "build_kernels.h"
 #include "launch_plan.h"
+#include "submission_plan.h"
 #include <hipcub/hipcub.hpp>
 #include <rccl/rccl.h>
 
@@ -247,9 +247,7 @@ struct lpt_renderer {
     ShardTable *d_table = nullptr;   // ... and the rule's copy in device memory for the unpack kernels; refreshed by alloc_frame_buffers
     bool use_noise = false, stats = false, timings = false;
     int sort_queues = 0;       // k_shade emits both ray queues ordered by direction octant within a block (lpt_renderer_set_sort_queues)
-    // the pieces of a cut batch against each other (LPT_EXP_LANE_PHASE; flush_pending): 0 free, 1 offset start, 2 alternating traversal.  1: the bench frame
-    // 10.44-10.47 ms against 10.52-10.53 free; 2: 11.87 (one traversal grid at a time gives up more than the shading beside it wins; profiles/r08_lane_phase_ab.txt)
-    uint32_t lane_phase = 1;
+    uint32_t lane_phase = 1;   // the pieces of a cut batch against each other (LPT_EXP_LANE_PHASE): 0 free, 1 offset start, 2 alternating traversal (submission_plan.h: the rules and what they measured)
     // device memory
     uint32_t n_slots = 0;
     float4 *accum = nullptr, *scratch = nullptr;
@@ -1907,7 +1905,7 @@ static void launch_filter(lpt_renderer *r, hipStream_t s) {
     const int cur = r->den_cur, prv = 1 - r->den_cur;
     const uint32_t npx = r->w * r->h;
     const uint32_t px_blocks = div_up(npx, kBlock);
-    const uint32_t stream_blocks = std::min<uint32_t>(px_blocks, (uint32_t)r->dev->compute_units * 8u);
+    const uint32_t stream_blocks = stream_grid(r, npx);
     hipLaunchKernelGGL(k_temporal, dim3(stream_blocks), dim3(kBlock), 0, s, (int)r->w, (int)r->h, r->den_noisy, r->den_gbuf[cur], r->den_gbuf[prv], r->den_motion,
                        r->den_rad[prv], r->den_mom[prv], r->den_hist[prv], r->den_rad[cur], r->den_mom[cur], r->den_hist[cur]);
     const float4 *result = r->den_rad[cur];
@@ -1949,24 +1947,46 @@ static void launch_k_trace(TraceVariant v, uint32_t blocks, size_t lds, hipStrea
 
 extern "C" {
 
-// How one stage of a wavefront's launches is ordered against the other lanes (flush_pending, LPT_EXP_LANE_PHASE): events it waits
+// How one stage of a wavefront's launches is ordered against the other lanes (submission_plan.h, LPT_EXP_LANE_PHASE): events it waits
 // for before its first launch / before its traversal launch, and the event recorded behind its traversal launch
 struct PhaseHooks { hipEvent_t wait_start = nullptr, wait_trav = nullptr, rec_trav = nullptr; };
 
-// A wavefront between its two halves (flush_pending): what the second half needs to know about the first
+// What the launches of one wavefront read (wavefront_prepare fills it, enqueue_stage and wavefront_finish read it): copies, so that the stages of the pieces
+// of a cut batch can be enqueued in any order across the lanes; `r`'s buffers and the scene do not change before the submission is enqueued
+struct WavefrontLaunch {
+    lpt_renderer *r = nullptr;
+    Wavefront *w = nullptr;          // the lane
+    hipStream_t s = nullptr;         // the stream the lane's launches go to
+    bool split = false;              // the renderer has more than one lane: the lane's `done` / `consumed` events order it against the renderer's stream
+    FrameParams p{};
+    GBufArgs gb{};                   // the denoising modes' targets and cameras
+    // the rest only for a wavefront with slots (p.n_slots != 0):
+    int slot = 0;                    // of the timing ring
+    uint32_t nb = 0, seed0 = 0;
+    WavefrontFacts f;
+    LaunchTuning tune;
+    LaunchPlan pl;
+    DScene sc{};
+    DProbe probe{};
+    DEnv ev{};                       // read by the ENV kernels alone
+    DNoise nz{};
+    OccProbe occ{nullptr, 0u, 0.0f};
+    size_t trace_lds = 0, coop_lds = 0;
+    int sort_queues = 0;
+    bool esamp = false;              // SPEC §23: the ESAMP forms of k_shade
+};
+
+// A wavefront between its two halves (flush_pending): what the second half needs to know about the first, and the first half's launches
 struct Ticket {
-    FrameParams p;
     int lane = 0;
-    bool split = false, denoise = false, packet = false;
-    CamBasis cur{};
-    uint32_t stages = 0;                                 // the launches of the first half, stage by stage (wavefront_trace)
-    std::function<int(uint32_t, const PhaseHooks &)> run;
+    bool denoise = false;
+    WavefrontLaunch launch;
 };
 
 // What the launches of one wavefront read about the frame: the camera of `view`, the renderer's size, seeds, shard and lens, `n_samples` samples over the rank's
-// slots [slot0, slot0 + piece_slots) (wavefront_trace; lpt_renderer_primary_rays runs k_raygen alone from the same record)
+// slots [slot0, slot0 + piece_slots) (wavefront_prepare; lpt_renderer_primary_rays runs k_raygen alone from the same record)
 static FrameParams frame_params(const lpt_renderer *r, const float view[16], uint32_t n_samples, uint32_t frame_count0, uint32_t seed0, bool acc0, uint32_t slot0, uint32_t piece_slots) {
-    FrameParams p;
+    FrameParams p = shard_params(r);             // camera.dimensions / global_uniforms.dimensions (:431,436), the shard
     p.right = mk3(view[0], view[1], view[2]);    // camera.rs:101-108: cols = right, up, direction, origin
     p.up = mk3(view[4], view[5], view[6]);
     p.fwd = mk3(view[8], view[9], view[10]);
@@ -1974,14 +1994,9 @@ static FrameParams frame_params(const lpt_renderer *r, const float view[16], uin
     const float th = tanf(0.5f * r->vfov);
     const float aspect = (float)r->w / (float)r->h;
     p.ax = aspect * th; p.ay = th;
-    p.width = r->w; p.height = r->h;             // camera.dimensions / global_uniforms.dimensions (:431,436)
     p.user_seed = r->user_seed;
     p.seed_counter = seed0;
-    p.rank = r->rank; p.world = r->world; p.tile_w = r->tile_w; p.tile_h = r->tile_h;
-    p.map = r->map;
-    shard_geometry(r, p.tiles_x, p.n_tiles, p.n_slots);
     p.slot0 = slot0;
-    p.block8 = (r->tile_w % 8u == 0u && r->tile_h % 8u == 0u) ? 1u : 0u;
     p.n_slots = piece_slots;                     // the slots of THIS wavefront
     p.frame_count = frame_count0;
     p.max_bounces = r->max_bounces;
@@ -1999,24 +2014,24 @@ static FrameParams frame_params(const lpt_renderer *r, const float view[16], uin
     return p;
 }
 
-// First half of a wavefront: the launches of `n_samples` recorded raytrace() calls over the rank's pixel slots
-// [slot0, slot0 + piece_slots) — ray generation, traversal, shading — on the wavefront's lane, from the protocol state the first
+// First half of a wavefront: the launches of the `b.n` recorded raytrace() calls over the rank's pixel slots
+// [piece.slot0, piece.slot0 + piece.n_slots) — ray generation, traversal, shading — on the wavefront's lane, from the protocol state the first
 // of the calls saw (frame_count0, seed0, acc0 = its accumulate flag; the later ones ran with accumulate == true by construction).
-// `defer`: the launches are left in tk.run for the caller to enqueue stage by stage; otherwise they are enqueued here.
-static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_samples, uint32_t frame_count0, uint32_t seed0, bool acc0,
-                           uint32_t slot0, uint32_t piece_slots, Ticket &tk, bool solo, bool defer = false) {
+// This is everything before the first launch: the lane `piece.lane` (submission_plan.h) and its buffers, the denoiser's flip and memsets, the wait for what consumed the
+// lane's previous radiance, the launch plan.  The launches themselves are left in `tk` for enqueue_stage, stage by stage.
+static int wavefront_prepare(lpt_renderer *r, const lpt_renderer::Pending &b, const SubmissionPiece &piece, Ticket &tk) {
+    r->n_wavefronts++;
     HIP_TRY(hipSetDevice(r->dev->ordinal));
     hipStream_t sm = r->stream;                  // accumulation, filter passes, bookkeeping, reads, the exchange: in call order
     const uint32_t nb = r->max_bounces;          // reference constant 3 (:398-399)
+    const uint32_t n_samples = b.n, seed0 = b.seed0;
 
-    const FrameParams p = frame_params(r, view, n_samples, frame_count0, seed0, acc0, slot0, piece_slots);
+    const FrameParams p = frame_params(r, b.view, n_samples, b.frame_count0, seed0, b.acc0, piece.slot0, piece.n_slots);
     const float th = tanf(0.5f * r->vfov);
     const uint32_t n_rays = p.n_slots * n_samples;
     const bool denoise = r->mode != LPT_BLIT_PATHTRACE;
-    // the lane (Wavefront) this call's rays live in: consecutive calls take the lanes in turn; the denoising modes
-    // carry frame-to-frame state (G-buffer ping-pong, motion) and stay on lane 0
     const bool split = r->n_lanes > 1;           // the wavefront runs on the lane's own stream (a single wavefront on the renderer's own stream instead: 2.89 against 2.90 ms per 1/8-shard frame, round 5)
-    const int lane = (denoise || !split) ? 0 : (int)(r->lane_rr++ % (uint32_t)r->n_lanes);
+    const int lane = (int)piece.lane;
     {
         int st = ensure_lane(r, lane);
         if (st != LPT_OK) return st;
@@ -2040,7 +2055,11 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
             if (st != LPT_OK) return st;
         }
     }
-    GBufArgs gb{};
+    tk = Ticket{};
+    tk.lane = lane; tk.denoise = denoise;
+    WavefrontLaunch &L = tk.launch;
+    L.r = r; L.w = &wf; L.s = s; L.split = split; L.p = p; L.nb = nb; L.seed0 = seed0;
+    GBufArgs &gb = L.gb;
     if (denoise) {
         int st = ensure_denoiser(r);
         if (st != LPT_OK) return st;
@@ -2065,106 +2084,108 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
         gb.prev = r->prev_cam;
     }
 
-    DProbe probe = r->probe ? r->probe->d : DProbe{(const uint8_t *)r->default_probe, 1u, 1u};
+    L.probe = r->probe ? r->probe->d : DProbe{(const uint8_t *)r->default_probe, 1u, 1u};
     bool env = false;   // SPEC §18: the ENV kernels while the mode is on and the bound probe has a distribution
     if (r->env_sampling && r->probe) TRY(probe_env(const_cast<lpt_probe *>(r->probe), env));
-    const DEnv ev = env ? r->probe->env : DEnv{};
-    DNoise nz{(const uint8_t *)r->noise, r->noise_w, r->noise_h, (r->use_noise && r->noise) ? 1u : 0u};
+    L.ev = env ? r->probe->env : DEnv{};
+    L.nz = DNoise{(const uint8_t *)r->noise, r->noise_w, r->noise_h, (r->use_noise && r->noise) ? 1u : 0u};
     const DScene &sc = r->sg->d;
     if (r->timings) { r->ring_pos++; harvest_slot(r, cur_slot(r)); }
+    if (!p.n_slots) return LPT_OK;
 
-    tk.stages = 0; tk.run = nullptr;
-    if (p.n_slots) {
-        // what the launches depend on, and the decision (launch_plan.h: the rules are stated there)
-        WavefrontFacts f;
-        f.n_rays = n_rays; f.n_slots = p.n_slots; f.slot0 = p.slot0; f.n_samples = n_samples; f.cus = (uint32_t)r->dev->compute_units;
-        f.solo = solo; f.stats = r->stats; f.denoise = denoise; f.env = env;
-        f.masked = sc.n_alpha != 0u; f.trans = sc.n_trans != 0u; f.emis = sc.n_emis != 0u; f.nmap = sc.n_nmap != 0u; f.lens = r->lens_r > 0.0f; f.punct = sc.n_punctual != 0u; f.max_depth = r->sg->stats.max_depth; f.stack_entries = sc.stack_entries;
-        f.pixel_rad = 2.0f * th / (float)std::max(r->h, 1u); f.dense = (r->w % r->tile_w == 0u) && (r->h % r->tile_h == 0u); f.block8 = p.block8 != 0u;
-        f.lim = KernelLimits{kBlock, kTraceBlock, kTailMax, kCoopWavesPerCu, kPacketBlocksPerCu, kPacketMaxPixelRad};
-        const LaunchTuning tune = r->tune;
-        const LaunchPlan pl = plan_wavefront(tune, f);
-        tk.packet = pl.packet;
-        OccProbe occ{nullptr, 0u, 0.0f};   // its table belongs to the renderer
-        if (pl.occ_probe && r->occ_table && r->occ_cell > 0.0f) occ = OccProbe{r->occ_table, kOccEntries - 1u, 1.0f / r->occ_cell};
-        const size_t trace_lds = pl.stack_lds + (pl.tail ? sizeof(uint32_t) * tail_lds_words(f.max_depth) : 0u) + (pl.stats_lds_pad ? 64u : 0u);
-        const size_t coop_lds = sizeof(uint32_t) * coop_stack_entries(kCoopStack, f.max_depth);
-        const int sort_queues = r->sort_queues;
-        const bool esamp = r->emissive_sampling && f.emis && sc.n_emit != 0u;   // SPEC §23: the ESAMP forms of k_shade while the mode is on and the scene has an emitter distribution
-        // The launches in stages, so that the pieces of a cut batch can be enqueued stage by stage across the lanes (flush_pending,
-        // LPT_EXP_LANE_PHASE): stage 0 = counters, ray generation and the primary rays (with the path kernel: the whole wavefront),
-        // stage b + 1 = shade(b) and the traversal launch behind it.  `ph` orders the stage against the other lanes' (stream events only).
-        // The closure holds copies of what the launches read; `r`'s buffers and the scene do not change before the submission is enqueued.
-        const int slot = cur_slot(r);
-        Wavefront *w = &wf;
-        tk.stages = nb + 1u;
-        tk.run = [=](uint32_t t, const PhaseHooks &ph) -> int {
-            if (ph.wait_start) HIP_TRY(hipStreamWaitEvent(s, ph.wait_start, 0));
-            // Traversal launches: closest-hit rays of bounce b+1 and shadow rays of bounce b, both produced by shade(b), are traced by
-            // ONE persistent launch (k_trace) — nb+1 traversal launches per frame instead of 2*nb.
-            auto trace = [&](int cb, int sb) {
-                stage_begin(r, cb >= 0 ? ST_INTERSECT : ST_SHADOW, s, slot);  // :457-464, :493-498
-                const Queue qin = w->q[(uint32_t)(cb < 0 ? 0 : cb) & 1u];
-                const int launch_no = cb >= 0 ? cb : (int)nb;   // which strag_count[] this launch fills
-                // every ray of both queues (coop-all), or the stragglers a budgeted launch left in w->strag: a whole wave each
-                auto coop = [&](const uint32_t *strag) { with_flags([&](auto S) { hipLaunchKernelGGL(k_trace_coop<decltype(S)::value>, dim3(pl.coop_blocks), dim3(kTraceBlock), coop_lds, s, sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, strag, launch_no); }, f.stats); };
-                if (pl.coop_all) coop(nullptr);
-                else {
-                    launch_k_trace(pl.variant, pl.trace_blocks, trace_lds, s, TraceKernargs{sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, tune.refill, occ, pl.budget, w->strag, launch_no, pl.tail});
-                    if (pl.budget) coop(w->strag);
-                }
-                stage_end(r, s, slot);
-            };
-            if (t == 0u) {
-                HIP_TRY(hipMemsetAsync(w->ctr, 0, sizeof(FrameCounters), s));
-                // "ray generation" (:444-448)
-                stage_begin(r, ST_RAYGEN, s, slot);
-                with_flags([&](auto D, auto L) { hipLaunchKernelGGL((k_raygen<decltype(D)::value, decltype(L)::value>), dim3(pl.stream_blocks), dim3(kBlock), 0, s, p, nz, w->q[0], w->Lsum, w->ctr); }, f.dense, f.lens);   // LENS: SPEC §25
-                stage_end(r, s, slot);
-                if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
-                if (pl.packet) {
-                    // the primary rays: 64 consecutive queue entries are an 8x8-pixel patch of one sample — packet traversal (k_trace_packet)
-                    stage_begin(r, ST_PRIMARY, s, slot);
-                    with_flags([&](auto S) { hipLaunchKernelGGL(k_trace_packet<decltype(S)::value>, dim3(pl.packet_blocks), dim3(kTraceBlock), pl.packet_lds, s, sc, w->q[0], w->hits, w->ctr, 0, pl.quad_slots); }, f.stats);
-                    stage_end(r, s, slot);
-                } else if (pl.coop_all || !pl.path) trace(0, -1);   // a path-kernel wavefront traces its primary rays itself
-                // every bounce behind the primary hits in ONE persistent launch — the passes of renderer.rs:484-509 without a chip-wide barrier between them (kernels.h k_path); same frame, same counters
-                if (pl.path) {
-                    stage_begin(r, ST_PATH, s, slot);
-                    const size_t plds = pl.stack_lds + kPathLdsExtra;   // stacks + sRGB table + per-bounce counters
-                    const float4 *h0 = pl.packet ? w->hits : (const float4 *)nullptr;
-                    // the instantiation: G-buffer x stats x PUNCT (SPEC §19) x ENV (SPEC §18: `e` is the probe's distribution, or nothing)
-                    with_flags([&](auto G, auto S, auto P) {
-                        auto launch = [&](auto... e) { hipLaunchKernelGGL((k_path<decltype(G)::value, decltype(S)::value, sizeof...(e) != 0, decltype(P)::value, decltype(e)...>), dim3(pl.path_blocks), dim3(kTraceBlock), plds, s, sc, probe, nz, p, w->q[0], h0, w->Lsum, w->ctr, seed0, gb, tune.path_refill, e...); };
-                        if (f.env) launch(ev); else launch();
-                    }, f.denoise, f.stats, f.punct);
-                    stage_end(r, s, slot);
-                }
-            } else if (!pl.path) {
-                const uint32_t b = t - 1u;
-                const uint32_t seed = seed0 + t;     // += 1 per bounce (:453, :487)
-                const Queue qin = w->q[b & 1u], qout = w->q[(b + 1u) & 1u];
-                stage_begin(r, ST_SHADE, s, slot);            // :471-480, :502-508
-                // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); PUNCT / ENV as for k_path; TRANS: SPEC §21; EMIS: SPEC §22; ESAMP: SPEC §23, only with EMIS; NMAP: SPEC §24
-                const ShadeKernargs ska{sc, probe, nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, gb, sort_queues, ev};   // ev: read by the ENV forms alone
-                with_flags([&](auto G, auto E, auto P, auto Tr, auto Em, auto Es, auto Nm) {
-                    hipLaunchKernelGGL((k_shade<decltype(G)::value, decltype(E)::value, decltype(P)::value, decltype(Tr)::value, decltype(Em)::value, decltype(Em)::value && decltype(Es)::value, decltype(Nm)::value>), dim3(pl.shade_blocks), dim3(kBlock), 0, s, ska);
-                }, f.denoise && b == 0u, f.env, f.punct, f.trans, f.emis, esamp, f.nmap);
-                stage_end(r, s, slot);
-                if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
-                trace(b + 1u < nb ? (int)(b + 1u) : -1, (int)b);
-            }
-            if (ph.rec_trav) HIP_TRY(hipEventRecord(ph.rec_trav, s));
-            if (t == nb && split) HIP_TRY(hipEventRecord(w->done, s));
-            HIP_TRY(hipGetLastError());
-            return LPT_OK;
-        };
-        for (uint32_t t = 0; !defer && t < tk.stages; ++t) {
-            const int st = tk.run(t, PhaseHooks{});
-            if (st != LPT_OK) return st;
-        }
+    // what the launches depend on, and the decision (launch_plan.h: the rules are stated there)
+    WavefrontFacts &f = L.f;
+    f.n_rays = n_rays; f.n_slots = p.n_slots; f.slot0 = p.slot0; f.n_samples = n_samples; f.cus = (uint32_t)r->dev->compute_units;
+    f.solo = piece.solo; f.stats = r->stats; f.denoise = denoise; f.env = env;
+    f.masked = sc.n_alpha != 0u; f.trans = sc.n_trans != 0u; f.emis = sc.n_emis != 0u; f.nmap = sc.n_nmap != 0u; f.lens = r->lens_r > 0.0f; f.punct = sc.n_punctual != 0u; f.max_depth = r->sg->stats.max_depth; f.stack_entries = sc.stack_entries;
+    f.pixel_rad = 2.0f * th / (float)std::max(r->h, 1u); f.dense = (r->w % r->tile_w == 0u) && (r->h % r->tile_h == 0u); f.block8 = p.block8 != 0u;
+    f.lim = KernelLimits{kBlock, kTraceBlock, kTailMax, kCoopWavesPerCu, kPacketBlocksPerCu, kPacketMaxPixelRad};
+    L.tune = r->tune;
+    L.sc = sc;
+    const LaunchPlan &pl = L.pl = plan_wavefront(L.tune, f);
+    if (pl.occ_probe && r->occ_table && r->occ_cell > 0.0f) L.occ = OccProbe{r->occ_table, kOccEntries - 1u, 1.0f / r->occ_cell};   // its table belongs to the renderer
+    L.trace_lds = pl.stack_lds + (pl.tail ? sizeof(uint32_t) * tail_lds_words(f.max_depth) : 0u) + (pl.stats_lds_pad ? 64u : 0u);
+    L.coop_lds = sizeof(uint32_t) * coop_stack_entries(kCoopStack, f.max_depth);
+    L.sort_queues = r->sort_queues;
+    L.esamp = r->emissive_sampling && f.emis && sc.n_emit != 0u;   // SPEC §23: the ESAMP forms of k_shade while the mode is on and the scene has an emitter distribution
+    L.slot = cur_slot(r);
+    return LPT_OK;
+}
+
+// One traversal launch: closest-hit rays of bounce b+1 and shadow rays of bounce b, both produced by shade(b), are traced by
+// ONE persistent launch (k_trace) — nb+1 traversal launches per frame instead of 2*nb.
+static void launch_traversal(const WavefrontLaunch &L, int cb, int sb) {
+    lpt_renderer *r = L.r;
+    const Wavefront *w = L.w;
+    hipStream_t s = L.s;
+    const LaunchPlan &pl = L.pl;
+    stage_begin(r, cb >= 0 ? ST_INTERSECT : ST_SHADOW, s, L.slot);  // :457-464, :493-498
+    const Queue qin = w->q[(uint32_t)(cb < 0 ? 0 : cb) & 1u];
+    const int launch_no = cb >= 0 ? cb : (int)L.nb;   // which strag_count[] this launch fills
+    // every ray of both queues (coop-all), or the stragglers a budgeted launch left in w->strag: a whole wave each
+    auto coop = [&](const uint32_t *strag) { with_flags([&](auto S) { hipLaunchKernelGGL(k_trace_coop<decltype(S)::value>, dim3(pl.coop_blocks), dim3(kTraceBlock), L.coop_lds, s, L.sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, strag, launch_no); }, L.f.stats); };
+    if (pl.coop_all) coop(nullptr);
+    else {
+        launch_k_trace(pl.variant, pl.trace_blocks, L.trace_lds, s, TraceKernargs{L.sc, qin, w->hits, w->sq, w->Lsum, w->ctr, cb, sb, L.tune.refill, L.occ, pl.budget, w->strag, launch_no, pl.tail});
+        if (pl.budget) coop(w->strag);
     }
-    tk.p = p; tk.lane = lane; tk.split = split; tk.denoise = denoise; tk.cur = gb.cur;
+    stage_end(r, s, L.slot);
+}
+
+// Stage t of a prepared wavefront's launches: stage 0 = counters, ray generation and the primary rays (with the path kernel: the whole wavefront),
+// stage b + 1 = shade(b) and the traversal launch behind it.  `ph` orders the stage against the other lanes' (stream events only).
+static int enqueue_stage(const WavefrontLaunch &L, uint32_t t, const PhaseHooks &ph) {
+    lpt_renderer *r = L.r;
+    const Wavefront *w = L.w;
+    hipStream_t s = L.s;
+    const int slot = L.slot;
+    const uint32_t nb = L.nb;
+    const LaunchPlan &pl = L.pl;
+    const WavefrontFacts &f = L.f;
+    const FrameParams &p = L.p;
+    if (ph.wait_start) HIP_TRY(hipStreamWaitEvent(s, ph.wait_start, 0));
+    if (t == 0u) {
+        HIP_TRY(hipMemsetAsync(w->ctr, 0, sizeof(FrameCounters), s));
+        // "ray generation" (:444-448)
+        stage_begin(r, ST_RAYGEN, s, slot);
+        with_flags([&](auto D, auto Ln) { hipLaunchKernelGGL((k_raygen<decltype(D)::value, decltype(Ln)::value>), dim3(pl.stream_blocks), dim3(kBlock), 0, s, p, L.nz, w->q[0], w->Lsum, w->ctr); }, f.dense, f.lens);   // LENS: SPEC §25
+        stage_end(r, s, slot);
+        if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
+        if (pl.packet) {
+            // the primary rays: 64 consecutive queue entries are an 8x8-pixel patch of one sample — packet traversal (k_trace_packet)
+            stage_begin(r, ST_PRIMARY, s, slot);
+            with_flags([&](auto S) { hipLaunchKernelGGL(k_trace_packet<decltype(S)::value>, dim3(pl.packet_blocks), dim3(kTraceBlock), pl.packet_lds, s, L.sc, w->q[0], w->hits, w->ctr, 0, pl.quad_slots); }, f.stats);
+            stage_end(r, s, slot);
+        } else if (pl.coop_all || !pl.path) launch_traversal(L, 0, -1);   // a path-kernel wavefront traces its primary rays itself
+        // every bounce behind the primary hits in ONE persistent launch — the passes of renderer.rs:484-509 without a chip-wide barrier between them (kernels.h k_path); same frame, same counters
+        if (pl.path) {
+            stage_begin(r, ST_PATH, s, slot);
+            const size_t plds = pl.stack_lds + kPathLdsExtra;   // stacks + sRGB table + per-bounce counters
+            const float4 *h0 = pl.packet ? w->hits : (const float4 *)nullptr;
+            // the instantiation: G-buffer x stats x PUNCT (SPEC §19) x ENV (SPEC §18: `e` is the probe's distribution, or nothing)
+            with_flags([&](auto G, auto S, auto P) {
+                auto launch = [&](auto... e) { hipLaunchKernelGGL((k_path<decltype(G)::value, decltype(S)::value, sizeof...(e) != 0, decltype(P)::value, decltype(e)...>), dim3(pl.path_blocks), dim3(kTraceBlock), plds, s, L.sc, L.probe, L.nz, p, w->q[0], h0, w->Lsum, w->ctr, L.seed0, L.gb, L.tune.path_refill, e...); };
+                if (f.env) launch(L.ev); else launch();
+            }, f.denoise, f.stats, f.punct);
+            stage_end(r, s, slot);
+        }
+    } else if (!pl.path) {
+        const uint32_t b = t - 1u;
+        const uint32_t seed = L.seed0 + t;     // += 1 per bounce (:453, :487)
+        const Queue qin = w->q[b & 1u], qout = w->q[(b + 1u) & 1u];
+        stage_begin(r, ST_SHADE, s, slot);            // :471-480, :502-508
+        // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); PUNCT / ENV as for k_path; TRANS: SPEC §21; EMIS: SPEC §22; ESAMP: SPEC §23, only with EMIS; NMAP: SPEC §24
+        const ShadeKernargs ska{L.sc, L.probe, L.nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, L.gb, L.sort_queues, L.ev};   // ev: read by the ENV forms alone
+        with_flags([&](auto G, auto E, auto P, auto Tr, auto Em, auto Es, auto Nm) {
+            hipLaunchKernelGGL((k_shade<decltype(G)::value, decltype(E)::value, decltype(P)::value, decltype(Tr)::value, decltype(Em)::value, decltype(Em)::value && decltype(Es)::value, decltype(Nm)::value>), dim3(pl.shade_blocks), dim3(kBlock), 0, s, ska);
+        }, f.denoise && b == 0u, f.env, f.punct, f.trans, f.emis, L.esamp, f.nmap);
+        stage_end(r, s, slot);
+        if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
+        launch_traversal(L, b + 1u < nb ? (int)(b + 1u) : -1, (int)b);
+    }
+    if (ph.rec_trav) HIP_TRY(hipEventRecord(ph.rec_trav, s));
+    if (t == nb && L.split) HIP_TRY(hipEventRecord(w->done, s));
+    HIP_TRY(hipGetLastError());
     return LPT_OK;
 }
 
@@ -2173,12 +2194,12 @@ static int wavefront_trace(lpt_renderer *r, const float view[16], uint32_t n_sam
 // completes are resolved (or tonemapped) and copied to the host right behind its accumulation.
 static int wavefront_finish(lpt_renderer *r, const Ticket &tk, const ReadPlan *read, uint32_t row0, uint32_t row1) {
     hipStream_t sm = r->stream;
-    const FrameParams &p = tk.p;
+    const FrameParams &p = tk.launch.p;
     Wavefront &wf = r->wf[tk.lane];
-    const bool split = tk.split;
+    const bool split = tk.launch.split;
     const uint32_t nb = p.max_bounces;
     if (p.n_slots) {
-        const uint32_t stream_blocks = std::min<uint32_t>(div_up(p.n_slots * p.n_samples, kBlock), (uint32_t)r->dev->compute_units * 8u);
+        const uint32_t stream_blocks = stream_grid(r, p.n_slots * p.n_samples);
         if (split) HIP_TRY(hipStreamWaitEvent(sm, wf.done, 0));
         if (r->mode == LPT_BLIT_PATHTRACE) {
             // AccumulationPass (:523-538)
@@ -2206,7 +2227,7 @@ static int wavefront_finish(lpt_renderer *r, const Ticket &tk, const ReadPlan *r
             if (r->world == 1u) launch_filter(r, sm);
             stage_end(r, sm);
         }  // GBuffer / MotionVector: the primary pass has written the debug targets; nothing else runs (:539)
-        hipLaunchKernelGGL(k_finish_frame, dim3(1), dim3(64), 0, sm, wf.ctr, r->totals, nb, tk.packet ? 1u : 0u);
+        hipLaunchKernelGGL(k_finish_frame, dim3(1), dim3(64), 0, sm, wf.ctr, r->totals, nb, tk.launch.pl.packet ? 1u : 0u);
         if (split) {
             HIP_TRY(hipEventRecord(wf.consumed, sm));
             wf.consumed_recorded = true;
@@ -2215,53 +2236,28 @@ static int wavefront_finish(lpt_renderer *r, const Ticket &tk, const ReadPlan *r
     } else if (r->mode != LPT_BLIT_PATHTRACE) {
         r->den_inputs_ready = true;   // a rank without tiles (a pure compositor / filter rank) still takes part in the frame's exchange
     }
-    if (tk.denoise) r->prev_cam = tk.cur;        // prev_model_to_screen = P * V^-1 (:542-546)
+    if (tk.denoise) r->prev_cam = tk.launch.gb.cur;       // prev_model_to_screen = P * V^-1 (:542-546)
     return LPT_OK;
 }
 
 // Submit what has been recorded (every synchronisation point and every setter that the launches read calls this first).
-// With an explicit batch size (lpt_renderer_set_max_fused(n >= 1), lpt_renderer_raytrace_n) the recorded calls are ONE wavefront.
-// Otherwise a batch of more than about 4 M rays is cut SPATIALLY — runs of whole tile rows (of whole tiles on a sharded frame),
-// every run with all the recorded samples — and the pieces take the renderer's lanes in turn: at 1920x1080 the 4 samples of a
-// frame leave as two wavefronts of 4.1 M rays (the upper and the lower half of the image), the shading of one overlaps the
-// traversal of the other (measured for two 4 M-ray wavefronts: 13.30 ms per frame against 13.68 for one 8 M-ray wavefront and
-// 14.1 for four 2 M-ray ones), and the piece that was launched first is complete about one stage before the last:
+// Where the batch is cut into wavefronts, which lane and ticket each takes and the order of their halves and stages is plan_submission's decision
+// (submission_plan.h: the rules are stated there); this walks its steps.  The piece that was launched first is complete about one stage before the last:
 // `read` (lpt_renderer_read_radiance, lpt_renderer_blit_rgba8) has every piece's rows copied to the host as soon as they are final.
 static int flush_pending(lpt_renderer *r, const ReadPlan *read) {
     if (!r->pend.n) return LPT_OK;
     const lpt_renderer::Pending b = r->pend;
     r->pend.n = 0;
-    uint32_t tiles_x, n_tiles, n_slots;
-    shard_geometry(r, tiles_x, n_tiles, n_slots);
-    const uint32_t area = r->tile_w * r->tile_h;
-    const bool whole_rows = r->world == 1u;                       // the rank's slots are the tiles in row-major order
-    const uint32_t granule = whole_rows ? tiles_x * area : area;  // slots per tile row / per tile
-    const uint32_t granules = granule ? n_slots / granule : 0u;
-    uint32_t per_piece = granules;
-    // ... and a batch of more than 3 M rays that would still fit one wavefront leaves as TWO (on the renderer's two lanes): a 1/2 shard of the headline frame
-    // (4.15 M rays) 7.22 -> 6.81 ms; below that the halves are too small to hide each other's drains (a 1/4 shard, 2 x 1.04 M: 4.62 -> 4.75 ms; profiles/r04_experiments_ab.txt E)
-    const uint64_t total = (uint64_t)n_slots * b.n;
-    if (!r->max_fused && r->mode == LPT_BLIT_PATHTRACE && granules > 1u && (total > r->wavefront_rays || (r->split_rays && total > r->split_rays && r->n_lanes > 1))) {
-        const uint64_t fit = r->wavefront_rays / ((uint64_t)granule * b.n);           // granules of b.n samples in about 4 M rays
-        const uint32_t pieces = std::max(2u, div_up(granules, (uint32_t)std::max<uint64_t>(fit, 1u)));
-        per_piece = div_up(granules, pieces);                     // the same number of pieces, evened out
-    }
-    Ticket tk[kMaxLanes];
-    if (!granules) {   // nothing owned (a compositor rank): one empty wavefront keeps the bookkeeping of the call
-        r->n_wavefronts++;
-        const int st = wavefront_trace(r, b.view, b.n, b.frame_count0, b.seed0, b.acc0, 0u, 0u, tk[0], true);
-        return st != LPT_OK ? st : wavefront_finish(r, tk[0], nullptr, 0u, 0u);
-    }
-    // The first halves run ahead of the second halves by the number of lanes: wavefront k's launches are enqueued before the
-    // renderer's stream is given the accumulation (and the read-back copy, which blocks the host when the destination is pageable
-    // memory) of wavefront k - lanes — the wavefront that used the same lane, whose buffers k overwrites.
-    const bool early = read && whole_rows && r->mode == LPT_BLIT_PATHTRACE;
-    const uint32_t ahead = (r->mode != LPT_BLIT_PATHTRACE || r->n_lanes < 2) ? 1u : (uint32_t)r->n_lanes;
-    const uint32_t pieces = div_up(granules, per_piece);
-    auto finish = [&](uint32_t k) {
-        const uint32_t g0 = k * per_piece, g1 = std::min(granules, g0 + per_piece);
-        return wavefront_finish(r, tk[k % ahead], early ? read : nullptr, std::min(r->h, g0 * r->tile_h), std::min(r->h, g1 * r->tile_h));
-    };
+    SubmissionFacts f;
+    uint32_t n_tiles;
+    shard_geometry(r, f.tiles_x, n_tiles, f.n_slots);
+    f.tile_w = r->tile_w; f.tile_h = r->tile_h; f.world = r->world; f.height = r->h;
+    f.n = b.n; f.max_fused = r->max_fused; f.pathtrace = r->mode == LPT_BLIT_PATHTRACE;
+    f.wavefront_rays = r->wavefront_rays; f.split_rays = r->split_rays;
+    f.n_lanes = (uint32_t)r->n_lanes; f.lane_phase = r->lane_phase; f.bounces = r->max_bounces;
+    f.lane_rr = r->lane_rr; f.read = read != nullptr;
+    const SubmissionPlan plan = plan_submission(f);
+    r->lane_rr = plan.lane_rr;
     // A failure part way leaves wavefronts on the lanes' streams whose second halves (the waits that put them behind the renderer's
     // stream) were never enqueued: wait for them here, so that nothing is still running on buffers a later call frees or reuses
     auto bail = [&](int st) {
@@ -2272,48 +2268,38 @@ static int flush_pending(lpt_renderer *r, const ReadPlan *read) {
         hipStreamSynchronize(r->stream);
         return st;
     };
-    // LPT_EXP_LANE_PHASE: the pieces that run side by side on the lanes (a group of `ahead`) are enqueued stage by stage — stage t of every
-    // piece of the group before stage t + 1 of any — so that the events that order them are always recorded before they are waited for.
-    // 1 (offset start): a piece's first launch waits for the previous piece's primary traversal; 2 (alternating traversal): a piece's
-    // traversal launch t waits for the previous piece's traversal t, the group's first piece's for the last piece's traversal t - 1,
-    // so one traversal grid at a time holds the chip and the other pieces shade beside it.
-    const uint32_t phase = (ahead > 1u && pieces > 1u) ? r->lane_phase : 0u;
-    const uint32_t group = phase ? ahead : 1u;
-    for (uint32_t k0 = 0; k0 < pieces; k0 += group) {
-        const uint32_t k1 = std::min(pieces, k0 + group);
-        for (uint32_t k = k0; k < k1; ++k) {
-            if (k >= ahead) { const int st = finish(k - ahead); if (st != LPT_OK) return bail(st); }
-            const uint32_t g0 = k * per_piece, g1 = std::min(granules, g0 + per_piece);
-            r->n_wavefronts++;
-            const int st = wavefront_trace(r, b.view, b.n, b.frame_count0, b.seed0, b.acc0, g0 * granule, (g1 - g0) * granule, tk[k % ahead], pieces == 1u, phase != 0u);
-            if (st != LPT_OK) return bail(st);
-        }
-        if (!phase) continue;
-        const uint32_t stages = tk[k0 % ahead].stages;   // nb + 1 for every piece
-        for (uint32_t k = k0; k < k1; ++k) {
-            Wavefront &wf = r->wf[tk[k % ahead].lane];
-            while (wf.trav.size() < stages) {
+    Ticket tickets[kMaxLanes];
+    const auto trav = [&](const TravEvent &e) { return e.piece < 0 ? (hipEvent_t) nullptr : r->wf[plan.pieces[(size_t)e.piece].lane].trav[e.stage]; };
+    for (const SubmissionStep &step : plan.steps) {
+        const SubmissionPiece &piece = plan.pieces[step.piece];
+        Ticket &tk = tickets[piece.ticket];
+        int st = LPT_OK;
+        switch (step.kind) {
+        case SubmissionStep::Prepare: {
+            st = wavefront_prepare(r, b, piece, tk);
+            std::vector<hipEvent_t> &ev = r->wf[piece.lane].trav;   // the events the piece's stages record
+            while (st == LPT_OK && ev.size() < plan.trav_events) {
                 hipEvent_t e = nullptr;
                 const hipError_t he = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-                if (he != hipSuccess) return bail(fail(LPT_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(he)));
-                wf.trav.push_back(e);
+                if (he != hipSuccess) st = fail(LPT_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(he));
+                else ev.push_back(e);
             }
+            break;
         }
-        for (uint32_t t = 0; t < stages; ++t) {
-            for (uint32_t k = k0; k < k1; ++k) {
-                const Ticket &cur = tk[k % ahead];
-                const Wavefront &prev = r->wf[tk[(k > k0 ? k - 1u : k1 - 1u) % ahead].lane];
-                PhaseHooks ph;
-                ph.rec_trav = r->wf[cur.lane].trav[t];
-                if (phase == 1u && t == 0u && k > k0) ph.wait_start = prev.trav[0];
-                if (phase == 2u && k > k0) ph.wait_trav = prev.trav[t];
-                if (phase == 2u && k == k0 && t > 0u) ph.wait_trav = prev.trav[t - 1u];
-                const int st = cur.run ? cur.run(t, ph) : LPT_OK;
-                if (st != LPT_OK) return bail(st);
-            }
+        case SubmissionStep::Stage: {
+            PhaseHooks ph;
+            ph.wait_start = trav(step.wait_start);
+            ph.wait_trav = trav(step.wait_trav);
+            if (step.record) ph.rec_trav = r->wf[piece.lane].trav[step.t];
+            st = enqueue_stage(tk.launch, step.t, ph);
+            break;
         }
+        case SubmissionStep::Finish:
+            st = wavefront_finish(r, tk, read, piece.row0, piece.row1);   // the rows are empty but for the early read-back
+            break;
+        }
+        if (st != LPT_OK) return bail(st);
     }
-    for (uint32_t k = pieces > ahead ? pieces - ahead : 0u; k < pieces; ++k) { const int st = finish(k); if (st != LPT_OK) return bail(st); }
     return LPT_OK;
 }
 

@@ -1,4 +1,4 @@
-// Which kernels a wavefront runs, and with which grids: one host-side decision (plan_wavefront) that device.hip's wavefront_trace consumes.  Plain C++17, nothing from HIP:
+// Which kernels a wavefront runs, and with which grids: one host-side decision (plan_wavefront) that device.hip's wavefront_prepare consumes.  Plain C++17, nothing from HIP:
 // tests/tools/plan_check.cpp compiles it with g++ and tests/test_launch_plan.py checks the rules below on a CPU.  Every plan gives the same frame bit for bit.
 #pragma once
 #include <algorithm>

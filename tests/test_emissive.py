@@ -1,5 +1,5 @@
 """CPU: emissive materials (SPEC.md §22) on the host — the scene API's side table, what the glTF loader reads (emissiveFactor, emissiveTexture,
-KHR_materials_emissive_strength; SPEC §14(9)), the launch plan's `emis` fact through tests/tools/plan_emis_check.cpp, the bindings' agreement on the new entry points,
+KHR_materials_emissive_strength; SPEC §14(9)), the launch plan's `emis` fact through tests/tools/plan_fact_check.cpp, the bindings' agreement on the new entry points,
 and tests/emissive_ref.py against what it restates."""
 import json
 import os
@@ -158,9 +158,9 @@ def test_the_committed_fixture_is_the_writers_output():
 
 # ---------------------------------------------------------------- launch plan
 def test_emis_keeps_a_wavefront_off_the_path_kernel_and_changes_nothing_else(tmp_path):
-    exe = str(tmp_path / "plan_emis_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "tools", "plan_emis_check.cpp")], check=True)
-    p = subprocess.run([exe], capture_output=True, text=True)
+    exe = str(tmp_path / "plan_fact_check")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "tools", "plan_fact_check.cpp")], check=True)
+    p = subprocess.run([exe, "emis"], capture_output=True, text=True)
     assert p.returncode == 0, p.stderr
     out = json.loads(p.stdout)
     assert out["cases"] == 9 * 128 * 3 * 2 and 0 < out["with_path"] < out["cases"]      # the grid does reach plans that would have taken the path kernel

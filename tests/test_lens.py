@@ -1,6 +1,6 @@
 """CPU: the thin lens (SPEC.md §25) without a GPU — tests/lens_ref.py against hand-worked values and against tests/primary_ref.py with the lens closed, what the
 reference alone says about the scenes of tests/test_gpu_lens.py (the board's excluded share, the spot's numbers), the launch plan's `lens` fact through
-tests/tools/plan_lens_check.cpp, and the bindings' agreement on the three new entry points with the argument checks that need no device."""
+tests/tools/plan_fact_check.cpp, and the bindings' agreement on the three new entry points with the argument checks that need no device."""
 import ctypes as C
 import json
 import math
@@ -134,9 +134,9 @@ def test_the_spot_is_two_pixels_wide_and_its_disc_at_least_six():
 
 # ---------------------------------------------------------------- launch plan
 def test_lens_keeps_a_wavefront_off_packets_and_the_path_kernel_and_changes_nothing_else(tmp_path):
-    exe = str(tmp_path / "plan_lens_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "tools", "plan_lens_check.cpp")], check=True)
-    p = subprocess.run([exe], capture_output=True, text=True)
+    exe = str(tmp_path / "plan_fact_check")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "tools", "plan_fact_check.cpp")], check=True)
+    p = subprocess.run([exe, "lens"], capture_output=True, text=True)
     assert p.returncode == 0, p.stderr
     out = json.loads(p.stdout)
     assert out["cases"] == 9 * 512 * 3 * 2 * 3

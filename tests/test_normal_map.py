@@ -1,5 +1,5 @@
 """CPU: normal maps (SPEC.md §24) on the host — the scene API's side table, what the glTF loader reads (normalTexture and its scale; SPEC §14(10)), the launch plan's
-`nmap` fact through tests/tools/plan_nmap_check.cpp, the bindings' agreement on the new entry points, tests/normal_ref.py against closed forms and against its own
+`nmap` fact through tests/tools/plan_fact_check.cpp, the bindings' agreement on the new entry points, tests/normal_ref.py against closed forms and against its own
 binary32 restatement, and the cap on the decisions that the GPU test's committed inputs leave to rounding."""
 import json
 import os
@@ -138,9 +138,9 @@ def test_the_committed_fixture_is_the_writers_output():
 
 # ---------------------------------------------------------------- launch plan
 def test_nmap_keeps_a_wavefront_off_the_path_kernel_and_changes_nothing_else(tmp_path):
-    exe = str(tmp_path / "plan_nmap_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "tools", "plan_nmap_check.cpp")], check=True)
-    p = subprocess.run([exe], capture_output=True, text=True)
+    exe = str(tmp_path / "plan_fact_check")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "tools", "plan_fact_check.cpp")], check=True)
+    p = subprocess.run([exe, "nmap"], capture_output=True, text=True)
     assert p.returncode == 0, p.stderr
     out = json.loads(p.stdout)
     assert out["cases"] == 9 * 256 * 3 * 2 and 0 < out["with_path"] < out["cases"]      # the grid does reach plans that would have taken the path kernel
