@@ -403,6 +403,13 @@ impl Renderer {
         check(unsafe { ffi::lpt_renderer_get_emissive_sampling(self.h, &mut f) })?;
         Ok(f != 0)
     }
+    /// SPEC.md §27: punctual lights' shadow rays pass thin-walled transmissive triangles; off by default
+    pub fn set_glass_shadows(&mut self, on: bool) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_glass_shadows(self.h, on as i32) }) }
+    pub fn glass_shadows(&self) -> Result<bool, Error> {
+        let mut f = 0i32;
+        check(unsafe { ffi::lpt_renderer_get_glass_shadows(self.h, &mut f) })?;
+        Ok(f != 0)
+    }
     /// launch tuning (the `LPT_OPT_` constants of `ffi`): never changes a frame
     pub fn set_option(&mut self, option: i32, value: u64) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_option(self.h, option, value) }) }
     /// tile-sharded frames: bind a communicator (implies `set_shard(rank, world, 32, 8)`), then `exchange` after the frame's `raytrace` calls

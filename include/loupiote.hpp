@@ -209,6 +209,10 @@ class SceneGPU {  // scene.rs:56-64,151-188
     void sample_textures(const Device &device, uint32_t n, const uint32_t *prim, const float *bary, float *out) const {
         check(lpt_scene_gpu_sample_textures(device.inner(), h_, n, prim, bary, out));
     }
+    // SPEC.md §27: what a punctual light's shadow ray along dirs is answered at (prim, bary) by the traversal's own function, out[n][8] (lpt.h), for tools and tests
+    void glass_shadow(const Device &device, uint32_t n, const uint32_t *prim, const float *bary, const float *dirs, float *out) const {
+        check(lpt_scene_gpu_glass_shadow(device.inner(), h_, n, prim, bary, dirs, out));
+    }
     void sample_emitter(const Device &device, uint32_t n, const float *points, const float *rands, uint32_t *prim, uint32_t *sampled, float *y, float *wi, float *dist, float *cl,
                         float *p_a, float *E) const {
         check(lpt_scene_gpu_sample_emitter(device.inner(), h_, n, points, rands, prim, sampled, y, wi, dist, cl, p_a, E));
@@ -283,6 +287,9 @@ class Renderer {  // renderer.rs:169-811
     // SPEC.md §23: next-event estimation samples the emissive triangles too; off by default
     void set_emissive_sampling(bool on) { check(lpt_renderer_set_emissive_sampling(h_, on ? 1 : 0)); }
     bool emissive_sampling() const { int f = 0; check(lpt_renderer_get_emissive_sampling(h_, &f)); return f != 0; }
+    // SPEC.md §27: punctual lights' shadow rays pass thin-walled transmissive triangles (off by default)
+    void set_glass_shadows(bool on) { check(lpt_renderer_set_glass_shadows(h_, on ? 1 : 0)); }
+    bool glass_shadows() const { int f = 0; check(lpt_renderer_get_glass_shadows(h_, &f)); return f != 0; }
     /// SPEC.md §25: a thin-lens camera — lens radius in world units (0, the default: the pinhole) and the distance of the plane in focus; frames change with it, so reset_accumulation() belongs after the call
     void set_lens(float radius, float focus_distance = 1.0f) { check(lpt_renderer_set_lens(h_, radius, focus_distance)); }
     std::pair<float, float> lens() const { float r = 0.f, f = 0.f; check(lpt_renderer_get_lens(h_, &r, &f)); return {r, f}; }

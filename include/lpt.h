@@ -434,6 +434,13 @@ int lpt_scene_gpu_shading_normal(lpt_device *dev, const lpt_scene_gpu *sg, uint3
  * scene's baked triangle count.  Blocking; host arrays. */
 int lpt_scene_gpu_sample_textures(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, float *out);
 
+/* build-only extension (SPEC.md §27), for tests and tools in the manner of lpt_scene_gpu_shading_normal: what a punctual light's
+ * shadow ray along the unit direction dirs[i] is answered at a hit of baked triangle prim[i] at barycentrics bary[i] = (u, v), by the
+ * traversal's own function.  out[n][8] = {the channel transmittance tau rgb, the threshold xi, the pass bits as a uint32 (bit c: tau_c >
+ * xi), 0, 0, 0}; zeros for a triangle that is no thin-walled transmissive pane (opaque, solid glass) and for a degenerate one (xi is
+ * still the pane's there).  LPT_ERR_INVALID_ARG for a prim at or beyond the scene's baked triangle count.  Blocking; host arrays. */
+int lpt_scene_gpu_glass_shadow(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, const float *dirs, float *out);
+
 /* build-only extension (SPEC.md §21), for tests and tools in the manner of lpt_probe_sample: the interface event of the shading kernels
  * (kernels.h interface_sample), once per element.  Inputs, n of each: dirs[n][3] the ray's unit direction d, ns[n][3] the shading
  * normal, ngf[n][3] the geometric normal flipped against d, entering[n] (non-zero: the geometric normal was not flipped), base[n][3]
@@ -622,6 +629,14 @@ int lpt_renderer_get_env_sampling(const lpt_renderer *r, int *flag);
  * scene has an emitter distribution (an emissive material in use on a triangle with an area); recorded calls are submitted first. */
 int lpt_renderer_set_emissive_sampling(lpt_renderer *r, int flag);
 int lpt_renderer_get_emissive_sampling(const lpt_renderer *r, int *flag);
+/* new (SPEC.md §27): the shadow rays of punctual lights pass thin-walled transmissive triangles, each colour channel with the pane's
+ * straight-through transmittance (decided per hit from the hit's own bits: no random number is drawn), so a KHR_lights_punctual sun
+ * lights a room through a KHR_materials_transmission window.  Off (0) by default; off, every frame, launch and kernel is what it was
+ * (SPEC.md §21: shadow rays stop at glass).  Active while the bound scene has a punctual light and a thin-walled transmissive triangle;
+ * rectangle lights, the probe and emitters keep stopping at glass (their BSDF partners carry that light), and so does
+ * lpt_trace_occluded.  Frames change with the call, so lpt_renderer_reset_accumulation belongs after it; recorded calls are submitted first. */
+int lpt_renderer_set_glass_shadows(lpt_renderer *r, int flag);
+int lpt_renderer_get_glass_shadows(const lpt_renderer *r, int *flag);
 /* new (SPEC.md §25): a thin-lens camera.  `radius` >= 0 is the lens radius in world units (0, the default: the pinhole of SPEC.md §11, and
  * every frame, launch and kernel is what it was, whatever the focus distance); `focus_distance` > 0 (default 1) is the distance of the
  * plane in focus along the view's forward column, in units of its length.  A point on that plane is seen from the pixel the pinhole sees

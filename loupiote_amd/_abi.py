@@ -135,6 +135,7 @@ SIGNATURES = {
     "lpt_scene_gpu_sample_emitter": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lpt_scene_gpu_shading_normal": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "lpt_scene_gpu_sample_textures": (_i, [_vp, _vp, _u32, _vp, _vp, _vp]),
+    "lpt_scene_gpu_glass_shadow": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "lpt_interface_sample": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lpt_bsdf_probe": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "lpt_probe_upload": (_i, [_vp, _vp, _u32, _u32, _pvp]),
@@ -185,6 +186,8 @@ SIGNATURES = {
     "lpt_renderer_get_env_sampling": (_i, [_vp, C.POINTER(_i)]),
     "lpt_renderer_set_emissive_sampling": (_i, [_vp, _i]),
     "lpt_renderer_get_emissive_sampling": (_i, [_vp, C.POINTER(_i)]),
+    "lpt_renderer_set_glass_shadows": (_i, [_vp, _i]),
+    "lpt_renderer_get_glass_shadows": (_i, [_vp, C.POINTER(_i)]),
     "lpt_renderer_set_lens": (_i, [_vp, _f, _f]),
     "lpt_renderer_get_lens": (_i, [_vp, C.POINTER(_f), C.POINTER(_f)]),
     "lpt_renderer_primary_rays": (_i, [_vp, _vp, _u32, _vp, _vp]),

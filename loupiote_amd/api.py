@@ -437,6 +437,20 @@ class SceneGPU:
         return {"albedo": out[:, 0:3].copy(), "mra": out[:, 3:5].copy(), "emissive": out[:, 5:8].copy(), "normal": out[:, 8:11].copy(),
                 "rejected": out[:, 11].view(np.uint32) != 0, "uv": out[:, 12:14].copy()}
 
+    def glass_shadow(self, prim, bary, dirs):
+        """What a punctual light's shadow ray is answered at a pane (SPEC.md §27) by the traversal's own function: prim[n], bary[n, 2] = (u, v), dirs[n, 3] (unit)
+        -> a dict of tau[n, 3] (the channel transmittance), xi[n] (the hit's threshold), both float32, and bits[n] (uint32; bit c: channel c passes).  Zeros for
+        a triangle that is no thin-walled transmissive pane."""
+        pr = np.ascontiguousarray(prim, np.uint32).reshape(-1)
+        n = pr.shape[0]
+        ba = np.ascontiguousarray(bary, np.float32).reshape(-1, 2)
+        di = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        if ba.shape[0] != n or di.shape[0] != n:
+            raise Error(A.LPT_ERR_INVALID_ARG, "glass_shadow: one (u, v) and one direction per prim")
+        out = np.zeros((n, 8), np.float32)
+        _check(A.lib().lpt_scene_gpu_glass_shadow(self._dev.inner(), self._h, n, A.ptr(pr), A.ptr(ba), A.ptr(di), A.ptr(out)))
+        return {"tau": out[:, 0:3].copy(), "xi": out[:, 3].copy(), "bits": out[:, 4].copy().view(np.uint32)}
+
     def sample_emitter(self, points, rands):
         """The emitter sample the shading kernels run (SPEC.md §23) on the GPU: points[n, 3], rands[n, 4] = (ra, rb, r1, r2) -> a dict of prim[n],
         sampled[n] (bool), y[n, 3], wi[n, 3], dist[n], cl[n], p_a[n], E[n, 3]; zeros where there is no sample (prim is still the pick)."""
@@ -685,6 +699,17 @@ class Renderer:
     def get_emissive_sampling(self):
         f = C.c_int()
         _check(A.lib().lpt_renderer_get_emissive_sampling(self._h, C.byref(f)))
+        return bool(f.value)
+
+    def set_glass_shadows(self, flag):
+        """SPEC.md §27: the shadow rays of punctual lights pass thin-walled transmissive triangles with the pane's transmittance (off by default; off, every
+        frame is what it was).  Frames change with the call: `reset_accumulation` belongs after it"""
+        _check(A.lib().lpt_renderer_set_glass_shadows(self._h, 1 if flag else 0))
+
+    @property
+    def glass_shadows(self):
+        f = C.c_int()
+        _check(A.lib().lpt_renderer_get_glass_shadows(self._h, C.byref(f)))
         return bool(f.value)
 
     def set_lens(self, radius, focus_distance=1.0):

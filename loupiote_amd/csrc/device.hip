@@ -152,6 +152,7 @@ struct lpt_scene_gpu {
     DevMem tri_verts, materials, lights, texels, images, srgb_lut, pair_texels, pair_images;
     DevMem punctual;                // SPEC §19: lpt_punctual_light records (DScene::punctual)
     struct { DevMem tri, recs; } mat_tab[MAT_KINDS];   // SPEC §20, §21, §22, §24: per kind of material_tables.h the per-triangle table and the records (DScene::alpha_tri / alpha_recs, ...); empty where the scene does not use the kind
+    uint32_t n_thin_glass = 0;      // SPEC §27: baked triangles whose material is transmissive and thin-walled (derived with the tables: upload, rebuild, instance update)
     DevMem emit_tab;                // SPEC §23: the emitter distribution's entries (DScene::emit_tab); empty without a distribution
     TexturePairs pairs;
     lpt_accel_stats stats{};
@@ -235,6 +236,7 @@ struct lpt_renderer {
     int mode = LPT_BLIT_PATHTRACE;
     // build-only knobs
     uint32_t max_bounces = 3, user_seed = 0;
+    int glass_shadows = 0;     // SPEC §27 (lpt_renderer_set_glass_shadows): punctual lights' shadow rays pass thin-walled panes, while the bound scene has both
     int emissive_sampling = 0; // SPEC §23 (lpt_renderer_set_emissive_sampling): the ESAMP kernels while the bound scene has an emitter distribution
     int env_sampling = 0;      // SPEC §18 (lpt_renderer_set_env_sampling): the ENV kernels while the bound probe has a distribution
     float vfov = 0.78539816339744830962f;
@@ -872,15 +874,17 @@ static int commit_emit(lpt_scene_gpu *sg, const EmitTable &et) {
 
 // Everything the device keeps per triangle of the scene's materials: the four side tables and the emitter distribution.  Derived on the host (an edit is checked
 // before anything is baked), committed together — at upload, rebuild and every instance update.  The distribution goes last: commit_emit reads the committed n_emis.
-struct SceneTables { MaterialTable mat[MAT_KINDS]; EmitTable emit; };
+struct SceneTables { MaterialTable mat[MAT_KINDS]; EmitTable emit; uint32_t n_thin_glass = 0; };
 static int derive_tables(const lpt_scene_gpu *sg, const lpt_scene &scene, SceneTables &out) {
     TRY(derive_material_tables(scene, sg->inst_first, sg->inst_count, sg->d.n_tris, sg->pairs.image_resident, out.mat));
+    out.n_thin_glass = thin_glass_triangles(out.mat[MAT_TRANS]);   // SPEC §27
     return derive_emit(sg, scene, out.emit);
 }
 static int commit_tables(lpt_scene_gpu *sg, const SceneTables &t) {
     int st = LPT_OK;
     for (int k = 0; k < MAT_KINDS && st == LPT_OK; ++k) st = commit_table(sg, k, t.mat[k]);
     if (st == LPT_OK) st = commit_emit(sg, t.emit);
+    if (st == LPT_OK) sg->n_thin_glass = t.n_thin_glass;
     HIP_TRY(hipStreamSynchronize(sg->dev->stream));   // the host vectors are the caller's: waited for behind a failed upload too
     return st;
 }
@@ -1205,6 +1209,16 @@ int lpt_scene_gpu_shading_normal(lpt_device *dev, const lpt_scene_gpu *sg, uint3
         mapped_out[i] = rows[i].mapped;
     }
     return LPT_OK;
+}
+
+// SPEC §27: glass_shadow_eval — what a marked shadow ray along dirs[i] asks at the hit (prim, bary) —, once per element.  out[n] is the row {tau rgb, xi, pass bits, 0, 0, 0}
+int lpt_scene_gpu_glass_shadow(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, const float *dirs, float *out) {
+    if (!dev || !sg || (n && (!prim || !bary || !dirs || !out))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_glass_shadow: null");
+    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_glass_shadow: the scene belongs to another device");
+    TRY(check_prims("lpt_scene_gpu_glass_shadow", sg->d, prim, n));
+    return run_probe(dev, n, kBlock, {{prim, sizeof(uint32_t)}, {bary, sizeof(float[2])}, {dirs, kF3}}, {{out, sizeof(GlassRow)}}, [&](dim3 grid, const DevMem *d) {
+        hipLaunchKernelGGL(k_glass_shadow, grid, dim3(kBlock), 0, dev->stream, sg->d, as<const uint32_t>(d[0]), as<const float>(d[1]), as<const float>(d[2]), n, as<GlassRow>(d[3]));
+    });
 }
 
 // SPEC §9: what a hit reads from its textures (shade_hit's dispatch over texture_lookup / texture_lookup_pair / alpha_rejects), once per (prim, bary).  out[n] is the row
@@ -1665,6 +1679,17 @@ int lpt_renderer_get_emissive_sampling(const lpt_renderer *r, int *flag) {
     *flag = r->emissive_sampling;
     return LPT_OK;
 }
+int lpt_renderer_set_glass_shadows(lpt_renderer *r, int flag) {
+    if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_glass_shadows: null");
+    FLUSH_OR_RETURN(r);
+    r->glass_shadows = flag ? 1 : 0;
+    return LPT_OK;
+}
+int lpt_renderer_get_glass_shadows(const lpt_renderer *r, int *flag) {
+    if (!r || !flag) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_get_glass_shadows: null");
+    *flag = r->glass_shadows;
+    return LPT_OK;
+}
 int lpt_renderer_set_lens(lpt_renderer *r, float radius, float focus_distance) {
     if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_lens: null");
     if (!std::isfinite(radius) || radius < 0.0f) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_lens: the radius must be finite and >= 0");
@@ -1930,7 +1955,7 @@ template <class F, class... Rest> static void with_flags(F &&f, bool flag, Rest.
     else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
-// k_trace<STATS, PIPE, TAIL, MASK>: the eight instantiations that exist, by name (launch_plan.h picks one)
+// k_trace<STATS, PIPE, TAIL, MASK>: the eight instantiations that exist, by name, and k_trace_glass<STATS> (SPEC §27) behind them (launch_plan.h picks one)
 static void launch_k_trace(TraceVariant v, uint32_t blocks, size_t lds, hipStream_t s, const TraceKernargs &ka) {
     const dim3 grid(blocks), block(kTraceBlock);
     switch (v) {
@@ -1942,6 +1967,8 @@ static void launch_k_trace(TraceVariant v, uint32_t blocks, size_t lds, hipStrea
     case TraceVariant::PipeTail:  hipLaunchKernelGGL((k_trace<false, true, true>), grid, block, lds, s, ka); break;
     case TraceVariant::Mask:      hipLaunchKernelGGL((k_trace<false, false, false, true>), grid, block, lds, s, ka); break;
     case TraceVariant::StatsMask: hipLaunchKernelGGL((k_trace<true, false, false, true>), grid, block, lds, s, ka); break;
+    case TraceVariant::Glass:      hipLaunchKernelGGL((k_trace_glass<false>), grid, block, lds, s, ka); break;
+    case TraceVariant::StatsGlass: hipLaunchKernelGGL((k_trace_glass<true>), grid, block, lds, s, ka); break;
     }
 }
 
@@ -2097,7 +2124,7 @@ static int wavefront_prepare(lpt_renderer *r, const lpt_renderer::Pending &b, co
     WavefrontFacts &f = L.f;
     f.n_rays = n_rays; f.n_slots = p.n_slots; f.slot0 = p.slot0; f.n_samples = n_samples; f.cus = (uint32_t)r->dev->compute_units;
     f.solo = piece.solo; f.stats = r->stats; f.denoise = denoise; f.env = env;
-    f.masked = sc.n_alpha != 0u; f.trans = sc.n_trans != 0u; f.emis = sc.n_emis != 0u; f.nmap = sc.n_nmap != 0u; f.lens = r->lens_r > 0.0f; f.punct = sc.n_punctual != 0u; f.max_depth = r->sg->stats.max_depth; f.stack_entries = sc.stack_entries;
+    f.masked = sc.n_alpha != 0u; f.trans = sc.n_trans != 0u; f.emis = sc.n_emis != 0u; f.nmap = sc.n_nmap != 0u; f.lens = r->lens_r > 0.0f; f.punct = sc.n_punctual != 0u; f.glass_shadow = r->glass_shadows && f.punct && r->sg->n_thin_glass != 0u; f.max_depth = r->sg->stats.max_depth; f.stack_entries = sc.stack_entries;
     f.pixel_rad = 2.0f * th / (float)std::max(r->h, 1u); f.dense = (r->w % r->tile_w == 0u) && (r->h % r->tile_h == 0u); f.block8 = p.block8 != 0u;
     f.lim = KernelLimits{kBlock, kTraceBlock, kTailMax, kCoopWavesPerCu, kPacketBlocksPerCu, kPacketMaxPixelRad};
     L.tune = r->tune;

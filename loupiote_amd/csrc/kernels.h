@@ -592,9 +592,81 @@ __device__ __forceinline__ bool alpha_rejects(const DScene &sc, const uint32_t p
     return !(a >= rec.x);
 }
 
+// SPEC §27: which colour channels of a punctual light's shadow ray pass the candidate hit (prim, u, v) on their way along the unit direction d?  Bit c (0 red, 1 green,
+// 2 blue) is set iff the triangle is a thin-walled transmissive pane and its straight-through transmittance tau_c = (pt (1 - Fr)) base_c beats the threshold xi hashed
+// from the hit's own (prim, u, v): 0 for an opaque triangle, a solid transmissive one, a degenerate one.  pt and base are §21's event pick at that point — the record's
+// material, shade_hit's interpolation and texture dispatch, the sRGB table read from memory (the traversal stages none in LDS) —, Fr is §21's Fresnel on the GEOMETRIC
+// normal.  A pure function of (prim, u, v, d) and scene data, like alpha_rejects, and called where it is: behind an accepted Woop test, behind the rare divergent branch
+// "the ray is marked and the triangle is in the transmission table", with the node rows and the Woop rows dead.  The probe hook (k_glass_shadow) returns all of it.
+struct GlassShadow { f3 tau; float xi; uint32_t bits; };
+__device__ __forceinline__ float4 texture_lookup(const DScene &sc, const float *lut, uint32_t image, float u, float v, bool srgb);
+__device__ __forceinline__ void texture_lookup_pair(const DScene &sc, const float *lut, uint32_t offset, uint32_t wh, float u, float v, f3 &albedo, float &mra_g, float &mra_b);
+__device__ __forceinline__ GlassShadow glass_shadow_eval(const DScene &sc, const uint32_t prim, const float hu, const float hv, const f3 d) {
+    GlassShadow g;
+    g.tau = mk3(0.0f, 0.0f, 0.0f); g.xi = 0.0f; g.bits = 0u;
+    const uint32_t te = sc.trans_tri[prim];
+    if (te == 0u) return g;                       // opaque: an occluder, as ever
+    const float4 tr = sc.trans_recs[te - 1u];     // transmission, ior, thin
+    if (tr.z == 0.0f) return g;                   // solid glass refracts: no straight way through (a caustic, out of reach of a shadow ray)
+    // the salt keeps xi apart from §26's on a material that is both blended and transmissive
+    const uint32_t h = pcg_hash(pcg_hash(pcg_hash(prim ^ 0x9E3779B9u) ^ __float_as_uint(hu)) ^ __float_as_uint(hv));
+    g.xi = (float)(h >> 8) * 5.9604644775390625e-8f;
+    const float4 *tv = sc.tri_verts + kTriRec * (size_t)prim;
+    const float4 P0 = tv[0], N0 = tv[1], P1 = tv[2], N1 = tv[3], P2 = tv[4], N2 = tv[5];
+    const float4 mc = tv[6], mp = tv[7];
+    const f3 p0 = mk3(P0.x, P0.y, P0.z), p1 = mk3(P1.x, P1.y, P1.z), p2 = mk3(P2.x, P2.y, P2.z);
+    const f3 Ng = cross(p1 - p0, p2 - p0);
+    const float l2 = dot(Ng, Ng);
+    if (!(l2 > 0.0f)) return g;                   // degenerate: §12 shades nothing there, and nothing passes
+    const float bw = (1.0f - hu) - hv;
+    const float tu = (P0.w * bw + P1.w * hu) + P2.w * hv;
+    const float tvv = (N0.w * bw + N1.w * hu) + N2.w * hv;
+    f3 base = mk3(mc.x, mc.y, mc.z);
+    float metal = mp.y;
+    const uint32_t atex = __float_as_uint(mp.z), mtex = __float_as_uint(mp.w);
+    if ((atex >> 30) == 1u) {   // kPairedBit set, not LPT_INVALID_INDEX (shade_hit's dispatch)
+        f3 alb;
+        float mg, mb;
+        texture_lookup_pair(sc, sc.srgb_lut, atex & ~kPairedBit, mtex, tu, tvv, alb, mg, mb);
+        base.x *= alb.x; base.y *= alb.y; base.z *= alb.z;
+        metal *= mb;
+    } else {
+        if (atex < sc.n_images) {
+            const float4 tex = texture_lookup(sc, sc.srgb_lut, atex, tu, tvv, true);
+            base.x *= tex.x; base.y *= tex.y; base.z *= tex.z;
+        }
+        if (mtex < sc.n_images) {
+            const float4 tex = texture_lookup(sc, sc.srgb_lut, mtex, tu, tvv, false);
+            metal *= tex.z;
+        }
+    }
+    const float pt = tr.x * (1.0f - clampf(metal, 0.0f, 1.0f));
+    const float c = min2(fabsf(dot(d, Ng)) * (1.0f / sqrtf(l2)), 1.0f);
+    const float eta = 1.0f / tr.y;
+    const float s2 = (eta * eta) * max2(0.0f, 1.0f - c * c);
+    float Fr = 1.0f;
+    if (!(s2 >= 1.0f)) {
+        const float ct = sqrtf(1.0f - s2);
+        const float rs = (eta * c - ct) / (eta * c + ct);
+        const float rp = (c - eta * ct) / (c + eta * ct);
+        Fr = 0.5f * (rs * rs + rp * rp);
+    }
+    const float k = pt * (1.0f - Fr);
+    g.tau = mk3(k * base.x, k * base.y, k * base.z);
+    g.bits = (g.tau.x > g.xi ? 1u : 0u) | (g.tau.y > g.xi ? 2u : 0u) | (g.tau.z > g.xi ? 4u : 0u);   // a NaN tau does not pass
+    return g;
+}
+__device__ __forceinline__ uint32_t glass_shadow_mask(const DScene &sc, const uint32_t prim, const float hu, const float hv, const f3 d) {
+    return glass_shadow_eval(sc, prim, hu, hv, d).bits;
+}
+// an any-hit ray's unused best.v holds the ray's §27 state: bit 3 = the ray is a punctual light's (it may pass panes), bits 0..2 = the channels still alive
+constexpr uint32_t kGlassMarked = 8u, kGlassAlive = 7u;
+
 // returns true when the ray is finished (ANY: also as soon as something is hit; best.prim != ~0 then)
 // MASK (SPEC §20): a hit on a masked triangle whose alpha is below the cutoff is no hit — the only acceptance site that asks (device.hip launches a masked scene on this step only)
-template <bool STATS, bool MASK = false>
+// GLASS (SPEC §27; with MASK, which then asks only while the scene has an alpha table): a marked any-hit ray ANDs its alive channels with the pass bits of what it hits and
+// goes on while one is left
+template <bool STATS, bool MASK = false, bool GLASS = false>
 __device__ __forceinline__ bool ray_step_any(const DScene &sc, RayState &rs, uint2 *stack, const bool ANY, uint32_t &n_nodes, uint32_t &n_tris, const uint8_t *lut = nullptr) {
     if (rs.tg.y == 0u) {
         if (!(rs.ng.y & 0xFF000000u)) {
@@ -614,7 +686,14 @@ __device__ __forceinline__ bool ray_step_any(const DScene &sc, RayState &rs, uin
         float t, u, v;
         if (ray_triangle(r0, r1, r2, rs.o, rs.d, rs.best.t, t, u, v)) {
             const uint32_t prim = sc.leaf_prim[ti];
-            if (MASK && alpha_rejects(sc, prim, u, v)) return false;   // as if §7 had rejected the triangle
+            if (MASK && (!GLASS || sc.n_alpha != 0u) && alpha_rejects(sc, prim, u, v)) return false;   // as if §7 had rejected the triangle
+            if (GLASS && ANY) {
+                const uint32_t gs = __float_as_uint(rs.best.v);
+                if (gs & kGlassMarked) {
+                    const uint32_t alive = gs & glass_shadow_mask(sc, prim, u, v, rs.d);   // AND: exact, commutative, idempotent — the order and the number of the tests do not matter
+                    if (alive) { rs.best.v = __uint_as_float(kGlassMarked | alive); return false; }   // the pane is passed by the channels left
+                }
+            }
             if (t < rs.best.t || prim < rs.best.prim) { rs.best.t = t; rs.best.u = u; rs.best.v = v; rs.best.prim = prim; }
             // the occluder's leaf slot, for the occluder-cache probe of the stats kernels (an any-hit ray's v is not read).  Round 5: only ray_step_pipe did this,
             // so `--opt pipe_rays=0` with stats on fed the probe a barycentric's bit pattern as a leaf slot: an out-of-bounds read (a GPU memory fault at bench size)
@@ -1009,9 +1088,13 @@ __device__ __forceinline__ TraceKernargsPtr trace_kernargs() {
 // TAIL: the variant whose waves finish their last rays cooperatively (tail_walk); kept to the 6 waves per SIMD of the one-round-trip step (without the attribute the
 // compiler takes the extra code as a licence for 90-100 VGPRs in the loop).  The other variants are compiled as before.
 // MASK (SPEC §20): the launches of a scene with alpha-masked materials — the plain per-lane step only (ray_step_any asks alpha_rejects), no tail, no step budget
-template <bool STATS, bool PIPE = false, bool TAIL = false, bool MASK = false>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(TAIL ? 6 : (PIPE && !STATS ? 7 : 1)))) void k_trace(const TraceKernargs a) {
+// GLASS (SPEC §27): the launches of a wavefront whose punctual lights' shadow rays pass thin panes — the MASK step again, which is the one that asks glass_shadow_mask; a shadow
+// ray's mark is read from its contribution's fourth word at the refill, its state rides in best.v, and the deposit adds the channels that are still alive.
+// The body is shared: k_trace<S, P, T, M> (GLASS = false: the kernels of every frame before §27, under their names) and k_trace_glass<S> are its two wrappers.
+template <bool STATS, bool PIPE, bool TAIL, bool MASK, bool GLASS>
+__device__ __forceinline__ void trace_body(const TraceKernargs &a) {
     static_assert(!MASK || (!PIPE && !TAIL), "a masked scene traces on the two-round-trip step: the only acceptance site that evaluates SPEC §20");
+    static_assert(!GLASS || MASK, "SPEC §27 is asked on the step that asks §20 / §26");
     const DScene &sc = a.sc;
     FrameCounters *const ctr = a.ctr;      // (the prologue and the stats epilogue; the loop re-reads it where it needs it)
     const int cb = a.cb, sb = a.sb, refill = a.refill;
@@ -1092,7 +1175,12 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(TAI
                         const uint32_t slot = __float_as_uint(rs.best.u);   // the pixel slot rides in the unused `u` of an any-hit ray
                         const float4 c = sq.c[ray];
                         float4 L = Lsum[slot];
-                        L.x = L.x + c.x; L.y = L.y + c.y; L.z = L.z + c.z;
+                        if (GLASS) {   // SPEC §27: a dead channel gets no add at all (an unmarked ray keeps all three)
+                            const uint32_t alive = __float_as_uint(rs.best.v);
+                            if (alive & 1u) L.x = L.x + c.x;
+                            if (alive & 2u) L.y = L.y + c.y;
+                            if (alive & 4u) L.z = L.z + c.z;
+                        } else { L.x = L.x + c.x; L.y = L.y + c.y; L.z = L.z + c.z; }
                         Lsum[slot] = L;
                     }
                 } else {
@@ -1115,6 +1203,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(TAI
                     ray_begin(sc, rs, mk3(o4.x, o4.y, o4.z), mk3(d4.x, d4.y, d4.z), use_s ? o4.w : LPT_T_INF);
                     my_steps = 0;
                     if (use_s) rs.best.u = d4.w;   // kept for the deposit; a hit overwrites it, and then nothing is deposited
+                    if (GLASS && use_s) rs.best.v = __uint_as_float(sq.c[idx].w != 0.0f ? (kGlassMarked | kGlassAlive) : kGlassAlive);   // SPEC §27: the punctual branch marks its ray (shade_hit)
                     ray = idx;
                     shadow = use_s;
                     active = true;
@@ -1135,7 +1224,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(TAI
             w_node += (uint32_t)__popcll(__ballot(PIPE ? active && (rs.tg2.y == 0u) && ((rs.ng.y & 0xFF000000u) != 0u || rs.sp != 0) : active && (rs.tg.y == 0u)));
         }
         if ((STATS || budget) && active) my_steps++;
-        if (active && (PIPE ? ray_step_pipe<STATS, PLACE>(sc, rs, stack, shadow, dn, dt, lut) : ray_step_any<STATS, MASK>(sc, rs, stack, shadow, dn, dt, lut))) {
+        if (active && (PIPE ? ray_step_pipe<STATS, PLACE>(sc, rs, stack, shadow, dn, dt, lut) : ray_step_any<STATS, MASK, GLASS>(sc, rs, stack, shadow, dn, dt, lut))) {
             active = false;
             finished = true;
         }
@@ -1178,6 +1267,15 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(TAI
             atomicAdd(&ctr->tri_lanes, (unsigned long long)w_tri);
         }
     }
+}
+template <bool STATS, bool PIPE = false, bool TAIL = false, bool MASK = false>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(TAIL ? 6 : (PIPE && !STATS ? 7 : 1)))) void k_trace(const TraceKernargs a) {
+    trace_body<STATS, PIPE, TAIL, MASK, false>(a);
+}
+// SPEC §27: a name of its own, so that k_trace keeps its four template arguments (its instantiations are found by name)
+template <bool STATS>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(1))) void k_trace_glass(const TraceKernargs a) {
+    trace_body<STATS, false, false, true, true>(a);
 }
 
 // The stragglers of a traversal launch (k_trace with a step budget) — or every ray of a tiny wavefront —, each traced from the root by a WHOLE WAVE (coop_walk
@@ -2053,7 +2151,7 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DEnv &ev, cons
                                 out.want_shadow = true;
                                 out.so4 = make_float4(Po.x, Po.y, Po.z, dist < LPT_T_INF ? dist * 0.999f : LPT_T_INF);
                                 out.sd4 = make_float4(wi.x, wi.y, wi.z, d4.w);
-                                out.sc4 = make_float4(contrib.x, contrib.y, contrib.z, 0.f);
+                                out.sc4 = make_float4(contrib.x, contrib.y, contrib.z, 1.0f);   // SPEC §27's mark: a delta light's ray may pass thin panes (read by k_trace_glass alone)
                             }
                         }
                     }

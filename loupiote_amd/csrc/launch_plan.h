@@ -49,14 +49,15 @@ struct WavefrontFacts {
     bool emis = false;                // SPEC §22: an emissive material is in use
     bool nmap = false;                // SPEC §24: a normal-mapped material is in use
     bool lens = false;                // SPEC §25: the renderer's lens is open (R > 0): every primary ray has an origin of its own
+    bool glass_shadow = false;        // SPEC §27: the renderer's switch is on, the scene has punctual lights and a thin-walled transmissive triangle
     uint32_t max_depth = 0, stack_entries = 0;   // the tree's depth / per-lane stack capacity
     float pixel_rad = 0.0f;           // angle per pixel (2 tan(vfov / 2) / height)
     bool dense = false, block8 = false;   // whole tiles only / 8x8-pixel blocks inside the tiles
     KernelLimits lim{};
 };
 
-// the k_trace instantiations that exist: (STATS, PIPE, TAIL, MASK) = 0000 0100 1000 1100 0010 0110 0001 1001
-enum class TraceVariant : uint8_t { Lane, Pipe, Stats, StatsPipe, Tail, PipeTail, Mask, StatsMask };
+// the k_trace instantiations that exist: (STATS, PIPE, TAIL, MASK) = 0000 0100 1000 1100 0010 0110 0001 1001; behind them k_trace_glass<STATS> (SPEC §27)
+enum class TraceVariant : uint8_t { Lane, Pipe, Stats, StatsPipe, Tail, PipeTail, Mask, StatsMask, Glass, StatsGlass };
 
 struct LaunchPlan {
     TraceVariant variant = TraceVariant::Lane;
@@ -75,6 +76,9 @@ struct LaunchPlan {
 //   -------------------------------------+-----------------------------------------------------------------+-----------
 //   masked (alpha-masked materials)      | pipe, packet, tail, budget, occluder probe, coop-all, path:     | SPEC §20
 //                                        | k_trace<STATS, false, false, MASK> alone asks the mask          |
+//   glass_shadow (punctual shadow rays   | what masked excludes — pipe, packet, tail, budget, occluder      | SPEC §27
+//   pass thin panes)                     | probe, coop-all, path —: k_trace_glass<STATS> alone asks the    |
+//                                        | pane (and §20's mask, where the scene has one)                  |
 //   stats                                | tail, budget, coop-all (a ray dropped at the budget would be    | DESIGN §5.5
 //                                        | missing from the histogram and counted twice by the re-trace)   |
 //   trans (a transmissive material used) | path (k_path's instantiations do not double); k_shade<.., TRANS>| SPEC §21
@@ -92,11 +96,12 @@ inline LaunchPlan plan_wavefront(const LaunchTuning &t, const WavefrontFacts &f)
     const KernelLimits &k = f.lim;
     const uint32_t n_rays = f.n_rays, cus = f.cus;
     LaunchPlan pl;
+    const bool plain = f.masked || f.glass_shadow;   // the plain per-lane step alone: the acceptance site that asks SPEC §20 / §26 / §27
     pl.stream_blocks = std::min<uint32_t>(div_up(n_rays, k.kBlock), cus * 8u);
     pl.shade_blocks = std::min<uint32_t>(div_up(n_rays, k.kBlock), cus * (t.shade_blocks_per_cu ? t.shade_blocks_per_cu : (f.solo ? 4u : 3u)));
     // the one-round-trip step (kernels.h ray_step_pipe): 72 VGPRs (round 6; 78 before), 6 waves per SIMD used of the 7 that fit, ~3 % more nodes and ~12 % more triangles fetched per ray —
     // and still 1 % less time per frame at 8 M rays, 2 % for a 1 M-ray tile shard (profiles/r03_experiments_ab.txt); LPT_EXP_PIPE_RAYS 0 selects the two-round-trip step
-    pl.pipe = !f.masked && n_rays <= t.pipe_rays;
+    pl.pipe = !plain && n_rays <= t.pipe_rays;
     // persistent waves: about 2.5 primary rays per lane, between 8 waves per CU and all that fit (24 = 6 per SIMD with the one-round-trip step — 28 measured no faster, round 6 —, 32 with the other).  A 1/8
     // tile shard (1 M rays per launch) is best at 24 either way (round 3, span form, two-round-trip step: 8 / 12 / 16 / 24 / 32 waves per CU -> 4.41 / 3.89 / 3.62 / 3.51 / 3.54 ms per frame)
     const uint32_t waves = t.trace_waves_per_cu ? cus * t.trace_waves_per_cu : std::min(std::max(n_rays / 160u, cus * 8u), cus * (pl.pipe ? 24u : 32u));
@@ -108,7 +113,7 @@ inline LaunchPlan plan_wavefront(const LaunchTuning &t, const WavefrontFacts &f)
     // for rays that need 14.9 each, and the walk runs at 11.5 Grays/s against 6.2 per ray; at 240x135 the same patch spans eight times the
     // angle, the walk visits several times the nodes, and the packet launch is a third of the frame (0.43 of 1.37 ms; 0.39 ms at 480x270,
     // where the per-ray launch needs 0.13).  LPT_OPT_PACKET_PRIMARY 2 (default): packets up to 1.8 mrad per pixel; 1: always; 0: never.
-    pl.packet = !f.masked && !f.lens && (t.packet_primary == 1u || (t.packet_primary == 2u && f.pixel_rad <= k.kPacketMaxPixelRad));
+    pl.packet = !plain && !f.lens && (t.packet_primary == 1u || (t.packet_primary == 2u && f.pixel_rad <= k.kPacketMaxPixelRad));
     if (pl.packet) {
         pl.packet_blocks = std::min(div_up(n_rays, 64u), cus * k.kPacketBlocksPerCu);
         pl.packet_lds = (48u + 7u * f.max_depth + 8u) * (uint32_t)sizeof(uint32_t);
@@ -116,24 +121,25 @@ inline LaunchPlan plan_wavefront(const LaunchTuning &t, const WavefrontFacts &f)
         // (queue index = sample * slots + slot), 8x8 pixel blocks inside the tiles, whole blocks, a multiple of four samples
         pl.quad_slots = (t.packet_quads && f.dense && f.block8 && f.n_slots % 64u == 0u && f.slot0 % 64u == 0u && f.n_samples % 4u == 0u) ? f.n_slots : 0u;
     }
-    pl.occ_probe = !f.masked && f.stats;   // the occluder-cache probe rides with the stats kernels only (kernels.h OccProbe)
+    pl.occ_probe = !plain && f.stats;   // the occluder-cache probe rides with the stats kernels only (kernels.h OccProbe)
     // the step budget pays where nothing else fills the tail of a launch: a submission that is ONE wavefront (a tile shard, a small frame).  The
     // pieces of a cut batch overlap on the renderer's lanes and hide each other's tails: 1/2 shard as two wavefronts 6.84 ms without, 6.93 with it
     // (not with the stats kernels: a ray dropped at the budget would be missing from the steps-per-ray histogram and its partial node / triangle counts would be
     // counted again by the cooperative kernel's full re-trace — ADVICE r04)
-    const bool tail_launch = !f.masked && !f.stats && (f.solo || t.budget_split) && n_rays <= t.budget_rays;
+    const bool tail_launch = !plain && !f.stats && (f.solo || t.budget_split) && n_rays <= t.budget_rays;
     // ... the tail finished in place (tail_walk) comes first where it is on: nothing is dropped then, so there is nothing to re-trace
     pl.tail = tail_launch ? std::min(std::min(t.tail_lanes, k.kTailMax), (uint32_t)std::max(t.refill, 0)) : 0u;
     pl.budget = (tail_launch && !pl.tail && t.step_budget) ? t.step_budget : 0u;
     // a TINY wavefront (fewer rays than the chip has wave slots): the per-bounce launches with EVERY ray traced by a whole wave (k_trace_coop over the queues) — a lane per
     // ray leaves the chip empty and the frame is one chain of dependent steps (64x36, 4 spp: k_path 0.72 ms per frame, the per-lane launches 0.83, this 0.39)
-    pl.coop_all = !f.masked && !f.stats && t.coop_rays && n_rays <= t.coop_rays;
+    pl.coop_all = !plain && !f.stats && t.coop_rays && n_rays <= t.coop_rays;
     // k_trace_coop's grid: a wave per ray of both queues, or a wave per straggler of a budgeted launch (most waves of that grid find none and leave at once)
     pl.coop_blocks = pl.coop_all ? std::min(2u * n_rays, cus * k.kCoopWavesPerCu) : (pl.budget ? cus * k.kCoopWavesPerCu : 0u);
     // A small wavefront (the tile shard of a multi-GPU frame): every bounce behind the primary hits in ONE persistent launch (k_path); the primary hits are there, whichever kernel found them
-    pl.path = !f.masked && !f.trans && !f.emis && !f.nmap && !f.lens && t.path_rays && n_rays <= t.path_rays && !pl.coop_all;
+    pl.path = !plain && !f.trans && !f.emis && !f.nmap && !f.lens && t.path_rays && n_rays <= t.path_rays && !pl.coop_all;
     if (pl.path) pl.path_blocks = std::min<uint32_t>(div_up(n_rays, k.kTraceBlock), std::max(8u, (cus * t.path_waves_per_cu) & ~7u));
-    pl.variant = f.masked ? (f.stats ? TraceVariant::StatsMask : TraceVariant::Mask)
+    pl.variant = f.glass_shadow ? (f.stats ? TraceVariant::StatsGlass : TraceVariant::Glass)
+               : f.masked ? (f.stats ? TraceVariant::StatsMask : TraceVariant::Mask)
                : pl.tail  ? (pl.pipe ? TraceVariant::PipeTail : TraceVariant::Tail)
                : f.stats  ? (pl.pipe ? TraceVariant::StatsPipe : TraceVariant::Stats)
                           : (pl.pipe ? TraceVariant::Pipe : TraceVariant::Lane);

@@ -91,6 +91,14 @@ static inline int derive_material_tables(const lpt_scene &scene, const std::vect
     return LPT_OK;
 }
 
+// SPEC §27: how many baked triangles are thin-walled transmissive panes, from the transmission table as derived above (its record's third float is `thin`)
+static inline uint32_t thin_glass_triangles(const MaterialTable &trans) {
+    uint32_t n = 0;
+    for (uint32_t e : trans.tri)
+        if (e != 0u && trans.recs[e - 1u].z != 0.0f) n++;
+    return n;
+}
+
 // Which images the tiled atlas holds on their own, given which materials' (albedo, mra) textures were stored as a pair: an image that only ever appears as half of
 // a pair is not stored a second time.  An image no material references is kept (a later material edit may start to sample it), and so is every image a side-table
 // record names, whatever pair it is also half of: the alpha lookup of the traversal, shade_hit<.., EMIS> and normal_map read the plain tiled image.

@@ -26,6 +26,9 @@ struct BsdfEval { float pspec, f[3], pdf; };
 struct BsdfSampled { float L_s[3], weight[3], pdf_s; };
 struct BsdfRowOut { BsdfEval eval; uint32_t ok; BsdfSampled sampled; };
 struct BsdfAbiOut { BsdfEval eval; BsdfSampled sampled; };   // host only: the ABI's out[n][12], the row without its `ok`
+// lpt_scene_gpu_glass_shadow, one per element, and the ABI's out[n][8] as it stands: glass_shadow_eval's channel transmittance, threshold and pass bits (SPEC §27)
+struct GlassRow { float tau[3], xi; uint32_t bits, pad[3]; };
+static_assert(sizeof(GlassRow) == 8 * 4, "probe rows: the word counts of the C ABI's callers");
 static_assert(sizeof(EmitterRow) == 16 * 4 && sizeof(NormalRow) == 4 * 4 && sizeof(TextureRow) == 16 * 4, "probe rows: the word counts of the C ABI's callers");
 static_assert(sizeof(InterfaceRowIn) == 16 * 4 && sizeof(InterfaceRowOut) == 7 * 4, "probe rows: the word counts of the C ABI's callers");
 static_assert(sizeof(BsdfRowIn) == 20 * 4 && sizeof(BsdfRowOut) == 13 * 4 && sizeof(BsdfAbiOut) == 12 * 4, "probe rows: the word counts of the C ABI's callers");
@@ -213,6 +216,19 @@ __global__ __launch_bounds__(kBlock) void k_sample_textures(DScene sc, const uin
     put3(row.emissive, emi); put3(row.normal, nrm);
     row.rejected = sc.n_alpha != 0u && alpha_rejects(sc, prim, hu, hv) ? 1u : 0u;
     row.uv[0] = tu; row.uv[1] = tvv;
+    out[i] = row;
+}
+
+// lpt_scene_gpu_glass_shadow: glass_shadow_eval, the function the traversal's GLASS step runs, one (prim, bary, direction) per thread; a scene without a transmission
+// table has no pane (zeros)
+__global__ __launch_bounds__(kBlock) void k_glass_shadow(DScene sc, const uint32_t *prims, const float *bary, const float *dirs, uint32_t n, GlassRow *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    GlassRow row{};
+    if (sc.n_trans != 0u) {
+        const GlassShadow g = glass_shadow_eval(sc, prims[i], bary[2u * (size_t)i], bary[2u * (size_t)i + 1u], get3(dirs + 3u * (size_t)i));
+        put3(row.tau, g.tau); row.xi = g.xi; row.bits = g.bits;
+    }
     out[i] = row;
 }
 
