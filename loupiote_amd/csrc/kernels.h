@@ -686,6 +686,7 @@ __device__ __forceinline__ bool ray_step_any(const DScene &sc, RayState &rs, uin
         float t, u, v;
         if (ray_triangle(r0, r1, r2, rs.o, rs.d, rs.best.t, t, u, v)) {
             const uint32_t prim = sc.leaf_prim[ti];
+            // (a candidate the mask or a pane turns away leaves through `return false`: should it have been the ray's last work, the top of the next step reports the end, as before)
             if (MASK && (!GLASS || sc.n_alpha != 0u) && alpha_rejects(sc, prim, u, v)) return false;   // as if §7 had rejected the triangle
             if (GLASS && ANY) {
                 const uint32_t gs = __float_as_uint(rs.best.v);
@@ -701,7 +702,8 @@ __device__ __forceinline__ bool ray_step_any(const DScene &sc, RayState &rs, uin
             if (ANY) return true;
         }
     }
-    return false;
+    // nothing left: the end is reported by the step that reaches it, not by the top of the next (round 10; ray_step_pipe)
+    return ((rs.ng.y >> 24) | (uint32_t)rs.sp | rs.tg.y) == 0u;
 }
 
 // The same step with ONE memory round trip instead of two: the triangle tested in a step is one that an EARLIER step found, so its
@@ -759,7 +761,9 @@ __device__ __forceinline__ bool ray_step_pipe(const DScene &sc, RayState &rs, ui
     if (visit) found = node_test(sc, rs, nr, lut);
     if (rs.tg.y == 0u) { rs.tg = rs.tg2; rs.tg2.y = 0u; }
     if (found.y != 0u) { if (rs.tg.y == 0u) rs.tg = found; else rs.tg2 = found; }
-    return false;
+    // THE END IS REPORTED BY THE STEP THAT USES UP THE LAST WORK (round 10), not by the top of the next one: a lane whose ray has nothing left would sit there, counted
+    // as live, for a whole wave step in which it fetches and tests nothing, and hold the refill back by that step.  The state is the one the top check would see.
+    return ((rs.ng.y >> 24) | (uint32_t)rs.sp | rs.tg.y) == 0u;   // no hit bit in the group in hand, nothing stacked, no triangle waiting (rs.tg2 only waits behind rs.tg)
 }
 
 template <bool ANY, bool STATS, bool MASK = false>
@@ -2521,6 +2525,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(LPT
             w_live += (uint32_t)__popcll(__ballot(phase == 1u));
             w_node += (uint32_t)__popcll(__ballot(phase == 1u && (rs.tg2.y == 0u) && ((rs.ng.y & 0xFF000000u) != 0u || rs.sp != 0)));
         }
+        const bool stepped_shadow = shadow;   // STATS: a ray's last step is a working one, and behind it the lane may already carry the path's next ray
         if (phase == 1u && ray_step_pipe<STATS>(sc, rs, stack, shadow, dn, dt)) {
             if (shadow) {
                 if (rs.best.prim == 0xFFFFFFFFu) { L.x = L.x + cs.x; L.y = L.y + cs.y; L.z = L.z + cs.z; }   // unoccluded: deposit the light sample
@@ -2539,7 +2544,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(LPT
         }
         if (STATS) {
             w_tri += (uint32_t)__popcll(__ballot(dt != 0u));
-            if (shadow) { s_nodes += dn; s_tris += dt; } else { n_nodes += dn; n_tris += dt; }
+            if (stepped_shadow) { s_nodes += dn; s_tris += dt; } else { n_nodes += dn; n_tris += dt; }
         }
     }
     __syncthreads();
