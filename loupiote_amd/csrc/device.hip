@@ -45,9 +45,40 @@ using namespace lptd;
         if (e__ != hipSuccess) return fail(LPT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e__)); \
     } while (0)
 
+// Owning handles: a unique_ptr that also reads as the raw handle it owns, so it goes to a launch or a HIP call as that handle does.  What an owner holds is
+// released when the owner goes or is assigned over; no release waits for work in flight on a stream (hipFree alone waits, for the whole device), so whoever
+// drops an owner has synchronised what still uses it.
+template <typename T, typename D> struct Owner : std::unique_ptr<T, D> {
+    operator T *() const { return this->get(); }
+};
+struct HipFree { void operator()(void *p) const { hipFree(p); } };
+struct HostFree { void operator()(void *p) const { hipHostFree(p); } };
+struct StreamDestroy { void operator()(hipStream_t s) const { hipStreamDestroy(s); } };
+struct EventDestroy { void operator()(hipEvent_t e) const { hipEventDestroy(e); } };
+// device memory of n elements: alloc() takes the new memory before it lets go of the old
+template <typename T> struct DevBuf : Owner<T, HipFree> {
+    int alloc(size_t n) {
+        void *p = nullptr;
+        HIP_TRY(hipMalloc(&p, sizeof(T) * n));
+        this->reset((T *)p);
+        return LPT_OK;
+    }
+};
+using DevMem = DevBuf<char>;   // untyped: alloc(bytes), read through as<T>()
+template <typename T> static inline T *as(const DevMem &m) { return (T *)m.get(); }
+struct Stream : Owner<std::remove_pointer_t<hipStream_t>, StreamDestroy> {
+    int create() { hipStream_t s = nullptr; HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); reset(s); return LPT_OK; }
+};
+struct Event : Owner<std::remove_pointer_t<hipEvent_t>, EventDestroy> {
+    int create(unsigned flags = hipEventDisableTiming) { hipEvent_t e = nullptr; HIP_TRY(hipEventCreateWithFlags(&e, flags)); reset(e); return LPT_OK; }
+};
+template <typename T> using HostWord = Owner<T, HostFree>;   // page-locked host memory
+// a group of owners is released by assignment: what it held goes, member by member in declaration order, and its plain members are back at their defaults
+template <typename G> static inline void release(G &g) { g = G{}; }
+
 struct lpt_device {
     int ordinal = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
     int compute_units = 0;
     char name[128] = {0};
     std::vector<lpt_renderer *> renderers;   // live renderers of this device: scene / probe edits submit their recorded calls first
@@ -120,11 +151,6 @@ static const Rccl *rccl() {
         if (r__ != ncclSuccess) return fail(LPT_ERR_RCCL, "%s failed: %s", #expr, rccl() ? rccl()->GetErrorString(r__) : "?"); \
     } while (0)
 
-// device memory, freed when its handle goes (hipFree waits for the device)
-struct HipFree { void operator()(void *p) const { hipFree(p); } };
-using DevMem = std::unique_ptr<void, HipFree>;
-template <typename T> static inline T *as(const DevMem &m) { return (T *)m.get(); }
-
 // The wide BVH on the device: what a build makes and a rebuild swaps in whole.  Nodes are stored breadth first: level l = [level_start[l], level_start[l+1]).
 struct DevTree {
     DevMem nodes, woop, leaf_prim;
@@ -168,10 +194,10 @@ struct lpt_scene_gpu {
 struct lpt_probe {
     lpt_device *dev = nullptr;
     DProbe d{};
-    void *rgbe = nullptr;
+    DevMem rgbe;
     // SPEC §18: the sampling distribution, built on first use (probe_env) — a probe never sampled costs nothing for it
     int env_state = 0;         // 0: not built, 1: built (env), 2: the probe has none (black)
-    void *env_buf = nullptr;   // rows then cols, 16-byte entries
+    DevBuf<float4> env_buf;    // rows then cols, 16-byte entries
     DEnv env{};
 };
 
@@ -186,19 +212,24 @@ static const char *kStageLabel[ST_COUNT] = {"ray generation", "intersection", "s
 // overlaps the drain tails of call k — what several renderers do for several frames, for the unchanged caller that issues
 // its samples one raytrace() at a time.  Accumulation stays on the renderer's stream, in call order (the fp32 sums are
 // order-sensitive), so results do not depend on the number of lanes.
-struct Wavefront {
-    hipStream_t stream = nullptr;   // the lane's own stream; lane 0 (and a renderer with one lane) runs on the renderer's stream and has none
-    Queue q[2]{};
-    ShadowQueue sq{};
-    float4 *hits = nullptr, *Lsum = nullptr;
-    uint32_t *strag = nullptr;      // the stragglers of a traversal launch (k_trace's step budget -> k_trace_coop): ray index | shadow << 31
-    FrameCounters *ctr = nullptr;
-    size_t ray_cap = 0;             // rays (pixel slots x samples) the per-ray buffers can hold; 0 = not allocated yet
-    hipEvent_t done = nullptr;      // recorded on `stream` behind the lane's last traversal / shading launch
-    hipEvent_t consumed = nullptr;  // recorded on the renderer's stream behind the accumulation that read this lane's Lsum
+// Its resources are two groups (bases, so that a member reads wf.Lsum): each is made whole or not at all, and released by assignment (release()).
+struct LaneSync {                   // ensure_lane; lives as long as the renderer
+    Stream stream;                  // the lane's own stream; lane 0 (and a renderer with one lane) runs on the renderer's stream and has none
+    Event done;                     // recorded on `stream` behind the lane's last traversal / shading launch
+    Event consumed;                 // recorded on the renderer's stream behind the accumulation that read this lane's Lsum
     bool consumed_recorded = false;
-    std::vector<hipEvent_t> trav;   // LPT_EXP_LANE_PHASE: trav[t] recorded on the lane's stream behind traversal launch t (0: the primary rays) of the lane's wavefront
+    Event trav[kMaxBounces + 1];    // LPT_EXP_LANE_PHASE: trav[t] recorded on the lane's stream behind traversal launch t (0: the primary rays) of the lane's wavefront; created when a plan first asks for them
+    DevBuf<FrameCounters> ctr;
 };
+struct RayBuffers {                 // alloc_ray_buffers: one element per ray of a wavefront
+    struct { DevBuf<float4> o, d, t; } q_mem[2], sq_mem;   // Queue's o, d, T and ShadowQueue's o, d, c
+    DevBuf<float4> hits, Lsum;
+    DevBuf<uint32_t> strag;         // the stragglers of a traversal launch (k_trace's step budget -> k_trace_coop): ray index | shadow << 31
+    size_t ray_cap = 0;             // rays (pixel slots x samples) the buffers can hold; 0 = not allocated yet
+    Queue q[2]{};                   // what the kernels get of the queues, by value: bound by alloc_ray_buffers
+    ShadowQueue sq{};
+};
+struct Wavefront : LaneSync, RayBuffers {};   // the stream and events outlive the buffers that were used on them
 constexpr int kMaxLanes = 4;
 constexpr float kPacketMaxPixelRad = 1.8e-3f;    // bounce 0 as packets up to this angle per pixel (measured: 1.53 mrad, 960x540: packets 4.46 against 4.51 ms; 2.05 mrad, 720x405: 3.32 against 3.20)
 constexpr uint32_t kOccEntries = 1u << 18;       // occluder-cache probe: 1 MB, L2-resident
@@ -207,10 +238,40 @@ constexpr uint32_t kPacketBlocksPerCu = 128u;   // k_trace_packet's grid: one-wa
 constexpr uint32_t kCoopWavesPerCu = 32u;   // k_trace_coop's grid: a wave per straggler, most waves find none and leave (8 / 4 per CU: the same 2.90 ms per 1/8-shard frame, round 5)
 constexpr uint64_t kWavefrontRays = 1ull << 22;   // rays (pixel slots x samples) per wavefront an automatic submission aims at
 
-struct lpt_renderer {
-    lpt_device *dev = nullptr;
-    hipStream_t stream = nullptr;   // every renderer enqueues on its OWN stream, so two renderers pipeline
+// A renderer's resources that come and go with its size or mode are groups, as a lane's are.  The stream and the exchange's event are the first base: they go last.
+struct RendererSync {
+    Stream stream;                  // every renderer enqueues on its OWN stream, so two renderers pipeline
                                     // consecutive frames (and a frame's collective overlaps the next frame)
+    Event xevent;
+};
+struct FrameBuffers {               // alloc_frame_buffers; `frame` and `xstage` join on the first exchange (ensure_exchange_buffers)
+    uint32_t n_slots = 0;
+    DevBuf<float4> accum, scratch;
+    // frame exchange (lpt_renderer_exchange): `frame` = the presented whole frame on rank 0 (accum stays owned-only),
+    // `xstage` = packed owned tiles (this rank's; on rank 0 those of every rank, concatenated)
+    DevBuf<float4> frame, xstage;
+    size_t xstage_elems = 0;
+    bool presented = false;         // read_radiance / read_pixels / blit resolve from `frame` (set by an exchange, cleared by raytrace)
+    bool xevent_recorded = false;
+};
+// denoiser path (reference render/asvgf.rs ScreenResources :9-152): 2x ping-pong {radiance, gbuffer, moments,
+// history} + motion + radiance_temp; allocated on first use of a denoising BlitMode (ensure_denoiser), whole or not at all
+struct Denoiser {
+    DevBuf<uint4> den_gbuf[2];
+    DevBuf<float4> den_rad[2];
+    DevBuf<float2> den_mom[2];
+    DevBuf<uint32_t> den_hist[2];
+    DevBuf<float2> den_motion;
+    DevBuf<float4> den_temp;
+    DevBuf<float4> den_noisy;       // per-pixel sample radiance of the current frame (filter input; exchanged when sharded)
+    DevBuf<float4> den_nd;          // the current G-buffer's normal + depth, decoded once per frame for the a-trous passes
+    bool den_inputs_ready = false;
+    int den_cur = 1;                // current_frame_back starts true (asvgf.rs:233); start() flips it
+    bool has_denoiser() const { return (bool)den_temp; }   // any member tells
+};
+
+struct lpt_renderer : RendererSync, FrameBuffers, Denoiser {
+    lpt_device *dev = nullptr;
     Wavefront wf[kMaxLanes];
     int n_lanes = 2;                // lpt_renderer_set_lanes
     uint32_t lane_rr = 0;
@@ -246,48 +307,27 @@ struct lpt_renderer {
     ShardMap map{1u, 1u, {0u}};      // this rank's part of the ownership rule
     ShardTable h_table{};            // rank 0: the whole rule ...
     std::vector<uint32_t> h_offset;  // ... the staging offsets of the ranks (world + 1 entries, any world size) ...
-    ShardTable *d_table = nullptr;   // ... and the rule's copy in device memory for the unpack kernels; refreshed by alloc_frame_buffers
+    DevBuf<ShardTable> d_table;      // ... and the rule's copy in device memory for the unpack kernels; refreshed by alloc_frame_buffers
     bool use_noise = false, stats = false, timings = false;
     int sort_queues = 0;       // k_shade emits both ray queues ordered by direction octant within a block (lpt_renderer_set_sort_queues)
     uint32_t lane_phase = 1;   // the pieces of a cut batch against each other (LPT_EXP_LANE_PHASE): 0 free, 1 offset start, 2 alternating traversal (submission_plan.h: the rules and what they measured)
-    // device memory
-    uint32_t n_slots = 0;
-    float4 *accum = nullptr, *scratch = nullptr;
-    // frame exchange (lpt_renderer_exchange): `frame` = the presented whole frame on rank 0 (accum stays owned-only),
-    // `xstage` = packed owned tiles (this rank's; on rank 0 those of every rank, concatenated)
     lpt_comm *comm = nullptr;
-    float4 *frame = nullptr, *xstage = nullptr;
-    size_t xstage_elems = 0;
-    bool presented = false;   // read_radiance / read_pixels / blit resolve from `frame` (set by an exchange, cleared by raytrace)
-    hipEvent_t xevent = nullptr;
-    bool xevent_recorded = false;
-    Totals *totals = nullptr;
+    // device memory that lives as long as the renderer
+    DevBuf<Totals> totals;
     uint64_t split_rays = kSplitRays;   // LPT_EXP_SPLIT_RAYS
-    uint32_t *err_host = nullptr, *err_dev = nullptr;   // the device's error word: one page-locked host word the kernels write (a bounded wait that ran out), checked behind every blocking call
-    uint32_t *occ_table = nullptr;   // occluder-cache probe (stats only): kOccEntries leaf slots + 1, zero = empty; allocated by enable_stats
+    HostWord<uint32_t> err_host;   // the device's error word: one page-locked host word the kernels write (a bounded wait that ran out), checked behind every blocking call
+    DevBuf<uint32_t> occ_table;      // occluder-cache probe (stats only): kOccEntries leaf slots + 1, zero = empty; allocated by enable_stats
     float occ_cell = 0.25f;          // its grid cell (scene units); LPT_EXP_OCC_CELL_MILLI
-    void *default_probe = nullptr;
-    float *srgb_thr = nullptr;   // 256 floats: the linear value at which sRGB code i starts (k_tonemap, SPEC §13.2)
-    void *noise = nullptr;
+    DevMem default_probe;
+    DevBuf<float> srgb_thr;      // 256 floats: the linear value at which sRGB code i starts (k_tonemap, SPEC §13.2)
+    DevMem noise;
     uint32_t noise_w = 0, noise_h = 0;
-    // denoiser path (reference render/asvgf.rs ScreenResources :9-152): 2x ping-pong {radiance, gbuffer, moments,
-    // history} + motion + radiance_temp; allocated on first use of a denoising BlitMode
-    uint4 *den_gbuf[2]{};
-    float4 *den_rad[2]{};
-    float2 *den_mom[2]{};
-    uint32_t *den_hist[2]{};
-    float2 *den_motion = nullptr;
-    float4 *den_temp = nullptr;
-    float4 *den_noisy = nullptr;  // per-pixel sample radiance of the current frame (filter input; exchanged when sharded)
-    float4 *den_nd = nullptr;     // the current G-buffer's normal + depth, decoded once per frame for the a-trous passes
-    bool den_inputs_ready = false;
-    int den_cur = 1;              // current_frame_back starts true (asvgf.rs:233); start() flips it
     CamBasis prev_cam{};          // prev_model_to_screen (renderer.rs:201,319,542-546), identity at start
     // per-stage timing: a ring of event sets (one per raytrace() call) harvested lazily, so
     // timing a run never stalls the host on the frame it has just enqueued
     static constexpr int kRing = 8;
     static constexpr int kMaxEvents = 3 * kMaxBounces + 4;
-    hipEvent_t *ev_start = nullptr, *ev_stop = nullptr;  // kRing * kMaxEvents each
+    std::vector<Event> ev_start, ev_stop;  // kRing * kMaxEvents each, from the first enable_timings(1)
     int ev_stage[kRing][kMaxEvents]{};
     int ev_count[kRing]{};
     uint64_t ring_pos = 0;
@@ -331,13 +371,6 @@ static int check_device_error(lpt_renderer *r) {
 }
 static inline size_t stack_bytes(const DScene &sc) { return (size_t)sc.stack_entries * kTraceBlock * sizeof(uint2); }
 
-static int dev_alloc(DevMem &m, size_t bytes) {
-    void *p = nullptr;
-    HIP_TRY(hipMalloc(&p, bytes));
-    m.reset(p);
-    return LPT_OK;
-}
-
 // The one path of every per-element probe (probe_kernels.h; the entry points are under "per-element probes" below): n elements up, one launch, n answers back.  Each
 // input and output is a host array and its bytes per element; `launch(grid, d)` gets the grid of `block`-thread blocks that covers n and the device arrays, the inputs
 // first, each list in its order.  Everything runs on dev->stream and is waited for once at the end, so nothing depends on how the null stream orders against a
@@ -350,8 +383,8 @@ static int run_probe(lpt_device *dev, uint32_t n, uint32_t block, std::initializ
     HIP_TRY(hipSetDevice(dev->ordinal));
     std::vector<DevMem> d(ins.size() + outs.size());
     size_t k = 0;
-    for (const ProbeIn &b : ins) TRY(dev_alloc(d[k++], b.stride * n));
-    for (const ProbeOut &b : outs) TRY(dev_alloc(d[k++], b.stride * n));
+    for (const ProbeIn &b : ins) TRY(d[k++].alloc(b.stride * n));
+    for (const ProbeOut &b : outs) TRY(d[k++].alloc(b.stride * n));
     k = 0;
     for (const ProbeIn &b : ins) HIP_TRY(hipMemcpyAsync(d[k++].get(), b.host, b.stride * n, hipMemcpyHostToDevice, dev->stream));
     launch(dim3(div_up(n, block)), d.data());
@@ -377,7 +410,7 @@ static int check_prims(const char *who, const DScene &d, const uint32_t *prim, u
 
 template <typename T>
 static int upload(DevMem &dst, const std::vector<T> &src, hipStream_t s) {
-    TRY(dev_alloc(dst, sizeof(T) * std::max<size_t>(src.size(), 1u)));
+    TRY(dst.alloc(sizeof(T) * std::max<size_t>(src.size(), 1u)));
     if (!src.empty()) HIP_TRY(hipMemcpyAsync(dst.get(), src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice, s));
     return LPT_OK;
 }
@@ -390,7 +423,7 @@ static int scene_bounds_and_grid(lpt_scene_gpu *sg, uint32_t n, hipStream_t s, f
     int hb[6];
     const int init[6] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, (int)0x80000000, (int)0x80000000, (int)0x80000000};
     DevMem db;
-    TRY(dev_alloc(db, sizeof init));
+    TRY(db.alloc(sizeof init));
     HIP_TRY(hipMemcpyAsync(db.get(), init, sizeof init, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_lbvh_bounds, dim3(std::min<uint32_t>(div_up(n, 256u), 1024u)), dim3(256), 0, s, sg->d, n, as<int>(db));
     HIP_TRY(hipMemcpyAsync(hb, db.get(), sizeof hb, hipMemcpyDeviceToHost, s));
@@ -445,7 +478,7 @@ static int build_lbvh(lpt_scene_gpu *sg, uint32_t n, const void *woop_prim, hipS
     if (sg->arena_bytes < need) {
         sg->arena.reset();
         sg->arena_bytes = 0;
-        if (dev_alloc(sg->arena, need) != LPT_OK) return fail(LPT_ERR_HIP, "GPU BVH build: out of device memory (%zu bytes of scratch)", need);
+        if (sg->arena.alloc(need) != LPT_OK) return fail(LPT_ERR_HIP, "GPU BVH build: out of device memory (%zu bytes of scratch)", need);
         sg->arena_bytes = need;
     }
     size_t arena_used = 0;
@@ -514,14 +547,14 @@ static int build_lbvh(lpt_scene_gpu *sg, uint32_t n, const void *woop_prim, hipS
     t.n_nodes = level_first;
     t.max_depth = (uint32_t)t.level_start.size() - 1u;
     const size_t places = (size_t)kNodeTris * t.n_nodes;
-    TRY(dev_alloc(t.nodes, sizeof(Node8) * (size_t)t.n_nodes));
+    TRY(t.nodes.alloc(sizeof(Node8) * (size_t)t.n_nodes));
     HIP_TRY(hipMemcpyAsync(t.nodes.get(), nodes_big, sizeof(Node8) * (size_t)t.n_nodes, hipMemcpyDeviceToDevice, s));
-    TRY(dev_alloc(t.node_lo, sizeof(float4) * (size_t)t.n_nodes));
-    TRY(dev_alloc(t.node_hi, sizeof(float4) * (size_t)t.n_nodes));
-    TRY(dev_alloc(t.leaf_prim, sizeof(uint32_t) * places));
+    TRY(t.node_lo.alloc(sizeof(float4) * (size_t)t.n_nodes));
+    TRY(t.node_hi.alloc(sizeof(float4) * (size_t)t.n_nodes));
+    TRY(t.leaf_prim.alloc(sizeof(uint32_t) * places));
     HIP_TRY(hipMemcpyAsync(t.leaf_prim.get(), leaf_big, sizeof(uint32_t) * places, hipMemcpyDeviceToDevice, s));
     // Woop maps: prim order -> their places (holes stay zero)
-    TRY(dev_alloc(t.woop, sizeof(WoopTri) * places));
+    TRY(t.woop.alloc(sizeof(WoopTri) * places));
     HIP_TRY(hipMemsetAsync(t.woop.get(), 0, sizeof(WoopTri) * places, s));
     scatter_woop(t, woop_prim, 0u, n, s);
     DScene d = sg->d;   // the scene's triangles and grid, the new tree's leaves
@@ -755,8 +788,8 @@ int lpt_device_create(int hip_ordinal, lpt_device **out) {
     d->ordinal = hip_ordinal;
     d->compute_units = prop.multiProcessorCount;
     snprintf(d->name, sizeof d->name, "%s (%s)", prop.name, prop.gcnArchName);
-    hipError_t se = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-    if (se != hipSuccess) { delete d; return fail(LPT_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(se)); }
+    const int st = d->stream.create();
+    if (st != LPT_OK) { delete d; return st; }
     *out = d;
     return LPT_OK;
 }
@@ -765,8 +798,7 @@ int lpt_device_destroy(lpt_device *dev) {
     if (!dev) return LPT_OK;
     hipSetDevice(dev->ordinal);
     hipStreamSynchronize(dev->stream);
-    hipStreamDestroy(dev->stream);
-    delete dev;
+    delete dev;   // its stream with it
     return LPT_OK;
 }
 
@@ -808,7 +840,7 @@ static int upload_punctual(lpt_scene_gpu *sg, const lpt_scene &scene) {
     static_assert(sizeof(lpt_punctual_light) == 4 * sizeof(float4), "a punctual light is four float4 rows");
     const uint32_t n = (uint32_t)scene.punctual.size();
     hipStream_t s = sg->dev->stream;
-    if (n != sg->d.n_punctual || !sg->punctual) TRY(dev_alloc(sg->punctual, sizeof(lpt_punctual_light) * std::max<size_t>(n, 1u)));
+    if (n != sg->d.n_punctual || !sg->punctual) TRY(sg->punctual.alloc(sizeof(lpt_punctual_light) * std::max<size_t>(n, 1u)));
     if (n) HIP_TRY(hipMemcpyAsync(sg->punctual.get(), scene.punctual.data(), sizeof(lpt_punctual_light) * (size_t)n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));   // the host vector is the caller's
     sg->d.punctual = as<const float4>(sg->punctual);
@@ -928,7 +960,7 @@ int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags,
     sg->pairs = std::move(pairs);
     hipStream_t s = dev->stream;
     if (gpu_build) {
-        TRY(dev_alloc(sg->tri_verts, sizeof(TriRec) * (size_t)n_tris));   // written by k_bake_instance
+        TRY(sg->tri_verts.alloc(sizeof(TriRec) * (size_t)n_tris));   // written by k_bake_instance
     } else {   // the host-built tree; its boxes are filled by the first refit
         DevTree &t = sg->tree;
         t.n_nodes = (uint32_t)acc.nodes.size();
@@ -939,8 +971,8 @@ int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags,
         TRY(upload(t.woop, acc.woop, s));
         TRY(upload(t.leaf_prim, acc.leaf_prim, s));
         const size_t box_bytes = sizeof(float4) * std::max<size_t>(t.n_nodes, 1u);
-        TRY(dev_alloc(t.node_lo, box_bytes));
-        TRY(dev_alloc(t.node_hi, box_bytes));
+        TRY(t.node_lo.alloc(box_bytes));
+        TRY(t.node_hi.alloc(box_bytes));
         HIP_TRY(hipMemsetAsync(t.node_lo.get(), 0, box_bytes, s));
         HIP_TRY(hipMemsetAsync(t.node_hi.get(), 0, box_bytes, s));
         TRY(upload(sg->tri_verts, recs, s));
@@ -992,7 +1024,7 @@ int lpt_scene_upload_ex(lpt_device *dev, const lpt_scene *scene, uint32_t flags,
 
     if (gpu_build) {   // bake every instance on the device, then build the tree there
         DevMem woop_prim;
-        TRY(dev_alloc(woop_prim, sizeof(WoopTri) * (size_t)n_tris));
+        TRY(woop_prim.alloc(sizeof(WoopTri) * (size_t)n_tris));
         TRY(bake_instances(sg.get(), *scene, every_instance(*scene), woop_prim.get()));
         TRY(build_lbvh(sg.get(), n_tris, woop_prim.get(), s, sg->tree));
     }
@@ -1031,7 +1063,7 @@ int lpt_scene_gpu_update_instances(lpt_scene_gpu *sg, const lpt_scene *scene, ui
         // re-bake on the device (the object-space meshes are resident, only the transforms travel); a place-driven scatter then takes the new
         // Woop maps to every place a triangle has in the tree (a split triangle has several)
         DevMem woop_prim;
-        TRY(dev_alloc(woop_prim, sizeof(WoopTri) * (size_t)std::max(sg->stats.triangles, 1u)));
+        TRY(woop_prim.alloc(sizeof(WoopTri) * (size_t)std::max(sg->stats.triangles, 1u)));
         const int st = bake_instances(sg, *scene, changed, woop_prim.get());
         if (st == LPT_ERR_INVALID_ARG) return st;   // found before anything was baked
         // recorded as baked even when a vertex was not finite: the next valid edit of the instance re-bakes it
@@ -1071,7 +1103,7 @@ int lpt_scene_gpu_rebuild(lpt_scene_gpu *sg, const lpt_scene *scene) {
         TRY(commit_tables(sg, tables));
     }
     DevMem woop_prim;
-    TRY(dev_alloc(woop_prim, sizeof(WoopTri) * (size_t)n));
+    TRY(woop_prim.alloc(sizeof(WoopTri) * (size_t)n));
     TRY(bake_instances(sg, *scene, every_instance(*scene), woop_prim.get()));
     // the new tree replaces the old one only when its build succeeds: bound renderers and later updates never see freed memory
     DevTree t;
@@ -1106,14 +1138,13 @@ int lpt_scene_gpu_update_punctual(lpt_scene_gpu *sg, const lpt_scene *scene) {
 int lpt_probe_upload(lpt_device *dev, const uint8_t *rgbe8, uint32_t w, uint32_t h, lpt_probe **out) {
     if (!dev || !rgbe8 || !w || !h || !out) return fail(LPT_ERR_INVALID_ARG, "lpt_probe_upload: null or empty");
     HIP_TRY(hipSetDevice(dev->ordinal));
-    lpt_probe *p = new lpt_probe();
+    std::unique_ptr<lpt_probe> p(new lpt_probe());
     p->dev = dev;
-    hipError_t e = hipMalloc(&p->rgbe, (size_t)w * h * 4);
-    if (e == hipSuccess) e = hipMemcpy(p->rgbe, rgbe8, (size_t)w * h * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { if (p->rgbe) hipFree(p->rgbe); delete p; return fail(LPT_ERR_HIP, "probe upload failed: %s", hipGetErrorString(e)); }
-    p->d.rgbe = (const uint8_t *)p->rgbe;
+    TRY(p->rgbe.alloc((size_t)w * h * 4));
+    HIP_TRY(hipMemcpy(p->rgbe, rgbe8, (size_t)w * h * 4, hipMemcpyHostToDevice));
+    p->d.rgbe = as<const uint8_t>(p->rgbe);
     p->d.w = w; p->d.h = h;
-    *out = p;
+    *out = p.release();
     return LPT_OK;
 }
 
@@ -1134,9 +1165,11 @@ static int probe_env(lpt_probe *p, bool &has) {
                 const size_t a = i - i % W + d.col_alias[i];   // the alias's place: same row
                 tab[H + i] = make_float4(d.col_q[i], bits_as_float(d.col_alias[i]), d.pdf_uv[i], d.pdf_uv[a]);
             }
-            HIP_TRY(hipMalloc(&p->env_buf, tab.size() * sizeof(float4)));
-            HIP_TRY(hipMemcpy(p->env_buf, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
-            const float4 *b = (const float4 *)p->env_buf;
+            DevBuf<float4> buf;   // the probe's only once it holds the table
+            TRY(buf.alloc(tab.size()));
+            HIP_TRY(hipMemcpy(buf, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
+            p->env_buf = std::move(buf);
+            const float4 *b = p->env_buf;
             p->env = DEnv{b, b + H, W, H};
             p->env_state = 1;
         } else {
@@ -1154,9 +1187,7 @@ int lpt_probe_destroy(lpt_probe *p) {
     hipDeviceSynchronize();   // frames in flight on the renderers' streams may still sample the probe
     for (lpt_renderer *r : p->dev->renderers)   // a renderer still bound to it falls back to the 1x1 default probe (renderer.rs:693-696)
         if (r->probe == p) r->probe = nullptr;
-    if (p->rgbe) hipFree(p->rgbe);
-    if (p->env_buf) hipFree(p->env_buf);
-    delete p;
+    delete p;   // its device memory with it
     return LPT_OK;
 }
 
@@ -1331,75 +1362,30 @@ int lpt_trace_occluded(lpt_device *dev, const lpt_scene_gpu *sg, const float *or
 }
 
 // ============================================================================ Renderer
-static void free_denoiser(lpt_renderer *r) {
-    for (int k = 0; k < 2; ++k) {
-        if (r->den_gbuf[k]) hipFree(r->den_gbuf[k]);
-        if (r->den_rad[k]) hipFree(r->den_rad[k]);
-        if (r->den_mom[k]) hipFree(r->den_mom[k]);
-        if (r->den_hist[k]) hipFree(r->den_hist[k]);
-        r->den_gbuf[k] = nullptr; r->den_rad[k] = nullptr; r->den_mom[k] = nullptr; r->den_hist[k] = nullptr;
-    }
-    if (r->den_motion) hipFree(r->den_motion);
-    if (r->den_temp) hipFree(r->den_temp);
-    if (r->den_noisy) hipFree(r->den_noisy);
-    if (r->den_nd) hipFree(r->den_nd);
-    r->den_motion = nullptr; r->den_temp = nullptr; r->den_noisy = nullptr; r->den_nd = nullptr;
-    r->den_inputs_ready = false;
-    r->den_cur = 1;
-}
-
-static int alloc_denoiser(lpt_renderer *r);
 static int ensure_denoiser(lpt_renderer *r) {
-    if (r->den_temp) return LPT_OK;
-    const int st = alloc_denoiser(r);
-    if (st != LPT_OK) free_denoiser(r);   // all or nothing: a later call starts over instead of leaking the part that was allocated
-    return st;
-}
-static int alloc_denoiser(lpt_renderer *r) {
+    if (r->has_denoiser()) return LPT_OK;
     const size_t n = (size_t)r->w * r->h;
     hipStream_t s = r->stream;
+    Denoiser d;   // joins the renderer once it is whole: a failure half way leaves the renderer without one, and a later call starts over
     for (int k = 0; k < 2; ++k) {
-        HIP_TRY(hipMalloc(&r->den_gbuf[k], sizeof(uint4) * n));
-        HIP_TRY(hipMalloc(&r->den_rad[k], sizeof(float4) * n));
-        HIP_TRY(hipMalloc(&r->den_mom[k], sizeof(float2) * n));
-        HIP_TRY(hipMalloc(&r->den_hist[k], sizeof(uint32_t) * n));
-        HIP_TRY(hipMemsetAsync(r->den_gbuf[k], 0, sizeof(uint4) * n, s));
-        HIP_TRY(hipMemsetAsync(r->den_rad[k], 0, sizeof(float4) * n, s));
-        HIP_TRY(hipMemsetAsync(r->den_mom[k], 0, sizeof(float2) * n, s));
-        HIP_TRY(hipMemsetAsync(r->den_hist[k], 0, sizeof(uint32_t) * n, s));  // history 0 = nothing to reproject
+        TRY(d.den_gbuf[k].alloc(n));
+        TRY(d.den_rad[k].alloc(n));
+        TRY(d.den_mom[k].alloc(n));
+        TRY(d.den_hist[k].alloc(n));
+        HIP_TRY(hipMemsetAsync(d.den_gbuf[k], 0, sizeof(uint4) * n, s));
+        HIP_TRY(hipMemsetAsync(d.den_rad[k], 0, sizeof(float4) * n, s));
+        HIP_TRY(hipMemsetAsync(d.den_mom[k], 0, sizeof(float2) * n, s));
+        HIP_TRY(hipMemsetAsync(d.den_hist[k], 0, sizeof(uint32_t) * n, s));  // history 0 = nothing to reproject
     }
-    HIP_TRY(hipMalloc(&r->den_motion, sizeof(float2) * n));
-    HIP_TRY(hipMalloc(&r->den_noisy, sizeof(float4) * n));
-    HIP_TRY(hipMalloc(&r->den_nd, sizeof(float4) * n));
-    HIP_TRY(hipMalloc(&r->den_temp, sizeof(float4) * n));   // the "allocated" marker (ensure_denoiser)
-    HIP_TRY(hipMemsetAsync(r->den_noisy, 0, sizeof(float4) * n, s));
-    HIP_TRY(hipMemsetAsync(r->den_motion, 0, sizeof(float2) * n, s));
+    TRY(d.den_motion.alloc(n));
+    TRY(d.den_noisy.alloc(n));
+    TRY(d.den_nd.alloc(n));
+    TRY(d.den_temp.alloc(n));
+    HIP_TRY(hipMemsetAsync(d.den_noisy, 0, sizeof(float4) * n, s));
+    HIP_TRY(hipMemsetAsync(d.den_motion, 0, sizeof(float2) * n, s));
     HIP_TRY(hipStreamSynchronize(s));   // the primary pass of the first frame may run on a lane's stream
+    static_cast<Denoiser &>(*r) = std::move(d);
     return LPT_OK;
-}
-
-static void free_ray_buffers(Wavefront &wf) {
-    void *ptrs[] = {wf.q[0].o, wf.q[0].d, wf.q[0].T, wf.q[1].o, wf.q[1].d, wf.q[1].T, wf.sq.o, wf.sq.d, wf.sq.c, wf.hits, wf.Lsum, wf.strag};
-    for (void *p : ptrs) if (p) hipFree(p);
-    wf.q[0] = Queue{}; wf.q[1] = Queue{}; wf.sq = ShadowQueue{};
-    wf.hits = wf.Lsum = nullptr;
-    wf.strag = nullptr;
-    wf.ray_cap = 0;
-}
-
-static void free_frame_buffers(lpt_renderer *r) {
-    free_denoiser(r);  // Renderer::resize re-creates the ASVGF resources (renderer.rs:347-355)
-    for (int l = 0; l < kMaxLanes; ++l) free_ray_buffers(r->wf[l]);
-    if (r->accum) hipFree(r->accum);
-    if (r->scratch) hipFree(r->scratch);
-    r->accum = r->scratch = nullptr;
-    if (r->frame) hipFree(r->frame);
-    if (r->xstage) hipFree(r->xstage);
-    r->frame = r->xstage = nullptr;
-    r->xstage_elems = 0;
-    r->xevent_recorded = false;
-    r->presented = false;
-    r->n_slots = 0;
 }
 
 // ---- tile ownership (kernels.h ShardMap / ShardTable).  The V = sum(weights) virtual ranks are dealt to the ranks so that every
@@ -1472,99 +1458,118 @@ static void shard_geometry(const lpt_renderer *r, uint32_t &tiles_x, uint32_t &n
     n_slots = owned_tiles(r->map, n_tiles) * r->tile_w * r->tile_h;
 }
 
-// per-ray buffers of one lane (queues, hits, shadow queue, per-sample radiance): one element per ray of a wavefront
+// per-ray buffers of one lane (queues, hits, shadow queue, per-sample radiance): one element per ray of a wavefront.  The lane lets go of what it has first;
+// the new buffers join it, with the queue views the kernels get, once they are whole
 static int alloc_ray_buffers(Wavefront &wf, size_t rays) {
-    free_ray_buffers(wf);
+    release<RayBuffers>(wf);
     const size_t n = std::max<size_t>(rays, 64);
     if (n > 0x7FFFFFFFull) return fail(LPT_ERR_INVALID_ARG, "a wavefront of %zu rays exceeds 2^31", n);
+    RayBuffers b;
     for (int k = 0; k < 2; ++k) {
-        HIP_TRY(hipMalloc(&wf.q[k].o, sizeof(float4) * n));
-        HIP_TRY(hipMalloc(&wf.q[k].d, sizeof(float4) * n));
-        HIP_TRY(hipMalloc(&wf.q[k].T, sizeof(float4) * n));
+        TRY(b.q_mem[k].o.alloc(n));
+        TRY(b.q_mem[k].d.alloc(n));
+        TRY(b.q_mem[k].t.alloc(n));
+        b.q[k] = Queue{b.q_mem[k].o, b.q_mem[k].d, b.q_mem[k].t};
     }
-    HIP_TRY(hipMalloc(&wf.sq.o, sizeof(float4) * n));
-    HIP_TRY(hipMalloc(&wf.sq.d, sizeof(float4) * n));
-    HIP_TRY(hipMalloc(&wf.sq.c, sizeof(float4) * n));
-    HIP_TRY(hipMalloc(&wf.hits, sizeof(float4) * n));
-    HIP_TRY(hipMalloc(&wf.Lsum, sizeof(float4) * n));
-    HIP_TRY(hipMalloc(&wf.strag, sizeof(uint32_t) * 2 * n));   // a launch carries at most n closest-hit + n shadow rays
-    wf.ray_cap = n;
+    TRY(b.sq_mem.o.alloc(n));
+    TRY(b.sq_mem.d.alloc(n));
+    TRY(b.sq_mem.t.alloc(n));
+    b.sq = ShadowQueue{b.sq_mem.o, b.sq_mem.d, b.sq_mem.t};
+    TRY(b.hits.alloc(n));
+    TRY(b.Lsum.alloc(n));
+    TRY(b.strag.alloc(2 * n));   // a launch carries at most n closest-hit + n shadow rays
+    b.ray_cap = n;
+    static_cast<RayBuffers &>(wf) = std::move(b);
     return LPT_OK;
 }
 
-// stream, events and counters of a lane (created on first use).  Lane 0 enqueues on the renderer's stream: the runtime maps
+// stream, events and counters of a lane (created on first use), and the `n_trav` traversal events a phased plan has its stages record.
+// Lane 0 enqueues on the renderer's stream: the runtime maps
 // streams onto a fixed number of hardware queues (4 by default: the null stream, the device's, the renderer's and one more), and
 // streams that share a queue run back to back — with a stream of its own for every lane, the two lanes of the default renderer
 // shared one queue and never overlapped (profiles/r08_lane_phase_ab.txt)
-static int ensure_lane(lpt_renderer *r, int l) {
+static int ensure_lane(lpt_renderer *r, int l, uint32_t n_trav = 0) {
     Wavefront &wf = r->wf[l];
-    if (l > 0 && !wf.stream) HIP_TRY(hipStreamCreateWithFlags(&wf.stream, hipStreamNonBlocking));
-    if (!wf.done) HIP_TRY(hipEventCreateWithFlags(&wf.done, hipEventDisableTiming));
-    if (!wf.consumed) HIP_TRY(hipEventCreateWithFlags(&wf.consumed, hipEventDisableTiming));
-    if (!wf.ctr) HIP_TRY(hipMalloc(&wf.ctr, sizeof(FrameCounters)));
+    if (l > 0 && !wf.stream) TRY(wf.stream.create());
+    if (!wf.done) TRY(wf.done.create());
+    if (!wf.consumed) TRY(wf.consumed.create());
+    if (!wf.ctr) TRY(wf.ctr.alloc(1));
+    for (uint32_t t = 0; t < n_trav; ++t)
+        if (!wf.trav[t]) TRY(wf.trav[t].create());
     return LPT_OK;
 }
 
+// lane `l` holds `n` rays: a lane that has to grow waits first for what still reads its buffers — everything that read them has been enqueued behind the
+// waits of the renderer's stream, and the lane's own launches are on its own
+static int lane_hold(lpt_renderer *r, int l, size_t n) {
+    TRY(ensure_lane(r, l));
+    Wavefront &wf = r->wf[l];
+    if (n <= wf.ray_cap) return LPT_OK;
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (wf.stream) HIP_TRY(hipStreamSynchronize(wf.stream));
+    return alloc_ray_buffers(wf, n);
+}
+
+// The frame buffers for the renderer's size and shard; what depended on the old ones (the denoiser: Renderer::resize re-creates the ASVGF resources,
+// renderer.rs:347-355; every lane's ray buffers) goes with them.  A failure leaves the renderer without frame buffers: raytrace() is then the no-op of a 0 x 0
+// renderer (record_call) and the reads report that there is no target.
 static int alloc_frame_buffers(lpt_renderer *r) {
     HIP_TRY(hipSetDevice(r->dev->ordinal));
     HIP_TRY(hipStreamSynchronize(r->stream));
-    free_frame_buffers(r);
+    release<Denoiser>(*r);
+    for (int l = 0; l < kMaxLanes; ++l) release<RayBuffers>(r->wf[l]);
+    release<FrameBuffers>(*r);
     if (!r->w || !r->h) return LPT_OK;
     uint32_t tiles_x, n_tiles, n_slots;
     shard_geometry(r, tiles_x, n_tiles, n_slots);
     const size_t px = (size_t)r->w * r->h;
-    r->n_slots = n_slots;   // the lanes' ray buffers are allocated by the first raytrace() that uses them
     if (r->rank == 0u) {   // a possible root of an exchange (also of a one-rank communicator): the whole ownership rule, for the unpack kernels
         r->h_table = make_shard_table(r->weights, r->world, n_tiles, r->tile_w * r->tile_h, r->h_offset);
-        if (!r->d_table) HIP_TRY(hipMalloc(&r->d_table, sizeof(ShardTable)));
+        if (!r->d_table) TRY(r->d_table.alloc(1));
         HIP_TRY(hipMemcpy(r->d_table, &r->h_table, sizeof(ShardTable), hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipMalloc(&r->accum, sizeof(float4) * px));
-    HIP_TRY(hipMalloc(&r->scratch, sizeof(float4) * px));
-    HIP_TRY(hipMemsetAsync(r->accum, 0, sizeof(float4) * px, r->stream));
+    FrameBuffers fb;
+    fb.n_slots = n_slots;   // the lanes' ray buffers are allocated by the first raytrace() that uses them
+    TRY(fb.accum.alloc(px));
+    TRY(fb.scratch.alloc(px));
+    HIP_TRY(hipMemsetAsync(fb.accum, 0, sizeof(float4) * px, r->stream));
+    static_cast<FrameBuffers &>(*r) = std::move(fb);
     return LPT_OK;
 }
 
 int lpt_renderer_create(lpt_device *dev, uint32_t width, uint32_t height, lpt_renderer **out) {
     if (!dev || !out) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_create: null");
     HIP_TRY(hipSetDevice(dev->ordinal));
-    lpt_renderer *r = new lpt_renderer();
+    std::unique_ptr<lpt_renderer> r(new lpt_renderer());   // a failure below drops it, and what it owns by then
     r->dev = dev;
-    {
-        hipError_t se = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
-        if (se != hipSuccess) { delete r; return fail(LPT_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(se)); }
-    }
+    TRY(r->stream.create());
     r->prev_cam.origin = mk3(0.f, 0.f, 0.f); r->prev_cam.right = mk3(1.f, 0.f, 0.f); r->prev_cam.up = mk3(0.f, 1.f, 0.f);
     r->prev_cam.fwd = mk3(0.f, 0.f, 1.f); r->prev_cam.ax = r->prev_cam.ay = 1.0f;   // Mat4::IDENTITY (renderer.rs:319)
     r->req_w = width; r->req_h = height;
     // get_downsampled_size (renderer.rs:18-22)
     r->w = (uint32_t)((float)width * r->downsample);
     r->h = (uint32_t)((float)height * r->downsample);
-    hipError_t e = hipMalloc(&r->totals, sizeof(Totals));
-    if (e == hipSuccess) e = hipMemset(r->totals, 0, sizeof(Totals));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&r->err_host, sizeof(uint32_t), hipHostMallocMapped);
-    if (e == hipSuccess) { *r->err_host = 0u; e = hipHostGetDevicePointer((void **)&r->err_dev, r->err_host, 0); }
-    if (e == hipSuccess) e = hipMalloc(&r->default_probe, 4);
-    if (e == hipSuccess) e = hipMemset(r->default_probe, 0, 4);  // 1x1 zero texel: black environment (device.rs:13-26)
-    if (e == hipSuccess) e = hipMalloc(&r->srgb_thr, 256 * sizeof(float));
-    if (e == hipSuccess) {
-        float thr[256];
-        thr[0] = 0.0f;
-        for (int i = 1; i < 256; ++i) {   // inverse OETF at (i - 0.5) / 255 in binary64, rounded once
-            const double v = ((double)i - 0.5) / 255.0;
-            thr[i] = (float)(v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4));
-        }
-        e = hipMemcpy(r->srgb_thr, thr, sizeof thr, hipMemcpyHostToDevice);
+    TRY(r->totals.alloc(1));
+    HIP_TRY(hipMemset(r->totals, 0, sizeof(Totals)));
+    {
+        void *word = nullptr;
+        HIP_TRY(hipHostMalloc(&word, sizeof(uint32_t), hipHostMallocMapped));
+        r->err_host.reset((uint32_t *)word);
+        *r->err_host = 0u;
     }
-    if (e != hipSuccess) {
-        const int st = fail(LPT_ERR_HIP, "renderer allocation failed: %s", hipGetErrorString(e));
-        lpt_renderer_destroy(r);   // frees whatever was allocated (every member starts out null)
-        return st;
+    TRY(r->default_probe.alloc(4));
+    HIP_TRY(hipMemset(r->default_probe, 0, 4));  // 1x1 zero texel: black environment (device.rs:13-26)
+    TRY(r->srgb_thr.alloc(256));
+    float thr[256];
+    thr[0] = 0.0f;
+    for (int i = 1; i < 256; ++i) {   // inverse OETF at (i - 0.5) / 255 in binary64, rounded once
+        const double v = ((double)i - 0.5) / 255.0;
+        thr[i] = (float)(v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4));
     }
-    int st = alloc_frame_buffers(r);
-    if (st != LPT_OK) { lpt_renderer_destroy(r); return st; }
-    dev->renderers.push_back(r);
-    *out = r;
+    HIP_TRY(hipMemcpy(r->srgb_thr, thr, sizeof thr, hipMemcpyHostToDevice));
+    TRY(alloc_frame_buffers(r.get()));
+    dev->renderers.push_back(r.get());
+    *out = r.release();
     return LPT_OK;
 }
 
@@ -1580,33 +1585,7 @@ int lpt_renderer_destroy(lpt_renderer *r) {
     hipStreamSynchronize(r->stream);
     for (int l = 0; l < kMaxLanes; ++l)   // a wavefront whose second half was never enqueued (a failed submission) is not behind r->stream
         if (r->wf[l].stream) hipStreamSynchronize(r->wf[l].stream);
-    free_frame_buffers(r);
-    for (int l = 0; l < kMaxLanes; ++l) {
-        Wavefront &wf = r->wf[l];
-        if (wf.stream) hipStreamDestroy(wf.stream);
-        if (wf.done) hipEventDestroy(wf.done);
-        if (wf.consumed) hipEventDestroy(wf.consumed);
-        for (hipEvent_t e : wf.trav) hipEventDestroy(e);
-        if (wf.ctr) hipFree(wf.ctr);
-    }
-    if (r->totals) hipFree(r->totals);
-    if (r->err_host) hipHostFree(r->err_host);
-    if (r->occ_table) hipFree(r->occ_table);
-    if (r->d_table) hipFree(r->d_table);
-    if (r->default_probe) hipFree(r->default_probe);
-    if (r->srgb_thr) hipFree(r->srgb_thr);
-    if (r->xevent) hipEventDestroy(r->xevent);
-    if (r->stream) hipStreamDestroy(r->stream);
-    if (r->noise) hipFree(r->noise);
-    if (r->ev_start) {
-        for (int i = 0; i < lpt_renderer::kRing * lpt_renderer::kMaxEvents; ++i) {
-            if (r->ev_start[i]) hipEventDestroy(r->ev_start[i]);
-            if (r->ev_stop[i]) hipEventDestroy(r->ev_stop[i]);
-        }
-        delete[] r->ev_start;
-        delete[] r->ev_stop;
-    }
-    delete r;
+    delete r;   // what it owns with it: the buffers before the streams and events they were used on
     return LPT_OK;
 }
 
@@ -1769,8 +1748,8 @@ int lpt_renderer_upload_noise(lpt_renderer *r, const uint8_t *rgba8, uint32_t w,
     FLUSH_OR_RETURN(r);
     HIP_TRY(hipSetDevice(r->dev->ordinal));
     HIP_TRY(hipStreamSynchronize(r->stream));
-    if (r->noise) { hipFree(r->noise); r->noise = nullptr; }
-    HIP_TRY(hipMalloc(&r->noise, (size_t)w * h * 4));
+    r->noise.reset();
+    TRY(r->noise.alloc((size_t)w * h * 4));
     HIP_TRY(hipMemcpy2D(r->noise, (size_t)w * 4, rgba8, row_bytes, (size_t)w * 4, h, hipMemcpyHostToDevice));
     r->noise_w = w; r->noise_h = h;
     return LPT_OK;
@@ -1795,7 +1774,7 @@ int lpt_renderer_set_lanes(lpt_renderer *r, int lanes) {
     for (int l = 0; l < kMaxLanes; ++l) {
         if (r->wf[l].stream) HIP_TRY(hipStreamSynchronize(r->wf[l].stream));
         r->wf[l].consumed_recorded = false;
-        if (l >= lanes) free_ray_buffers(r->wf[l]);
+        if (l >= lanes) release<RayBuffers>(r->wf[l]);
     }
     r->n_lanes = lanes;
     r->lane_rr = 0;
@@ -1860,7 +1839,7 @@ int lpt_renderer_enable_stats(lpt_renderer *r, int flag) {
     r->stats = flag != 0;
     if (flag) {   // the occluder-cache probe's table (kernels.h OccProbe): empty at the start of every stats session
         HIP_TRY(hipSetDevice(r->dev->ordinal));
-        if (!r->occ_table) HIP_TRY(hipMalloc(&r->occ_table, sizeof(uint32_t) * kOccEntries));
+        if (!r->occ_table) TRY(r->occ_table.alloc(kOccEntries));
         HIP_TRY(hipMemsetAsync(r->occ_table, 0, sizeof(uint32_t) * kOccEntries, r->stream));
         HIP_TRY(hipStreamSynchronize(r->stream));
     }
@@ -1871,14 +1850,12 @@ int lpt_renderer_enable_timings(lpt_renderer *r, int flag) {
     FLUSH_OR_RETURN(r);
     HIP_TRY(hipSetDevice(r->dev->ordinal));
     const int total = lpt_renderer::kRing * lpt_renderer::kMaxEvents;
-    if (flag && !r->ev_start) {
-        r->ev_start = new hipEvent_t[total]();   // null until created: a failure half way leaves nothing undefined for destroy
-        r->ev_stop = new hipEvent_t[total]();
-    }
     if (flag) {
+        r->ev_start.resize(total);   // empty owners until created: a failure half way is made up for by the next call
+        r->ev_stop.resize(total);
         for (int i = 0; i < total; ++i) {
-            if (!r->ev_start[i]) HIP_TRY(hipEventCreate(&r->ev_start[i]));
-            if (!r->ev_stop[i]) HIP_TRY(hipEventCreate(&r->ev_stop[i]));
+            if (!r->ev_start[i]) TRY(r->ev_start[i].create(hipEventDefault));
+            if (!r->ev_stop[i]) TRY(r->ev_stop[i].create(hipEventDefault));
         }
     }
     if (flag) {  // (re)start accumulating
@@ -2046,7 +2023,7 @@ static FrameParams frame_params(const lpt_renderer *r, const float view[16], uin
 // of the calls saw (frame_count0, seed0, acc0 = its accumulate flag; the later ones ran with accumulate == true by construction).
 // This is everything before the first launch: the lane `piece.lane` (submission_plan.h) and its buffers, the denoiser's flip and memsets, the wait for what consumed the
 // lane's previous radiance, the launch plan.  The launches themselves are left in `tk` for enqueue_stage, stage by stage.
-static int wavefront_prepare(lpt_renderer *r, const lpt_renderer::Pending &b, const SubmissionPiece &piece, Ticket &tk) {
+static int wavefront_prepare(lpt_renderer *r, const lpt_renderer::Pending &b, const SubmissionPiece &piece, uint32_t trav_events, Ticket &tk) {
     r->n_wavefronts++;
     HIP_TRY(hipSetDevice(r->dev->ordinal));
     hipStream_t sm = r->stream;                  // accumulation, filter passes, bookkeeping, reads, the exchange: in call order
@@ -2059,38 +2036,23 @@ static int wavefront_prepare(lpt_renderer *r, const lpt_renderer::Pending &b, co
     const bool denoise = r->mode != LPT_BLIT_PATHTRACE;
     const bool split = r->n_lanes > 1;           // the wavefront runs on the lane's own stream (a single wavefront on the renderer's own stream instead: 2.89 against 2.90 ms per 1/8-shard frame, round 5)
     const int lane = (int)piece.lane;
-    {
-        int st = ensure_lane(r, lane);
-        if (st != LPT_OK) return st;
-    }
+    TRY(ensure_lane(r, lane, trav_events));   // with the events the piece's stages record
     Wavefront &wf = r->wf[lane];
     hipStream_t s = (split && lane > 0) ? wf.stream : sm;
     r->last_lane = lane;
     if ((size_t)n_rays > wf.ray_cap && p.n_slots) {
-        HIP_TRY(hipStreamSynchronize(sm));       // everything that read this lane's buffers has been enqueued behind `sm`'s waits
-        HIP_TRY(hipStreamSynchronize(s));
-        int st = alloc_ray_buffers(wf, n_rays);
-        if (st != LPT_OK) return st;
+        TRY(lane_hold(r, lane, n_rays));
         // the next wavefronts of this size take the other lanes: give them their buffers now, not in the middle of a later frame
         // (a first-use hipMalloc of gigabytes takes tens of milliseconds on some hosts)
-        for (int l = 0; split && !denoise && l < r->n_lanes; ++l) {
-            if (l == lane || r->wf[l].ray_cap >= (size_t)n_rays) continue;
-            st = ensure_lane(r, l);
-            if (st != LPT_OK) return st;
-            if (r->wf[l].stream) HIP_TRY(hipStreamSynchronize(r->wf[l].stream));   // lane 0's work is behind `sm`, synchronised above
-            st = alloc_ray_buffers(r->wf[l], n_rays);
-            if (st != LPT_OK) return st;
-        }
+        for (int l = 0; split && !denoise && l < r->n_lanes; ++l)
+            if (l != lane) TRY(lane_hold(r, l, n_rays));
     }
     tk = Ticket{};
     tk.lane = lane; tk.denoise = denoise;
     WavefrontLaunch &L = tk.launch;
     L.r = r; L.w = &wf; L.s = s; L.split = split; L.p = p; L.nb = nb; L.seed0 = seed0;
     GBufArgs &gb = L.gb;
-    if (denoise) {
-        int st = ensure_denoiser(r);
-        if (st != LPT_OK) return st;
-    }
+    if (denoise) TRY(ensure_denoiser(r));
     // the accumulation that consumed this lane's previous radiance.  A denoising frame also overwrites what the previous
     // frame's filter passes read (G-buffer ping-pong, motion) — and on a sharded frame those are enqueued by a later call
     // (lpt_renderer_exchange / denoise_filter) — so it waits for everything the renderer's stream holds so far.
@@ -2111,11 +2073,11 @@ static int wavefront_prepare(lpt_renderer *r, const lpt_renderer::Pending &b, co
         gb.prev = r->prev_cam;
     }
 
-    L.probe = r->probe ? r->probe->d : DProbe{(const uint8_t *)r->default_probe, 1u, 1u};
+    L.probe = r->probe ? r->probe->d : DProbe{as<const uint8_t>(r->default_probe), 1u, 1u};
     bool env = false;   // SPEC §18: the ENV kernels while the mode is on and the bound probe has a distribution
     if (r->env_sampling && r->probe) TRY(probe_env(const_cast<lpt_probe *>(r->probe), env));
     L.ev = env ? r->probe->env : DEnv{};
-    L.nz = DNoise{(const uint8_t *)r->noise, r->noise_w, r->noise_h, (r->use_noise && r->noise) ? 1u : 0u};
+    L.nz = DNoise{as<const uint8_t>(r->noise), r->noise_w, r->noise_h, (r->use_noise && r->noise) ? 1u : 0u};
     const DScene &sc = r->sg->d;
     if (r->timings) { r->ring_pos++; harvest_slot(r, cur_slot(r)); }
     if (!p.n_slots) return LPT_OK;
@@ -2240,7 +2202,7 @@ static int wavefront_finish(lpt_renderer *r, const Ticket &tk, const ReadPlan *r
                     hipLaunchKernelGGL(k_resolve, dim3(div_up((uint32_t)cnt, kBlock)), dim3(kBlock), 0, sm, r->accum + off, r->scratch + off, (uint32_t)cnt);
                     HIP_TRY(hipMemcpyAsync(read->radiance + 4u * off, r->scratch + off, sizeof(float4) * cnt, hipMemcpyDeviceToHost, sm));
                 } else {
-                    uchar4 *px = reinterpret_cast<uchar4 *>(r->scratch) + off;
+                    uchar4 *px = reinterpret_cast<uchar4 *>(r->scratch.get()) + off;
                     hipLaunchKernelGGL(k_tonemap, dim3(div_up((uint32_t)cnt, kBlock)), dim3(kBlock), 0, sm, r->accum + off, px, (uint32_t)cnt, r->srgb_thr);
                     HIP_TRY(hipMemcpy2DAsync(read->rgba8 + (size_t)row0 * read->row_bytes, read->row_bytes, px, (size_t)r->w * 4, (size_t)r->w * 4, row1 - row0, hipMemcpyDeviceToHost, sm));
                 }
@@ -2296,23 +2258,15 @@ static int flush_pending(lpt_renderer *r, const ReadPlan *read) {
         return st;
     };
     Ticket tickets[kMaxLanes];
-    const auto trav = [&](const TravEvent &e) { return e.piece < 0 ? (hipEvent_t) nullptr : r->wf[plan.pieces[(size_t)e.piece].lane].trav[e.stage]; };
+    const auto trav = [&](const TravEvent &e) -> hipEvent_t { return e.piece < 0 ? nullptr : r->wf[plan.pieces[(size_t)e.piece].lane].trav[e.stage]; };
     for (const SubmissionStep &step : plan.steps) {
         const SubmissionPiece &piece = plan.pieces[step.piece];
         Ticket &tk = tickets[piece.ticket];
         int st = LPT_OK;
         switch (step.kind) {
-        case SubmissionStep::Prepare: {
-            st = wavefront_prepare(r, b, piece, tk);
-            std::vector<hipEvent_t> &ev = r->wf[piece.lane].trav;   // the events the piece's stages record
-            while (st == LPT_OK && ev.size() < plan.trav_events) {
-                hipEvent_t e = nullptr;
-                const hipError_t he = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-                if (he != hipSuccess) st = fail(LPT_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(he));
-                else ev.push_back(e);
-            }
+        case SubmissionStep::Prepare:
+            st = wavefront_prepare(r, b, piece, plan.trav_events, tk);
             break;
-        }
         case SubmissionStep::Stage: {
             PhaseHooks ph;
             ph.wait_start = trav(step.wait_start);
@@ -2340,7 +2294,7 @@ static uint32_t fuse_cap(const lpt_renderer *r) { return r->max_fused ? r->max_f
 static int record_call(lpt_renderer *r, const float view[16]) {
     r->frame_back = !r->frame_back;              // renderer.rs:401
     if (!r->resources_set || !r->sg) return LPT_OK;  // :403-407, :419-422
-    if (!r->w || !r->h) return LPT_OK;
+    if (!r->accum) return LPT_OK;                // no frame buffers: a 0 x 0 renderer, or one whose allocation failed (alloc_frame_buffers)
     r->presented = false;                        // a new sample: the exchanged frame (if any) is stale
     lpt_renderer::Pending &b = r->pend;
     const bool pathtrace = r->mode == LPT_BLIT_PATHTRACE;
@@ -2420,14 +2374,14 @@ int lpt_renderer_primary_rays(lpt_renderer *r, const float view[16], uint32_t sa
     // the sample-th of consecutive calls: its seeds are max_bounces per call further (record_call); frame_count does not reach k_raygen
     const FrameParams p = frame_params(r, view, 1u, r->frame_count, r->seed + sample * r->max_bounces, r->accumulate, 0u, n_slots);
     DevMem qo, qd, qT, lsum, ctr;
-    TRY(dev_alloc(qo, sizeof(float4) * n_slots));
-    TRY(dev_alloc(qd, sizeof(float4) * n_slots));
-    TRY(dev_alloc(qT, sizeof(float4) * n_slots));
-    TRY(dev_alloc(lsum, sizeof(float4) * n_slots));
-    TRY(dev_alloc(ctr, sizeof(FrameCounters)));
+    TRY(qo.alloc(sizeof(float4) * n_slots));
+    TRY(qd.alloc(sizeof(float4) * n_slots));
+    TRY(qT.alloc(sizeof(float4) * n_slots));
+    TRY(lsum.alloc(sizeof(float4) * n_slots));
+    TRY(ctr.alloc(sizeof(FrameCounters)));
     hipStream_t s = r->stream;
     HIP_TRY(hipMemsetAsync(ctr.get(), 0, sizeof(FrameCounters), s));
-    const DNoise nz{(const uint8_t *)r->noise, r->noise_w, r->noise_h, (r->use_noise && r->noise) ? 1u : 0u};
+    const DNoise nz{as<const uint8_t>(r->noise), r->noise_w, r->noise_h, (r->use_noise && r->noise) ? 1u : 0u};
     const Queue q{as<float4>(qo), as<float4>(qd), as<float4>(qT)};
     const bool dense = (r->w % r->tile_w == 0u) && (r->h % r->tile_h == 0u);
     const uint32_t blocks = std::min<uint32_t>(div_up(n_slots, kBlock), (uint32_t)r->dev->compute_units * 8u);   // launch_plan.h stream_blocks
@@ -2564,11 +2518,11 @@ int lpt_renderer_blit_rgba8(lpt_renderer *r, uint8_t *dst, size_t row_bytes) {
     hipError_t e = hipSetDevice(r->dev->ordinal);
     const uint32_t n = r->w * r->h;
     if (e == hipSuccess) {
-        if ((r->mode == LPT_BLIT_GBUFFER || r->mode == LPT_BLIT_MOTION) && r->den_temp)  // debug views (renderer.rs:574-586)
+        if ((r->mode == LPT_BLIT_GBUFFER || r->mode == LPT_BLIT_MOTION) && r->has_denoiser())  // debug views (renderer.rs:574-586)
             hipLaunchKernelGGL(k_debug_view, dim3(div_up(n, kBlock)), dim3(kBlock), 0, r->stream, r->den_gbuf[r->den_cur], r->den_motion,
-                               (uchar4 *)r->scratch, (int)r->w, (int)r->h, r->mode);
+                               (uchar4 *)r->scratch.get(), (int)r->w, (int)r->h, r->mode);
         else
-            hipLaunchKernelGGL(k_tonemap, dim3(div_up(n, kBlock)), dim3(kBlock), 0, r->stream, presented_target(r), (uchar4 *)r->scratch, n, r->srgb_thr);
+            hipLaunchKernelGGL(k_tonemap, dim3(div_up(n, kBlock)), dim3(kBlock), 0, r->stream, presented_target(r), (uchar4 *)r->scratch.get(), n, r->srgb_thr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy2DAsync(dst, row_bytes, r->scratch, (size_t)r->w * 4, (size_t)r->w * 4, r->h, hipMemcpyDeviceToHost, r->stream);
@@ -2589,7 +2543,7 @@ int lpt_renderer_read_pixels(lpt_renderer *r, uint8_t *dst) {
 int lpt_renderer_read_denoiser(lpt_renderer *r, uint32_t *gbuffer, float *motion, float *radiance, uint32_t *history) {
     if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_read_denoiser: null");
     FLUSH_OR_RETURN(r);
-    if (!r->den_temp) return fail(LPT_ERR_READBACK, "failed to read pixels from GPU to CPU: no denoising frame has been traced");
+    if (!r->has_denoiser()) return fail(LPT_ERR_READBACK, "failed to read pixels from GPU to CPU: no denoising frame has been traced");
     HIP_TRY(hipSetDevice(r->dev->ordinal));
     HIP_TRY(hipStreamSynchronize(r->stream));
     const size_t n = (size_t)r->w * r->h;
@@ -2608,7 +2562,7 @@ int lpt_renderer_read_denoiser(lpt_renderer *r, uint32_t *gbuffer, float *motion
 int lpt_renderer_denoiser_inputs(lpt_renderer *r, void **noisy, void **gbuffer, void **motion, size_t *n_pixels) {
     if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_denoiser_inputs: null");
     FLUSH_OR_RETURN(r);
-    if (!r->den_temp) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_denoiser_inputs: no denoising frame has been traced");
+    if (!r->has_denoiser()) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_denoiser_inputs: no denoising frame has been traced");
     if (noisy) *noisy = r->den_noisy;
     if (gbuffer) *gbuffer = r->den_gbuf[r->den_cur];
     if (motion) *motion = r->den_motion;
@@ -2619,7 +2573,7 @@ int lpt_renderer_denoiser_inputs(lpt_renderer *r, void **noisy, void **gbuffer, 
 int lpt_renderer_denoise_filter(lpt_renderer *r) {
     if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_denoise_filter: null");
     FLUSH_OR_RETURN(r);
-    if (!r->den_temp || !r->den_inputs_ready) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_denoise_filter: no denoising frame has been traced");
+    if (!r->has_denoiser() || !r->den_inputs_ready) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_denoise_filter: no denoising frame has been traced");
     if (r->world == 1u) return LPT_OK;  // raytrace() has already filtered the frame
     HIP_TRY(hipSetDevice(r->dev->ordinal));
     launch_filter(r, r->stream);
@@ -2657,7 +2611,7 @@ int lpt_renderer_get_timings(lpt_renderer *r, lpt_timing *out, int *inout_count)
     HIP_TRY(hipSetDevice(r->dev->ordinal));
     HIP_TRY(hipStreamSynchronize(r->stream));
     lpt_timing acc[ST_COUNT];
-    if (r->ev_start) for (int k = 0; k < lpt_renderer::kRing; ++k) harvest_slot(r, k);
+    if (!r->ev_start.empty()) for (int k = 0; k < lpt_renderer::kRing; ++k) harvest_slot(r, k);
     for (int i = 0; i < ST_COUNT; ++i) {
         memset(&acc[i], 0, sizeof acc[i]);
         snprintf(acc[i].label, sizeof acc[i].label, "%s", kStageLabel[i]);
@@ -2827,17 +2781,17 @@ static FrameParams shard_params(const lpt_renderer *r) {
 // receive buffer) and the staging area for packed tiles: this rank's slots, or every rank's on the root
 static int ensure_exchange_buffers(lpt_renderer *r, bool root, bool want_frame, bool want_stage, size_t bytes_per_slot = 16) {
     const size_t npx = (size_t)r->w * r->h;
-    if ((root || want_frame) && !r->frame) HIP_TRY(hipMalloc(&r->frame, sizeof(float4) * std::max<size_t>(npx, 1)));
-    if (!r->xevent) HIP_TRY(hipEventCreateWithFlags(&r->xevent, hipEventDisableTiming));
+    if ((root || want_frame) && !r->frame) TRY(r->frame.alloc(std::max<size_t>(npx, 1)));
+    if (!r->xevent) TRY(r->xevent.create());
     if (!want_stage) return LPT_OK;
     const FrameParams p = shard_params(r);
     const size_t slots = root ? (size_t)p.n_tiles * p.tile_w * p.tile_h : (size_t)p.n_slots;
     const size_t need = std::max<size_t>((slots * bytes_per_slot + 15) / 16, 1);   // in float4 units
     if (r->xstage_elems < need) {
         HIP_TRY(hipStreamSynchronize(r->stream));
-        if (r->xstage) hipFree(r->xstage);
-        r->xstage = nullptr; r->xstage_elems = 0;
-        HIP_TRY(hipMalloc(&r->xstage, sizeof(float4) * need));
+        r->xstage.reset();
+        r->xstage_elems = 0;
+        TRY(r->xstage.alloc(need));
         r->xstage_elems = need;
     }
     return LPT_OK;
@@ -2869,7 +2823,7 @@ static int exchange_enqueue(lpt_renderer *r, int mode) {
         int st = ensure_exchange_buffers(r, root, false, true, 40);
         if (st != LPT_OK) return st;
         const FrameParams p = shard_params(r);
-        unsigned char *stage = reinterpret_cast<unsigned char *>(r->xstage);
+        unsigned char *stage = reinterpret_cast<unsigned char *>(r->xstage.get());
         if (p.n_slots) hipLaunchKernelGGL(k_pack_den, dim3(stream_grid(r, p.n_slots)), dim3(kBlock), 0, s, p, r->den_noisy, r->den_gbuf[r->den_cur], r->den_motion, stage);
         HIP_TRY(hipGetLastError());
         if (root) {
@@ -2919,7 +2873,7 @@ static int exchange_finish(lpt_renderer *r, int mode) {
     if (r->mode != LPT_BLIT_PATHTRACE) {
         if (root && mode == LPT_EXCHANGE_GATHER_TILES) {
             const FrameParams p = shard_params(r);
-            hipLaunchKernelGGL(k_unpack_den, dim3(stream_grid(r, npx)), dim3(kBlock), 0, s, p, r->d_table, reinterpret_cast<unsigned char *>(r->xstage), r->den_noisy, r->den_gbuf[r->den_cur], r->den_motion);
+            hipLaunchKernelGGL(k_unpack_den, dim3(stream_grid(r, npx)), dim3(kBlock), 0, s, p, r->d_table, reinterpret_cast<unsigned char *>(r->xstage.get()), r->den_noisy, r->den_gbuf[r->den_cur], r->den_motion);
         }
         if (root && r->world != 1u) launch_filter(r, s);   // world == 1: raytrace() has filtered already
         stage_end(r, s);
@@ -2982,7 +2936,7 @@ int lpt_renderer_exchange(lpt_renderer *r, int mode) {
     if ((uint32_t)c->rank != r->rank || (uint32_t)c->world != r->world)
         return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_exchange: the renderer's shard (%u of %u) is not the communicator's (%d of %d); call lpt_renderer_set_comm again",
                     r->rank, r->world, c->rank, c->world);
-    if (r->mode != LPT_BLIT_PATHTRACE && (!r->den_temp || !r->den_inputs_ready)) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_exchange: no denoising frame has been traced");
+    if (r->mode != LPT_BLIT_PATHTRACE && (!r->has_denoiser() || !r->den_inputs_ready)) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_exchange: no denoising frame has been traced");
     if (!rccl()) return LPT_ERR_RCCL;
     HIP_TRY(hipSetDevice(r->dev->ordinal));
     if (r->timings) { r->ring_pos++; harvest_slot(r, cur_slot(r)); }
@@ -3007,19 +2961,19 @@ int lpt_renderer_exchange_local(lpt_renderer *root, lpt_renderer *const *peers, 
     seen[0] = 1;
     for (int i = 0; i < n_peers; ++i) {
         const lpt_renderer *q = peers[i];
-        if (!q || q->w != root->w || q->h != root->h || q->world != root->world || q->tile_w != root->tile_w || q->tile_h != root->tile_h || q->rank >= root->world || seen[q->rank] ||
+        if (!q || !q->accum || q->w != root->w || q->h != root->h || q->world != root->world || q->tile_w != root->tile_w || q->tile_h != root->tile_h || q->rank >= root->world || seen[q->rank] ||
             q->weights != root->weights || (q->mode != LPT_BLIT_PATHTRACE) != den)
             return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_exchange_local: peer %d does not complete the shard set of the root", i);
-        if (den && (!q->den_temp || !q->den_inputs_ready)) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_exchange_local: peer %d has not traced a denoising frame", i);
+        if (den && (!q->has_denoiser() || !q->den_inputs_ready)) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_exchange_local: peer %d has not traced a denoising frame", i);
         seen[q->rank] = 1;
     }
-    if (den && (!root->den_temp || !root->den_inputs_ready)) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_exchange_local: no denoising frame has been traced");
+    if (den && (!root->has_denoiser() || !root->den_inputs_ready)) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_exchange_local: no denoising frame has been traced");
     const size_t bps = den ? 40 : 16;
     HIP_TRY(hipSetDevice(root->dev->ordinal));
     int st = ensure_exchange_buffers(root, true, true, true, bps);
     if (st != LPT_OK) return st;
     const FrameParams p0 = shard_params(root);
-    unsigned char *stage0 = reinterpret_cast<unsigned char *>(root->xstage);
+    unsigned char *stage0 = reinterpret_cast<unsigned char *>(root->xstage.get());
     if (p0.n_slots) {
         if (den) hipLaunchKernelGGL(k_pack_den, dim3(stream_grid(root, p0.n_slots)), dim3(kBlock), 0, root->stream, p0, root->den_noisy, root->den_gbuf[root->den_cur], root->den_motion, stage0);
         else hipLaunchKernelGGL(k_pack_owned, dim3(stream_grid(root, p0.n_slots)), dim3(kBlock), 0, root->stream, p0, root->accum, root->xstage);
@@ -3033,7 +2987,7 @@ int lpt_renderer_exchange_local(lpt_renderer *root, lpt_renderer *const *peers, 
         // the root's staging area may still be read by the unpack of its previous exchange
         if (root->xevent_recorded) HIP_TRY(hipStreamWaitEvent(q->stream, root->xevent, 0));
         if (pq.n_slots) {
-            if (den) hipLaunchKernelGGL(k_pack_den, dim3(stream_grid(q, pq.n_slots)), dim3(kBlock), 0, q->stream, pq, q->den_noisy, q->den_gbuf[q->den_cur], q->den_motion, reinterpret_cast<unsigned char *>(q->xstage));
+            if (den) hipLaunchKernelGGL(k_pack_den, dim3(stream_grid(q, pq.n_slots)), dim3(kBlock), 0, q->stream, pq, q->den_noisy, q->den_gbuf[q->den_cur], q->den_motion, reinterpret_cast<unsigned char *>(q->xstage.get()));
             else hipLaunchKernelGGL(k_pack_owned, dim3(stream_grid(q, pq.n_slots)), dim3(kBlock), 0, q->stream, pq, q->accum, q->xstage);
             // the stand-in of ncclSend / ncclRecv inside one process: a (peer) copy into the root's staging area
             HIP_TRY(hipMemcpyPeerAsync(stage0 + bps * (size_t)root->h_offset[pq.rank], root->dev->ordinal, q->xstage, q->dev->ordinal,

@@ -155,11 +155,21 @@ def test_destroying_a_scene_or_probe_detaches_the_renderers_bound_to_it(device, 
 
 
 def test_lifecycle_does_not_leak_device_memory(device, cornell_glb):
-    """create / resize / render / destroy in a loop: free device memory returns to where it started"""
+    """create / resize / render / destroy in a loop: free device memory returns to where it started.  `cycle` walks sizes and the denoiser at small frames;
+    `churn` walks what else a renderer, its lanes and a probe own — lane streams, events and ray buffers (set_lanes up and down under a cut batch), the noise
+    texture uploaded twice, the stats table and the timing events, the exchange's frame and staging buffers (regrown for the 40-byte denoising slots), the
+    probe's sampling table — at 768 x 512, where each of those buffers is 3 MiB or more: 24 cycles of one leaked buffer exceed the 64 MiB bound.  What is
+    smaller (the 1 MiB occluder table, the counters, the history and straggler words of a small frame, streams and events) is beneath what free memory shows;
+    it is released through the same handle types.  The churn must not change a frame either: every cycle ends with one fixed render, equal to the first's."""
     import torch
     scene = lp.Scene()
     lp.loaders.load_gltf(cornell_glb, scene)
     view = T.look(T.CORNELL_EYE, T.CORNELL_DIR)
+    W, H = 768, 512
+    noise = np.random.default_rng(5).integers(0, 256, (1024, 1024, 4), dtype=np.uint8)   # 4 MiB
+    env = np.zeros((512, 1024, 4), np.uint8)
+    env[100, 300] = (200, 180, 160, 130)                  # one lit texel: the probe has a distribution (8 MiB once built)
+    fixed = []
 
     def cycle(k):
         sg = lp.SceneGPU.new_from_scene(scene, device, gpu_build=bool(k & 1))
@@ -179,12 +189,64 @@ def test_lifecycle_does_not_leak_device_memory(device, cornell_glb):
         sg.rebuild(scene)
         r.close(); pr.close(); sg.close()
 
+    def traced(r):
+        r.reset_accumulation(); r.accumulate = True
+        r.raytrace(view); r.raytrace(view)               # one batch of 2 samples, cut by the submission (raytrace_n would keep it whole)
+        return r.read_radiance()
+
+    def churn(k):
+        sg = lp.SceneGPU.new_from_scene(scene, device)
+        pr = lp.ProbeGPU(device, env, 1024, 512)
+        r, q = lp.Renderer(device, (W, H)), lp.Renderer(device, (W, H))
+        for x in (r, q):
+            x.downsample_factor = 1.0
+            x.resize(device, sg, pr, (W, H))
+            x.set_seed(7)
+        # lanes: 2 x 393216 rays in pieces of at most 262144 are 4 pieces, one per lane; then back to one lane
+        r.set_option("wavefront_rays", 1 << 18)
+        r.set_lanes(4)
+        traced(r)
+        assert r.submission_stats()[1] >= 3
+        r.set_lanes(1)
+        traced(r)
+        # noise and counters
+        for _ in range(2):
+            r.upload_noise_texture(noise, 1024, 1024, 4096)
+        r.use_noise_texture(True)
+        r.enable_stats(True)
+        r.enable_timings(True)
+        traced(r)
+        r.enable_stats(False)
+        # exchange: rank 0 and rank 1 of 2, 16-byte slots, then the denoiser's 40-byte slots, then back
+        r.set_shard(0, 2); q.set_shard(1, 2)
+        for x in (r, q):
+            traced(x)
+        r.exchange_local([q])
+        for x in (r, q):
+            x.set_blit_mode(lp.BlitMode.DenoisedPathrace)
+            x.reset_accumulation()
+            x.raytrace(view)
+        r.exchange_local([q])
+        r.read_radiance()
+        for x in (r, q):
+            x.set_blit_mode(lp.BlitMode.Pahtrace)
+        r.set_shard(0, 1)
+        # environment sampling: the probe's table is built by the first frame that samples it
+        r.set_env_sampling(True)
+        r.set_lanes(2)
+        fixed.append(traced(r).tobytes())                # same seed, Pathtrace, 2 lanes, no shard
+        assert fixed[-1] == fixed[0], k
+        del fixed[1:]
+        r.close(); q.close(); pr.close(); sg.close()
+
     for k in range(12):                                  # every variant once: the runtime's own pools are warm
         cycle(k)
+        churn(k)
     device.synchronize()
     free0 = torch.cuda.mem_get_info(0)[0]
     for k in range(24):
         cycle(k)
+        churn(k)
     device.synchronize()
     free1 = torch.cuda.mem_get_info(0)[0]
     assert free0 - free1 < 64 << 20, (free0, free1)      # allocator slack only, no per-cycle growth
