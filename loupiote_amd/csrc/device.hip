@@ -22,6 +22,7 @@
 #include <mutex>
 #include <new>
 #include <numeric>
+#include <utility>
 
 #include "common.h"
 #include "env_dist.h"
@@ -1925,7 +1926,7 @@ static void launch_filter(lpt_renderer *r, hipStream_t s) {
 }
 
 // Runtime flags as template arguments: calls f(std::bool_constant<flag>{}...), so every combination of the flags is instantiated.  For kernels whose
-// instantiations are a full cross product (k_shade, k_path); NOT for k_trace, which exists in eight of its sixteen forms (launch_plan.h TraceVariant).
+// instantiations are a full cross product (k_raygen, k_trace_coop, k_trace_packet); the kernels that exist in some of their forms only have a launcher each, below.
 template <class F> static void with_flags(F &&f) { f(); }
 template <class F, class... Rest> static void with_flags(F &&f, bool flag, Rest... rest) {
     if (flag) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
@@ -1947,6 +1948,30 @@ static void launch_k_trace(TraceVariant v, uint32_t blocks, size_t lds, hipStrea
     case TraceVariant::Glass:      hipLaunchKernelGGL((k_trace_glass<false>), grid, block, lds, s, ka); break;
     case TraceVariant::StatsGlass: hipLaunchKernelGGL((k_trace_glass<true>), grid, block, lds, s, ka); break;
     }
+}
+
+// A runtime form word as a template argument: calls f(std::integral_constant<uint32_t, W>{}) for the W of the sequence that equals `form`; false if there is none, or if f says so
+template <uint32_t... W, class F> static bool with_form(std::integer_sequence<uint32_t, W...>, uint32_t form, F &&f) { return ((form == W && f(std::integral_constant<uint32_t, W>{})) || ...); }
+
+// k_shade<FORM>: the 96 words of kernel_forms.h that exist (launch_plan.h picks one); false, and no launch, for any other word
+static bool launch_k_shade(uint32_t form, uint32_t blocks, hipStream_t s, const ShadeKernargs &ka) {
+    return with_form(std::make_integer_sequence<uint32_t, kShadeForms>{}, form, [&](auto w) {
+        constexpr uint32_t W = decltype(w)::value;
+        if constexpr (shade_form_valid(W)) hipLaunchKernelGGL((k_shade<W>), dim3(blocks), dim3(kBlock), 0, s, ka);
+        return shade_form_valid(W);
+    });
+}
+
+// k_path<FORM, STATS>: the 8 words x 2; an ENV form takes the probe's distribution behind its other arguments `a`, the others nothing (their argument segment ends before it)
+template <class... A> static bool launch_k_path(uint32_t form, bool stats, uint32_t blocks, size_t lds, hipStream_t s, const DEnv &ev, const A &...a) {
+    return with_form(std::make_integer_sequence<uint32_t, kPathForms>{}, form, [&](auto w) {
+        constexpr uint32_t W = decltype(w)::value;
+        if constexpr (path_form_valid(W)) with_flags([&](auto S) {
+            if constexpr ((W & kShadeEnv) != 0u) hipLaunchKernelGGL((k_path<W, decltype(S)::value, DEnv>), dim3(blocks), dim3(kTraceBlock), lds, s, a..., ev);
+            else hipLaunchKernelGGL((k_path<W, decltype(S)::value>), dim3(blocks), dim3(kTraceBlock), lds, s, a...);
+        }, stats);
+        return path_form_valid(W);
+    });
 }
 
 extern "C" {
@@ -1977,7 +2002,6 @@ struct WavefrontLaunch {
     OccProbe occ{nullptr, 0u, 0.0f};
     size_t trace_lds = 0, coop_lds = 0;
     int sort_queues = 0;
-    bool esamp = false;              // SPEC §23: the ESAMP forms of k_shade
 };
 
 // A wavefront between its two halves (flush_pending): what the second half needs to know about the first, and the first half's launches
@@ -2086,7 +2110,7 @@ static int wavefront_prepare(lpt_renderer *r, const lpt_renderer::Pending &b, co
     WavefrontFacts &f = L.f;
     f.n_rays = n_rays; f.n_slots = p.n_slots; f.slot0 = p.slot0; f.n_samples = n_samples; f.cus = (uint32_t)r->dev->compute_units;
     f.solo = piece.solo; f.stats = r->stats; f.denoise = denoise; f.env = env;
-    f.masked = sc.n_alpha != 0u; f.trans = sc.n_trans != 0u; f.emis = sc.n_emis != 0u; f.nmap = sc.n_nmap != 0u; f.lens = r->lens_r > 0.0f; f.punct = sc.n_punctual != 0u; f.glass_shadow = r->glass_shadows && f.punct && r->sg->n_thin_glass != 0u; f.max_depth = r->sg->stats.max_depth; f.stack_entries = sc.stack_entries;
+    f.masked = sc.n_alpha != 0u; f.trans = sc.n_trans != 0u; f.emis = sc.n_emis != 0u; f.esamp = r->emissive_sampling && f.emis && sc.n_emit != 0u; f.nmap = sc.n_nmap != 0u; f.lens = r->lens_r > 0.0f; f.punct = sc.n_punctual != 0u; f.glass_shadow = r->glass_shadows && f.punct && r->sg->n_thin_glass != 0u; f.max_depth = r->sg->stats.max_depth; f.stack_entries = sc.stack_entries;
     f.pixel_rad = 2.0f * th / (float)std::max(r->h, 1u); f.dense = (r->w % r->tile_w == 0u) && (r->h % r->tile_h == 0u); f.block8 = p.block8 != 0u;
     f.lim = KernelLimits{kBlock, kTraceBlock, kTailMax, kCoopWavesPerCu, kPacketBlocksPerCu, kPacketMaxPixelRad};
     L.tune = r->tune;
@@ -2096,7 +2120,6 @@ static int wavefront_prepare(lpt_renderer *r, const lpt_renderer::Pending &b, co
     L.trace_lds = pl.stack_lds + (pl.tail ? sizeof(uint32_t) * tail_lds_words(f.max_depth) : 0u) + (pl.stats_lds_pad ? 64u : 0u);
     L.coop_lds = sizeof(uint32_t) * coop_stack_entries(kCoopStack, f.max_depth);
     L.sort_queues = r->sort_queues;
-    L.esamp = r->emissive_sampling && f.emis && sc.n_emit != 0u;   // SPEC §23: the ESAMP forms of k_shade while the mode is on and the scene has an emitter distribution
     L.slot = cur_slot(r);
     return LPT_OK;
 }
@@ -2151,11 +2174,8 @@ static int enqueue_stage(const WavefrontLaunch &L, uint32_t t, const PhaseHooks 
             stage_begin(r, ST_PATH, s, slot);
             const size_t plds = pl.stack_lds + kPathLdsExtra;   // stacks + sRGB table + per-bounce counters
             const float4 *h0 = pl.packet ? w->hits : (const float4 *)nullptr;
-            // the instantiation: G-buffer x stats x PUNCT (SPEC §19) x ENV (SPEC §18: `e` is the probe's distribution, or nothing)
-            with_flags([&](auto G, auto S, auto P) {
-                auto launch = [&](auto... e) { hipLaunchKernelGGL((k_path<decltype(G)::value, decltype(S)::value, sizeof...(e) != 0, decltype(P)::value, decltype(e)...>), dim3(pl.path_blocks), dim3(kTraceBlock), plds, s, L.sc, L.probe, L.nz, p, w->q[0], h0, w->Lsum, w->ctr, L.seed0, L.gb, L.tune.path_refill, e...); };
-                if (f.env) launch(L.ev); else launch();
-            }, f.denoise, f.stats, f.punct);
+            if (!launch_k_path(pl.path_form, f.stats, pl.path_blocks, plds, s, L.ev, L.sc, L.probe, L.nz, p, w->q[0], h0, w->Lsum, w->ctr, L.seed0, L.gb, L.tune.path_refill))
+                return fail(LPT_ERR_INVALID_ARG, "the launch plan names k_path form 0x%x, which does not exist", pl.path_form);
             stage_end(r, s, slot);
         }
     } else if (!pl.path) {
@@ -2163,11 +2183,9 @@ static int enqueue_stage(const WavefrontLaunch &L, uint32_t t, const PhaseHooks 
         const uint32_t seed = L.seed0 + t;     // += 1 per bounce (:453, :487)
         const Queue qin = w->q[b & 1u], qout = w->q[(b + 1u) & 1u];
         stage_begin(r, ST_SHADE, s, slot);            // :471-480, :502-508
-        // G: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481); PUNCT / ENV as for k_path; TRANS: SPEC §21; EMIS: SPEC §22; ESAMP: SPEC §23, only with EMIS; NMAP: SPEC §24
         const ShadeKernargs ska{L.sc, L.probe, L.nz, p, qin, w->hits, qout, w->sq, w->Lsum, w->ctr, (int)b, seed, L.gb, L.sort_queues, L.ev};   // ev: read by the ENV forms alone
-        with_flags([&](auto G, auto E, auto P, auto Tr, auto Em, auto Es, auto Nm) {
-            hipLaunchKernelGGL((k_shade<decltype(G)::value, decltype(E)::value, decltype(P)::value, decltype(Tr)::value, decltype(Em)::value, decltype(Em)::value && decltype(Es)::value, decltype(Nm)::value>), dim3(pl.shade_blocks), dim3(kBlock), 0, s, ska);
-        }, f.denoise && b == 0u, f.env, f.punct, f.trans, f.emis, L.esamp, f.nmap);
+        const uint32_t form = b == 0u ? pl.shade_form0 : pl.shade_form;   // bounce 0 of a denoising frame: the PrimaryRayPass form (bounce-0 shading + G-buffer + motion, renderer.rs:466-481)
+        if (!launch_k_shade(form, pl.shade_blocks, s, ska)) return fail(LPT_ERR_INVALID_ARG, "the launch plan names k_shade form 0x%x, which does not exist", form);
         stage_end(r, s, slot);
         if (ph.wait_trav) HIP_TRY(hipStreamWaitEvent(s, ph.wait_trav, 0));
         launch_traversal(L, b + 1u < nb ? (int)(b + 1u) : -1, (int)b);

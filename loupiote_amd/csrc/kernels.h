@@ -13,6 +13,7 @@
 // persistent: a fixed grid of waves pulls 64-ray packets from a device-side head.
 #pragma once
 #include "device_math.h"
+#include "kernel_forms.h"
 
 namespace lptd {
 
@@ -1885,16 +1886,18 @@ struct ShadeOut {
 // every bounce, before the hit's own light sample — and changes nothing else of the hit.
 struct PunctPick { float p_p, p_pick; };   // the punctual share of the non-probe light samples; the probability with which ONE punctual light is picked
 // ESAMP (SPEC §23): the emitter set takes p_m = 1/2 of the non-probe light samples from the punctual and rectangle lights, whose pdfs gain the factor 1 - p_m = 1/2
-template <bool ENV, bool ESAMP = false>
+template <uint32_t FORM>
 __device__ __forceinline__ PunctPick punct_pick(const DScene &sc) {
+    constexpr bool ENV = FORM & kShadeEnv, ESAMP = FORM & kShadeEsamp;
     PunctPick pk;
     pk.p_p = (float)sc.n_punctual / (float)(sc.n_punctual + sc.n_lights);
     pk.p_pick = (((ENV ? 0.5f : 1.0f) * (ESAMP ? 0.5f : 1.0f)) * pk.p_p) / (float)sc.n_punctual;
     return pk;
 }
 // 1 / n of the rectangle lights' pdfs: the probe's half (ENV) and the punctual share (PUNCT) taken off
-template <bool ENV, bool PUNCT, bool ESAMP = false>
+template <uint32_t FORM>
 __device__ __forceinline__ float rect_inv_nl(const DScene &sc, const PunctPick &pk) {
+    constexpr bool ENV = FORM & kShadeEnv, PUNCT = FORM & kShadePunct, ESAMP = FORM & kShadeEsamp;
     if (PUNCT) return sc.n_lights ? (((ENV ? 0.5f : 1.0f) * (ESAMP ? 0.5f : 1.0f)) * (1.0f - pk.p_p)) / (float)sc.n_lights : 0.0f;
     return sc.n_lights ? ((ENV ? 0.5f : 1.0f) * (ESAMP ? 0.5f : 1.0f)) / (float)sc.n_lights : 0.0f;   // ENV: a rectangle light is picked with 1 - p_env = 1/2
 }
@@ -1913,10 +1916,12 @@ __device__ __forceinline__ float light_rl(const float r0, const float p_env, con
 // ESAMP / NMAP — and is asked where that part begins: k_shade re-reads them from its argument segment there (ShadeKernargs), so that they hold no scalar register
 // across its loop; k_path hands out its own parameters.
 struct ShadeCold { const DScene &sc; const DProbe &probe; const DNoise &nz; const GBufArgs &gb; };
-template <bool GBUF, bool ENV, bool PUNCT, bool TRANS = false, bool EMIS = false, bool ESAMP = false, bool NMAP = false, typename LoadO, typename AddL, typename Cold>
+template <uint32_t FORM, typename LoadO, typename AddL, typename Cold>
 __device__ __forceinline__ void shade_hit(const DScene &sc, const DEnv &ev, const FrameParams &p, const float *s_lut,
                                           const uint32_t bounce, const bool last_bounce, const uint32_t seed_base, const float inv_nl, const PunctPick &pk,
                                           const float4 d4, const float4 T4, const float4 h4, LoadO load_o, AddL add_l, Cold cold, ShadeOut &out) {
+    constexpr bool GBUF = FORM & kShadeGbuf, ENV = FORM & kShadeEnv, PUNCT = FORM & kShadePunct, TRANS = FORM & kShadeTrans, EMIS = FORM & kShadeEmis,
+                   ESAMP = FORM & kShadeEsamp, NMAP = FORM & kShadeNmap;   // kernel_forms.h
     out.want_next = false; out.want_shadow = false; out.is_surface = false;
     const uint32_t pxy = __float_as_uint(T4.w);  // x | y << 13 | sample << 26 (k_raygen)
     const f3 d = mk3(d4.x, d4.y, d4.z);
@@ -2244,29 +2249,11 @@ __device__ __forceinline__ ShadeKernargsPtr shade_kernargs() {
     asm volatile("" : "+s"(ka));
     return ka;
 }
-// PUNCT (SPEC §19): the instantiations that run while the scene has punctual lights; LPT_SHADE_WAVES from the compiler's register report
-#ifndef LPT_SHADE_WAVES
-#define LPT_SHADE_WAVES(ENV, PUNCT) (((ENV) || (PUNCT)) ? 3 : 4)
-#endif
-// TRANS (SPEC §21): the instantiations that run while the scene has a transmissive material in use
-#ifndef LPT_SHADE_WAVES_TRANS
-#define LPT_SHADE_WAVES_TRANS(ENV, PUNCT) 3
-#endif
-// EMIS (SPEC §22): the instantiations that run while the scene has an emissive material in use
-#ifndef LPT_SHADE_WAVES_EMIS
-#define LPT_SHADE_WAVES_EMIS(ENV, PUNCT, TRANS) 3
-#endif
-// ESAMP (SPEC §23): the instantiations that run while emitter sampling is on and the scene has an emitter distribution
-#ifndef LPT_SHADE_WAVES_ESAMP
-#define LPT_SHADE_WAVES_ESAMP(ENV, PUNCT, TRANS) 3
-#endif
-// NMAP (SPEC §24): the instantiations that run while the scene has a normal-mapped material in use
-#ifndef LPT_SHADE_WAVES_NMAP
-#define LPT_SHADE_WAVES_NMAP(ENV, PUNCT, TRANS, EMIS, ESAMP) 3
-#endif
-template <bool GBUF, bool ENV = false, bool PUNCT = false, bool TRANS = false, bool EMIS = false, bool ESAMP = false, bool NMAP = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NMAP ? LPT_SHADE_WAVES_NMAP(ENV, PUNCT, TRANS, EMIS, ESAMP) : ESAMP ? LPT_SHADE_WAVES_ESAMP(ENV, PUNCT, TRANS) : EMIS ? LPT_SHADE_WAVES_EMIS(ENV, PUNCT, TRANS) : TRANS ? LPT_SHADE_WAVES_TRANS(ENV, PUNCT) : LPT_SHADE_WAVES(ENV, PUNCT)))) void k_shade(const ShadeKernargs a) {
-    static_assert(EMIS || !ESAMP, "emitter sampling (SPEC §23) exists only for a scene with an emissive material in use");
+// FORM: the features the instantiation shades with, a bit each (kernel_forms.h: the 96 words that exist, and how many waves per SIMD each one runs at)
+template <uint32_t FORM>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(shade_waves(FORM)))) void k_shade(const ShadeKernargs a) {
+    static_assert(shade_form_valid(FORM), "no such k_shade: emitter sampling (SPEC §23) exists only for a scene with an emissive material in use");
+    constexpr bool PUNCT = FORM & kShadePunct;
     // the hot arguments, from the parameter; the cold ones are re-read where they are used (ShadeKernargs)
     const DScene &sc = a.sc;
     const FrameParams &p = a.p;
@@ -2290,8 +2277,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NMAP ? L
     const uint32_t rounded = (count + 255u) & ~255u;  // keep whole blocks in the loop for the barriers
     uint32_t n_surface = 0;
     const bool last_bounce = (uint32_t)bounce + 1u >= p.max_bounces;
-    const PunctPick pk = PUNCT ? punct_pick<ENV, ESAMP>(sc) : PunctPick{0.0f, 0.0f};
-    const float inv_nl = rect_inv_nl<ENV, PUNCT, ESAMP>(sc, pk);
+    const PunctPick pk = PUNCT ? punct_pick<FORM>(sc) : PunctPick{0.0f, 0.0f};
+    const float inv_nl = rect_inv_nl<FORM>(sc, pk);
     for (uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x; i0 < rounded; i0 += stride) {
         ShadeOut so;
         so.want_next = false; so.want_shadow = false; so.is_surface = false;
@@ -2299,7 +2286,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NMAP ? L
         if (i < count) {
             const float4 d4 = ld_nt(qin_d + i), T4 = ld_nt(qin_T + i), h4 = ld_nt(hits + i);
             const uint32_t slot = __float_as_uint(d4.w);
-            shade_hit<GBUF, ENV, PUNCT, TRANS, EMIS, ESAMP, NMAP>(sc, a.ev, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, d4, T4, h4,
+            shade_hit<FORM>(sc, a.ev, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, d4, T4, h4,
                             [&]() { return ld_nt(shade_kernargs()->qin.o + i); },
                             [&](float r, float g, float b) {
                                 float4 *const Lsum = shade_kernargs()->Lsum;
@@ -2411,15 +2398,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NMAP ? L
 // cost (profiles/r04_experiments_ab.txt)
 // The ENV instantiations (SPEC §18: probe sampling in the shading batch) need more registers than that and run at 3 waves per SIMD
 // (168 VGPRs), which they fit without spilling.
-#ifndef LPT_PATH_WAVES
-#define LPT_PATH_WAVES(ENV, PUNCT) (((ENV) || (PUNCT)) ? 3 : 4)
-#endif
 constexpr uint32_t kPathLdsExtra = 1024u + 3u * kMaxBounces * 4u;   // sRGB table + counters: what a wave needs besides its stacks
-template <bool GBUF, bool STATS, bool ENV = false, bool PUNCT = false, typename... Env>
-__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(LPT_PATH_WAVES(ENV, PUNCT), LPT_PATH_WAVES(ENV, PUNCT)))) void k_path(
+template <uint32_t FORM, bool STATS, typename... Env>
+__global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(path_waves(FORM), path_waves(FORM)))) void k_path(
         DScene sc, DProbe probe, DNoise nz, FrameParams p, Queue q0, const float4 *hits0, float4 *Lsum, FrameCounters *ctr, uint32_t seed0, GBufArgs gb, int refill,
         Env... env) {
-    static_assert(sizeof...(Env) == (ENV ? 1u : 0u), "the ENV instantiations take the distribution, the others nothing");
+    static_assert(path_form_valid(FORM), "no such k_path: its forms are the subsets of GBUF | ENV | PUNCT (kernel_forms.h)");
+    constexpr bool PUNCT = FORM & kShadePunct;
+    static_assert(sizeof...(Env) == ((FORM & kShadeEnv) ? 1u : 0u), "the ENV instantiations take the distribution, the others nothing");
     const DEnv ev = env_arg(env...);
     static_assert(kTraceBlock == 64, "one wave per block: the LDS hand-overs below are ordered by the wave's own program order");
     uint2 *stack = reinterpret_cast<uint2 *>(lds_dyn) + threadIdx.x;
@@ -2435,8 +2421,8 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(LPT
     ChunkPuller pl;
     puller_init(pl, &ctr->phead[0], QC(ctr, 0));
     const uint32_t nb = p.max_bounces;
-    const PunctPick pk = PUNCT ? punct_pick<ENV>(sc) : PunctPick{0.0f, 0.0f};
-    const float inv_nl = rect_inv_nl<ENV, PUNCT>(sc, pk);
+    const PunctPick pk = PUNCT ? punct_pick<FORM>(sc) : PunctPick{0.0f, 0.0f};
+    const float inv_nl = rect_inv_nl<FORM>(sc, pk);
     const int min_batch = 64 - refill;
     uint32_t n_nodes = 0, n_tris = 0, s_nodes = 0, s_tris = 0;
     uint32_t w_steps = 0, w_live = 0, w_node = 0, w_tri = 0;
@@ -2486,7 +2472,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(LPT
                 const float4 d4 = make_float4(rs.d.x, rs.d.y, rs.d.z, __uint_as_float(vslot));
                 const float4 T4 = make_float4(T.x, T.y, T.z, __uint_as_float(pxy));
                 const float4 h4 = make_float4(rs.best.t, rs.best.u, rs.best.v, __uint_as_float(rs.best.prim));
-                shade_hit<GBUF, ENV, PUNCT>(sc, ev, p, s_lut, bounce, bounce + 1u >= nb, seed0 + bounce + 1u, inv_nl, pk, d4, T4, h4,
+                shade_hit<FORM>(sc, ev, p, s_lut, bounce, bounce + 1u >= nb, seed0 + bounce + 1u, inv_nl, pk, d4, T4, h4,
                                 [&]() { return make_float4(rs.o.x, rs.o.y, rs.o.z, pdf); },
                                 [&](float r, float g, float b) { L.x = L.x + r; L.y = L.y + g; L.z = L.z + b; },
                                 [&]() { return ShadeCold{sc, probe, nz, gb}; }, so);

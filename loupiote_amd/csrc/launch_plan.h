@@ -1,8 +1,11 @@
-// Which kernels a wavefront runs, and with which grids: one host-side decision (plan_wavefront) that device.hip's wavefront_prepare consumes.  Plain C++17, nothing from HIP:
-// tests/tools/plan_check.cpp compiles it with g++ and tests/test_launch_plan.py checks the rules below on a CPU.  Every plan gives the same frame bit for bit.
+// Which kernels a wavefront runs — the k_trace form by name (TraceVariant), the k_shade and k_path forms as words (kernel_forms.h) — and with which grids: one host-side
+// decision (plan_wavefront) that device.hip's wavefront_prepare consumes.  Plain C++17, nothing from HIP: tests/tools/plan_check.cpp compiles it with g++ and
+// tests/test_launch_plan.py checks the rules below on a CPU.  Every plan gives the same frame bit for bit.
 #pragma once
 #include <algorithm>
 #include <cstdint>
+
+#include "kernel_forms.h"
 
 constexpr uint32_t kStepBudget = 48u, kBudgetRays = 3000000u;  // defaults of LPT_EXP_STEP_BUDGET / LPT_EXP_BUDGET_RAYS (measured: profiles/r04_experiments_ab.txt H)
 constexpr uint32_t kPathRays = 120000u;           // rays of a wavefront up to which the path kernel is used: the measured cross-over against the per-bounce launches with their tails in place
@@ -17,7 +20,7 @@ struct LaunchTuning {
     // wavefronts of at most this many rays run every bounce behind the primary hits in ONE launch (k_path: no chip-wide barrier per
     // bounce); larger ones take the per-bounce launches, whose drains are then a few per cent.  LPT_OPT_PATH_RAYS; 0: never
     uint32_t path_rays = kPathRays;
-    uint32_t path_waves_per_cu = 16;   // k_path: 4 waves per SIMD (kernels.h LPT_PATH_WAVES)
+    uint32_t path_waves_per_cu = 16;   // k_path: 4 waves per SIMD (kernel_forms.h path_waves)
     int path_refill = 32;              // k_path: a batch of lanes is shaded (and idle lanes start new paths) when at most this many lanes are tracing
     int refill = 44;                   // k_trace: the lanes of a wave refill from the queue when at most this many are tracing (LPT_EXP_REFILL)
     // k_shade grid, blocks per CU (LPT_EXP_SHADE_BLOCKS_PER_CU); 0 = by the submission: 4 (what is resident at 4 waves / SIMD; 8: a 1/8 shard 1.89 instead of 1.80 ms) for a
@@ -47,6 +50,7 @@ struct WavefrontFacts {
     bool stats = false, denoise = false;
     bool masked = false, trans = false, punct = false, env = false;   // SPEC §20, §21, §19, §18
     bool emis = false;                // SPEC §22: an emissive material is in use
+    bool esamp = false;               // SPEC §23: the renderer's switch is on, `emis`, and the scene has an emitter distribution
     bool nmap = false;                // SPEC §24: a normal-mapped material is in use
     bool lens = false;                // SPEC §25: the renderer's lens is open (R > 0): every primary ray has an origin of its own
     bool glass_shadow = false;        // SPEC §27: the renderer's switch is on, the scene has punctual lights and a thin-walled transmissive triangle
@@ -61,6 +65,8 @@ enum class TraceVariant : uint8_t { Lane, Pipe, Stats, StatsPipe, Tail, PipeTail
 
 struct LaunchPlan {
     TraceVariant variant = TraceVariant::Lane;
+    uint32_t shade_form = 0, shade_form0 = 0;   // k_shade<FORM> of the bounces >= 1 / of bounce 0 (kernel_forms.h)
+    uint32_t path_form = 0;                     // k_path<FORM, stats> where `path`, else 0
     bool pipe = false, packet = false, coop_all = false, path = false;
     bool occ_probe = false;       // the occluder-cache probe rides along (where the renderer has its table)
     bool stats_lds_pad = false;   // k_trace<STATS>: 64 bytes of LDS behind the stacks (the steps-per-ray histogram)
@@ -72,23 +78,28 @@ struct LaunchPlan {
 
 // The rules (the expressions below are their only statement in code; the SPEC sections say why):
 //
-//   fact / knob                          | excludes                                                        | where
-//   -------------------------------------+-----------------------------------------------------------------+-----------
-//   masked (alpha-masked materials)      | pipe, packet, tail, budget, occluder probe, coop-all, path:     | SPEC §20
-//                                        | k_trace<STATS, false, false, MASK> alone asks the mask          |
-//   glass_shadow (punctual shadow rays   | what masked excludes — pipe, packet, tail, budget, occluder      | SPEC §27
-//   pass thin panes)                     | probe, coop-all, path —: k_trace_glass<STATS> alone asks the    |
-//                                        | pane (and §20's mask, where the scene has one)                  |
-//   stats                                | tail, budget, coop-all (a ray dropped at the budget would be    | DESIGN §5.5
-//                                        | missing from the histogram and counted twice by the re-trace)   |
-//   trans (a transmissive material used) | path (k_path's instantiations do not double); k_shade<.., TRANS>| SPEC §21
-//   emis (an emissive material used)     | path (k_path's instantiations do not double); k_shade<.., EMIS> | SPEC §22
-//   nmap (a normal-mapped material used) | path (k_path's instantiations do not double); k_shade<.., NMAP> | SPEC §24
-//   lens (the lens radius R > 0)         | packet, path: k_trace_packet rests on ONE origin per packet and  | SPEC §25
-//                                        | k_path reads the shared origin; k_raygen<.., LENS> fills q.o    |
-//   coop-all (n_rays <= coop_rays)       | path                                                            | DESIGN §5.5
-//   tail (solo, n_rays <= budget_rays)   | budget (nothing is dropped, so nothing to re-trace)             | DESIGN §5.5
-//   env, punct                           | nothing: they pick the ENV / PUNCT forms of k_shade and k_path  | SPEC §18, §19
+//   fact / knob                          | excludes                                                        | picks                          | where
+//   -------------------------------------+-----------------------------------------------------------------+--------------------------------+-----------
+//   masked (alpha-masked materials)      | pipe, packet, tail, budget, occluder probe, coop-all, path:     | TraceVariant::Mask / StatsMask | SPEC §20
+//                                        | k_trace<STATS, false, false, MASK> alone asks the mask          |                                |
+//   glass_shadow (punctual shadow rays   | what masked excludes — pipe, packet, tail, budget, occluder      | TraceVariant::Glass /          | SPEC §27
+//   pass thin panes)                     | probe, coop-all, path —: k_trace_glass<STATS> alone asks the    | StatsGlass                     |
+//                                        | pane (and §20's mask, where the scene has one)                  |                                |
+//   stats                                | tail, budget, coop-all (a ray dropped at the budget would be    | TraceVariant::Stats*;          | DESIGN §5.5
+//                                        | missing from the histogram and counted twice by the re-trace)   | k_path<.., STATS>              |
+//   denoise                              | nothing                                                         | kShadeGbuf in shade_form0 and  | SPEC §15.1
+//                                        |                                                                 | path_form                      |
+//   env, punct                           | nothing                                                         | kShadeEnv, kShadePunct in the  | SPEC §18, §19
+//                                        |                                                                 | shade forms and path_form      |
+//   trans (a transmissive material used) | path (k_path's instantiations do not double)                    | kShadeTrans in the shade forms | SPEC §21
+//   emis (an emissive material used)     | path (k_path's instantiations do not double)                    | kShadeEmis in the shade forms  | SPEC §22
+//   esamp (emitter sampling; with emis)  | nothing (emis has excluded the path kernel)                     | kShadeEsamp in the shade forms,| SPEC §23
+//                                        |                                                                 | only where emis                |
+//   nmap (a normal-mapped material used) | path (k_path's instantiations do not double)                    | kShadeNmap in the shade forms  | SPEC §24
+//   lens (the lens radius R > 0)         | packet, path: k_trace_packet rests on ONE origin per packet and  | k_raygen<.., LENS>, which      | SPEC §25
+//                                        | k_path reads the shared origin                                  | fills q.o                      |
+//   coop-all (n_rays <= coop_rays)       | path                                                            |                                | DESIGN §5.5
+//   tail (solo, n_rays <= budget_rays)   | budget (nothing is dropped, so nothing to re-trace)             | TraceVariant::Tail / PipeTail  | DESIGN §5.5
 //
 // Without any of these facts the plan is the default launches of every frame before the feature.
 inline LaunchPlan plan_wavefront(const LaunchTuning &t, const WavefrontFacts &f) {
@@ -143,5 +154,10 @@ inline LaunchPlan plan_wavefront(const LaunchTuning &t, const WavefrontFacts &f)
                : pl.tail  ? (pl.pipe ? TraceVariant::PipeTail : TraceVariant::Tail)
                : f.stats  ? (pl.pipe ? TraceVariant::StatsPipe : TraceVariant::Stats)
                           : (pl.pipe ? TraceVariant::Pipe : TraceVariant::Lane);
+    // the shading forms: a bit per fact; bounce 0 of a denoising frame also writes the G-buffer, and k_path exists in the forms of GBUF | ENV | PUNCT alone
+    const uint32_t lights = (f.env ? kShadeEnv : 0u) | (f.punct ? kShadePunct : 0u);
+    pl.shade_form = lights | (f.trans ? kShadeTrans : 0u) | (f.emis ? kShadeEmis : 0u) | (f.emis && f.esamp ? kShadeEsamp : 0u) | (f.nmap ? kShadeNmap : 0u);
+    pl.shade_form0 = pl.shade_form | (f.denoise ? kShadeGbuf : 0u);
+    pl.path_form = pl.path ? (lights | (f.denoise ? kShadeGbuf : 0u)) : 0u;
     return pl;
 }

@@ -12,7 +12,10 @@ The references, both bit for bit:
  * tests/golden/shade_kernargs_frames.json: SHA-256 of the frames the library gave BEFORE the change (written by tests/golden/make_shade_kernargs.py on an MI355X with
    the parent commit's library), for every form: plain, GBUF, ENV, PUNCT, TRANS, EMIS, EMIS + ESAMP, NMAP.  The oracle has no §18 - §24, and k_path no TRANS / EMIS /
    NMAP form, so for those the library's own earlier output is the only bit-exact reference there is; a frame is keyed by pixel slot and does not depend on the grid
-   or on the order of the queues, so the digests hold on any device."""
+   or on the order of the queues, so the digests hold on any device.
+
+`combined` came with the form words (kernel_forms.h): the one case whose word has several bits, ENV | PUNCT | TRANS | EMIS | ESAMP | NMAP, held to the frame of the
+library before k_shade's seven bools became that word."""
 import functools
 import hashlib
 import json
@@ -28,7 +31,7 @@ from oracle import harness
 from test_gpu_emissive import STAGES
 from test_gpu_emitter_sampling import BLACK, CAM, ERig, lamp_floor
 from test_gpu_normal_map import DIR as FLOOR_DIR, EYE as FLOOR_EYE, VFOV as FLOOR_VFOV, floor_scene, image4
-from test_gpu_transmission import DIR as PANE_DIR, EYE as PANE_EYE, VFOV as PANE_VFOV, pane_scene
+from test_gpu_transmission import DIR as PANE_DIR, EYE as PANE_EYE, VFOV as PANE_VFOV, add_rect, pane_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -49,10 +52,21 @@ def _cornell():
     return s
 
 
+def _lamp_and_pane(s):
+    """onto the floor scene: an emissive quad above the floor, facing down, and a half-transmissive thin pane 0.7 in front of FLOOR_EYE, across the middle of the view"""
+    lamp = s.add_material((0.0, 0.0, 0.0, 1.0), 1.0, 0.0)
+    s.set_material_emission(lamp, (1.0, 0.9, 0.7), 6.0)
+    add_rect(s, (0.5, 1.2, -1.5), (1, 0, 0), (0, 0, 1), 0.3, 0.3, lamp)
+    glass = s.add_material((0.5, 1.0, 0.25, 1.0), 0.3, 0.0)
+    s.set_material_transmission(glass, 0.5, 1.5, True)
+    add_rect(s, (0.11, 0.505, -0.295), (1, 0, 0), (0, 0.7071, -0.7071), 0.2, 0.15, glass)
+
+
 CORNELL_CAM = dict(eye=T.CORNELL_EYE, direction=T.CORNELL_DIR, vfov=T.VFOV)
 FLOOR_CAM = dict(eye=FLOOR_EYE, direction=FLOOR_DIR, vfov=FLOOR_VFOV)
 PANE_CAM = dict(eye=PANE_EYE, direction=PANE_DIR, vfov=PANE_VFOV)
-# form -> (scene, probe, camera, what else the rig gets; `size` / `spp`: instead of SIZE / SPP).  One flag of k_shade per case (GBUF: a denoising mode, whose bounce 0 is the GBUF form)
+# form -> (scene, probe, camera, what else the rig gets; `size` / `spp`: instead of SIZE / SPP).  One flag of k_shade per case (GBUF: a denoising mode, whose bounce 0 is the GBUF form),
+# and `combined`: every flag but GBUF
 CASES = {
     "plain": (_cornell, GREY, CORNELL_CAM, {}),
     "gbuf": (_cornell, GREY, CORNELL_CAM, dict(mode=lp.BlitMode.DenoisedPathrace, size=(512, 288), spp=1)),      # a denoised frame is one sample per pixel: the same 147 456 rays
@@ -62,6 +76,7 @@ CASES = {
     "emis": (lambda: lamp_floor(walls=True), BLACK, CAM, dict(sampling=False)),
     "emis_esamp": (lambda: lamp_floor(walls=True), BLACK, CAM, dict(sampling=True)),
     "nmap": (lambda: floor_scene(image4(), light=False), GREY, FLOOR_CAM, {}),
+    "combined": (lambda: floor_scene(image4(), extra=_lamp_and_pane), PROBE_ENV, FLOOR_CAM, dict(env=True, sampling=True)),
 }
 
 

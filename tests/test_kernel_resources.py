@@ -22,7 +22,7 @@ TOOLS = ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")
 FIELDS = ("name", "sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count", "agpr_count", "private_segment_fixed_size")
 
 # the instantiations bench.py's frame launches (mangled-name prefixes: the argument types follow)
-K_SHADE = "_ZN4lptd7k_shadeILb0ELb0ELb0ELb0ELb0ELb0ELb0EE"      # k_shade<false x 7>
+K_SHADE = "_ZN4lptd7k_shadeILj0EE"                                # k_shade<0u>: no feature bit (kernel_forms.h)
 K_PACKET = "_ZN4lptd14k_trace_packetILb0EE"                       # k_trace_packet<false>
 K_TRACE = "_ZN4lptd7k_traceILb0ELb1ELb0ELb0EE"                    # k_trace<false, true, false, false>
 
@@ -76,8 +76,14 @@ def one(kernels, prefix):
 def test_k_shade_of_the_bench_frame_spills_nothing_and_keeps_four_waves(kernels):
     k = one(kernels, K_SHADE)
     assert k["sgpr_spill_count"] == 0
-    assert k["vgpr_count"] <= 128          # 4 waves per SIMD (LPT_SHADE_WAVES)
+    assert k["vgpr_count"] <= 128          # 4 waves per SIMD (kernel_forms.h shade_waves)
     assert k["private_segment_fixed_size"] == 0
+
+
+def test_the_shading_kernels_exist_in_their_valid_forms_and_no_others(kernels):
+    # kernel_forms.h: 96 of k_shade's 128 words are valid (ESAMP only with EMIS), k_path's 8 words with STATS off and on
+    assert len([k for k in kernels if k.startswith("_ZN4lptd7k_shadeI")]) == 96
+    assert len([k for k in kernels if k.startswith("_ZN4lptd6k_pathI")]) == 16
 
 
 def test_k_trace_packet_of_the_bench_frame_keeps_eight_waves(kernels):

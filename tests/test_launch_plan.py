@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "loupiote_amd", "csrc")
 VARIANTS = {"0000", "0100", "1000", "1100", "0010", "0110", "0001", "1001"}   # (STATS, PIPE, TAIL, MASK): the k_trace instantiations that exist
 MAX_RAYS = 0x7FFFFFFF
+GBUF, ENV, PUNCT, TRANS, EMIS, ESAMP, NMAP = (1 << i for i in range(7))   # kernel_forms.h: the bits of a k_shade / k_path form
 DEFAULT_COOP_RAYS, DEFAULT_PATH_RAYS = 32000, 120000
 
 
@@ -76,6 +77,7 @@ def test_named_cases(plan):
         return all(not p[n] for n in names)
     # one half of the bench frame: 4 147 200 rays / 160 = 25 920 waves wanted, 24 per CU allowed; 16 200 shading blocks wanted, 3 per CU for a piece
     assert bench_half["variant"] == "0100" and bench_half["packet"] and bench_half["quad_slots"] == 1036800
+    assert (bench_half["shade_form"], bench_half["shade_form0"], bench_half["path_form"]) == (0, 0, 0) and bench_half["variant_name"] == "Pipe"   # k_shade<0u> on every bounce
     assert off(bench_half, "tail", "budget", "coop_all", "path")
     assert (bench_half["trace_blocks"], bench_half["shade_blocks"], bench_half["stream_blocks"]) == (6144, 768, 2048)
     # a solo 1/8 shard: 1 036 800 rays / 160 = 6480 waves wanted; the tail in place, so no budget
@@ -122,3 +124,30 @@ def test_the_exclusion_rules_hold_over_a_sweep(plan):
         assert 1 <= p["trace_blocks"] <= div_up(c["n_rays"], 64), (c, p)
         assert p["trace_waves"] % 8 == 0 and p["trace_waves"] >= 8 and p["trace_blocks"] == min(div_up(c["n_rays"], 64), p["trace_waves"]), (c, p)
         assert bool(p["coop_blocks"]) == bool(p["coop_all"] or p["budget"]) and bool(p["path_blocks"]) == bool(p["path"]) and bool(p["packet_blocks"]) == bool(p["packet"]), (c, p)
+
+
+def test_the_shading_forms_are_the_facts_bits(plan):
+    """kernel_forms.h's words as plan_wavefront states them, over every combination of the facts that pick a shading kernel, at a size that takes coop-all (9216 rays),
+    one that takes the path kernel (65 536) and the full bench frame's"""
+    facts = ("denoise", "env", "punct", "trans", "emis", "esamp", "nmap", "stats")
+    bit = dict(env=ENV, punct=PUNCT, trans=TRANS, emis=EMIS, nmap=NMAP)
+    sizes = (frame(64, 36, 4), frame(256, 256, 1), frame(3840, 2160, 1))
+    assert [s["n_rays"] for s in sizes] == [9216, 65536, 8294400]
+    cases = [dict(s, solo=1, **dict(zip(facts, bits))) for s in sizes for bits in itertools.product((0, 1), repeat=len(facts))]
+    out = plan(cases)
+    assert len(out) == 3 * 2 ** 8
+    seen = set()
+    for c, p in zip(cases, out):
+        want = sum(b for k, b in bit.items() if c[k]) | (ESAMP if c["emis"] and c["esamp"] else 0)
+        assert p["shade_form"] == want, (c, p)
+        assert p["shade_form0"] == want | (GBUF if c["denoise"] else 0), (c, p)
+        for form in (p["shade_form"], p["shade_form0"]):   # shade_form_valid
+            assert form < 128 and (not form & ESAMP or form & EMIS), (c, p)
+        if p["path"]:
+            assert p["path_form"] == (GBUF if c["denoise"] else 0) | (ENV if c["env"] else 0) | (PUNCT if c["punct"] else 0), (c, p)
+            assert not p["shade_form"] & (TRANS | EMIS | NMAP), (c, p)
+        else:
+            assert p["path_form"] == 0, (c, p)
+        seen.add((c["n_rays"], bool(p["coop_all"]), bool(p["path"])))
+    # the three sizes are what they are chosen for (stats keeps a tiny wavefront off coop-all, and it then takes the path kernel)
+    assert {(9216, True, False), (65536, False, True), (8294400, False, False)} <= seen and not any(n == 8294400 and (co or pa) for n, co, pa in seen)

@@ -1,7 +1,7 @@
-"""Host logic: SPEC.md §27's fact in the launch plan (loupiote_amd/csrc/launch_plan.h plan_wavefront), checked on the CPU through tests/tools/plan_glass_check.cpp.
+"""Host logic: SPEC.md §27's fact in the launch plan (loupiote_amd/csrc/launch_plan.h plan_wavefront), checked on the CPU through tests/tools/plan_check.cpp.
 `glass_shadow` excludes what `masked` excludes — pipe, packet, tail, budget, occluder probe, coop-all, path — at every size class and picks k_trace_glass<STATS>;
-with the fact false the plan is the plan of a case that never names the field, field for field, and that plan is what tests/tools/plan_check.cpp (which does
-not know the field) prints for the same case."""
+with the fact false the plan is the plan of a case that never names the field, field for field, and its kernel is one of the eight k_trace
+instantiations, by name what the bit string says."""
 import itertools
 import json
 import os
@@ -34,14 +34,13 @@ def _run(exe, limits, cases):
 
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory, limits):
-    exe = _build(tmp_path_factory, "plan_glass_check.cpp")
+    exe = _build(tmp_path_factory, "plan_check.cpp")
     return lambda cases: _run(exe, limits, cases)
 
 
 @pytest.fixture(scope="module")
-def old_plan(tmp_path_factory, limits):
-    exe = _build(tmp_path_factory, "plan_check.cpp")
-    return lambda cases: _run(exe, limits, cases)
+def old_plan(plan):
+    return plan   # one driver since it knows every fact: the case that never names the field, by the bit strings of the eight k_trace instantiations
 
 
 def _sweep():
@@ -58,12 +57,12 @@ def test_glass_shadow_excludes_what_masked_excludes_at_every_size(plan):
     as_masked = plan([dict(c, masked=1) for c in cases])
     assert len(on) == len(RAYS) * 32 * 3 * 2 * 2 * 3
     for c, p, m in zip(cases, on, as_masked):
-        assert p["variant"] == ("StatsGlass" if c["stats"] else "Glass"), (c, p)
+        assert p["variant_name"] == ("StatsGlass" if c["stats"] else "Glass"), (c, p)
         assert not any(p[k] for k in EXCLUDED), (c, p)
         assert p["stats_lds_pad"] == c["stats"], (c, p)
         # everything but the kernel's name is the masked scene's plan: the same step, the same grids
         assert {k: v for k, v in p.items() if not k.startswith("variant")} == {k: v for k, v in m.items() if not k.startswith("variant")}, (c, p, m)
-        assert m["variant"] == ("StatsMask" if c["stats"] else "Mask")
+        assert m["variant_name"] == ("StatsMask" if c["stats"] else "Mask")
 
 
 def test_with_the_fact_false_the_plan_is_the_plan_without_the_field(plan, old_plan):
@@ -71,7 +70,7 @@ def test_with_the_fact_false_the_plan_is_the_plan_without_the_field(plan, old_pl
     unset, off, before = plan(cases), plan([dict(c, glass_shadow=0) for c in cases]), old_plan(cases)
     assert unset == off
     for c, p, b in zip(cases, unset, before):
-        assert p["variant"] == CODES[b["variant"]] and p["variant_index"] < 8, (c, p, b)
+        assert p["variant_name"] == CODES[b["variant"]] and p["variant_index"] < 8, (c, p, b)
         for k, v in b.items():
             if k not in ("variant", "same_again"):
                 assert p[k] == v, (k, c, p, b)
@@ -81,7 +80,7 @@ def test_named_cases(plan):
     shard = dict(frame(1920, 1080, 4, parts=8), solo=1, punct=1, trans=1)
     tiny = dict(frame(64, 64, 16), solo=1, punct=1, trans=1)
     a, b, c, d = plan([dict(shard, glass_shadow=1), shard, dict(tiny, glass_shadow=1), tiny])
-    assert a["variant"] == "Glass" and a["tail"] == 0 and b["variant"] == "PipeTail" and b["tail"] == 4 and b["packet"]
+    assert a["variant_name"] == "Glass" and a["tail"] == 0 and b["variant_name"] == "PipeTail" and b["tail"] == 4 and b["packet"]
     # 64 x 64 x 16 = 65 536 rays: 409 waves wanted, at least 8 per CU (2048) taken, capped by one wave per 64 rays (1024)
-    assert c["variant"] == "Glass" and c["trace_blocks"] == min(1024, 256 * 8) and not c["path"] and not c["coop_all"]
-    assert d["variant"] == "PipeTail"
+    assert c["variant_name"] == "Glass" and c["trace_blocks"] == min(1024, 256 * 8) and not c["path"] and not c["coop_all"]
+    assert d["variant_name"] == "PipeTail"

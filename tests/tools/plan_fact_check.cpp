@@ -10,17 +10,17 @@
 
 #include "../../loupiote_amd/csrc/launch_plan.h"
 
-struct Fact { const char *name; bool WavefrontFacts::*field; int flag_bits; bool packet_knob, removes_packet; };
-static const Fact kFacts[] = {{"emis", &WavefrontFacts::emis, 7, false, false}, {"nmap", &WavefrontFacts::nmap, 8, false, false}, {"lens", &WavefrontFacts::lens, 9, true, true}};
+struct Fact { const char *name; bool WavefrontFacts::*field; int flag_bits; bool packet_knob, removes_packet; uint32_t bit; };   // bit: what the fact sets in the k_shade forms
+static const Fact kFacts[] = {{"emis", &WavefrontFacts::emis, 7, false, false, kShadeEmis}, {"nmap", &WavefrontFacts::nmap, 8, false, false, kShadeNmap}, {"lens", &WavefrontFacts::lens, 9, true, true, 0u}};
 
-// every field none of these facts may move
-static bool same_rest(const LaunchPlan &a, const LaunchPlan &b) {
-    return a.variant == b.variant && a.pipe == b.pipe && a.coop_all == b.coop_all && a.occ_probe == b.occ_probe && a.stats_lds_pad == b.stats_lds_pad && a.tail == b.tail &&
+// every field none of these facts may move; of the shading forms, `own` is the one bit the fact sets in shade_form and shade_form0 (0: none), path_form apart (same_path)
+static bool same_rest(const LaunchPlan &a, const LaunchPlan &b, uint32_t own = 0u) {
+    return (a.shade_form | own) == (b.shade_form | own) && (a.shade_form0 | own) == (b.shade_form0 | own) && a.variant == b.variant && a.pipe == b.pipe && a.coop_all == b.coop_all && a.occ_probe == b.occ_probe && a.stats_lds_pad == b.stats_lds_pad && a.tail == b.tail &&
            a.budget == b.budget && a.trace_waves == b.trace_waves && a.stream_blocks == b.stream_blocks && a.shade_blocks == b.shade_blocks && a.trace_blocks == b.trace_blocks &&
            a.coop_blocks == b.coop_blocks && a.stack_lds == b.stack_lds;
 }
 static bool same_packet(const LaunchPlan &a, const LaunchPlan &b) { return a.packet == b.packet && a.packet_blocks == b.packet_blocks && a.packet_lds == b.packet_lds && a.quad_slots == b.quad_slots; }
-static bool same_path(const LaunchPlan &a, const LaunchPlan &b) { return a.path == b.path && a.path_blocks == b.path_blocks; }
+static bool same_path(const LaunchPlan &a, const LaunchPlan &b) { return a.path == b.path && a.path_blocks == b.path_blocks && a.path_form == b.path_form; }
 
 int main(int argc, char **argv) {
     const Fact *fact = nullptr;
@@ -63,7 +63,8 @@ int main(int argc, char **argv) {
                             return 1;
                         }
                         const bool packet_ok = fact->removes_packet ? (!on.packet && on.packet_blocks == 0u && on.packet_lds == 0u && on.quad_slots == 0u) : same_packet(off, on);
-                        if (on.path || on.path_blocks != 0u || !packet_ok || !same_rest(off, on)) {
+                        const bool bit_ok = (on.shade_form & ~off.shade_form) == fact->bit && (on.shade_form0 & ~off.shade_form0) == fact->bit && on.path_form == 0u;
+                        if (on.path || on.path_blocks != 0u || !packet_ok || !bit_ok || !same_rest(off, on, fact->bit)) {
                             std::fprintf(stderr, "%s = true: packet %d, path %d, blocks %u / %u, packet_lds %u, quad_slots %u, or another field moved: n_rays %u flags %d path_rays %u coop_rays %u packet_primary %u\n",
                                          fact->name, (int)on.packet, (int)on.path, on.packet_blocks, on.path_blocks, on.packet_lds, on.quad_slots, n_rays, flags, path_rays, coop_rays, packet_primary);
                             return 1;

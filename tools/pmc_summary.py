@@ -8,9 +8,13 @@ from collections import defaultdict
 
 def short(name):
     # k_trace<STATS, PIPE, TAIL>: keyed by the first template argument (the STATS variant is a different kernel for the averages)
-    m = re.search(r"lptd::(k_[a-z_]+)(<(true|false)(, (true|false))*>)?", name)
+    # k_shade<FORM>, k_path<FORM, STATS>: keyed by the word's GBUF bit (kernel_forms.h kShadeGbuf), which was their first template argument — the keys of earlier traces
+    m = re.search(r"lptd::(k_[a-z_]+)(<(true|false|\d+u?)(, (true|false))*>)?", name)
     if m:
-        return m.group(1) + ("<%s>" % m.group(3) if m.group(3) else "")
+        first = m.group(3)
+        if first and first[0].isdigit():
+            first = "true" if int(first.rstrip("u")) & 1 else "false"
+        return m.group(1) + ("<%s>" % first if first else "")
     return name[:40]
 
 
