@@ -145,6 +145,16 @@ impl Scene {
         check(unsafe { ffi::lpt_scene_get_material_transmission(self.h, material, &mut factor, &mut ior, &mut thin) })?;
         Ok((factor, ior, thin != 0))
     }
+    /// SPEC.md §28: volume attenuation (glTF attenuationColor / attenuationDistance) of a solid transmissive material; colour (1, 1, 1) or `f32::INFINITY`: none
+    pub fn set_material_attenuation(&mut self, material: u32, color: [f32; 3], distance: f32) -> Result<(), Error> {
+        check(unsafe { ffi::lpt_scene_set_material_attenuation(self.h, material, color.as_ptr(), distance) })
+    }
+    /// -> (color, distance, sigma)
+    pub fn material_attenuation(&self, material: u32) -> Result<([f32; 3], f32, [f32; 3]), Error> {
+        let (mut color, mut distance, mut sigma) = ([0f32; 3], 0f32, [0f32; 3]);
+        check(unsafe { ffi::lpt_scene_get_material_attenuation(self.h, material, color.as_mut_ptr(), &mut distance, sigma.as_mut_ptr()) })?;
+        Ok((color, distance, sigma))
+    }
     /// SPEC.md §22: emissive materials; `Le = factor x strength` per channel, times the sRGB emissive `image` where one is given; a product of 0: non-emissive again
     pub fn set_material_emission(&mut self, material: u32, factor: [f32; 3], strength: f32, image: Option<u32>) -> Result<(), Error> {
         check(unsafe { ffi::lpt_scene_set_material_emission(self.h, material, factor.as_ptr(), strength, image.unwrap_or(ffi::LPT_INVALID_INDEX)) })

@@ -4,6 +4,7 @@
 // Result<_, Error> are thrown as loupiote::Error (kind mirrors errors.rs:2-6).
 #pragma once
 #include <array>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -105,6 +106,16 @@ class Scene {  // scene.rs:30-54
         check(lpt_scene_get_material_transmission(h_, material, &t.factor, &t.ior, &thin));
         t.thin_walled = thin != 0;
         return t;
+    }
+    // SPEC.md §28: volume attenuation (glTF attenuationColor / attenuationDistance) of a solid transmissive material; colour (1, 1, 1) or distance +inf: none
+    struct MaterialAttenuation { float color[3]; float distance; float sigma[3]; };
+    void set_material_attenuation(uint32_t material, const float color[3], float distance = std::numeric_limits<float>::infinity()) {
+        check(lpt_scene_set_material_attenuation(h_, material, color, distance));
+    }
+    MaterialAttenuation material_attenuation(uint32_t material) const {
+        MaterialAttenuation a{};
+        check(lpt_scene_get_material_attenuation(h_, material, a.color, &a.distance, a.sigma));
+        return a;
     }
     // SPEC.md §22: emissive materials; Le = factor x strength per channel, times the sRGB emissive image where one is given; a product of 0: non-emissive again
     struct MaterialEmission { float le[3]; uint32_t image; };
@@ -212,6 +223,10 @@ class SceneGPU {  // scene.rs:56-64,151-188
     // SPEC.md §27: what a punctual light's shadow ray along dirs is answered at (prim, bary) by the traversal's own function, out[n][8] (lpt.h), for tools and tests
     void glass_shadow(const Device &device, uint32_t n, const uint32_t *prim, const float *bary, const float *dirs, float *out) const {
         check(lpt_scene_gpu_glass_shadow(device.inner(), h_, n, prim, bary, dirs, out));
+    }
+    // SPEC.md §28: the volume attenuation of a hit of prim along dirs at distance t by the shading kernels' own function, out[n][4] (lpt.h), for tools and tests
+    void attenuation(const Device &device, uint32_t n, const uint32_t *prim, const float *dirs, const float *t, float *out) const {
+        check(lpt_scene_gpu_attenuation(device.inner(), h_, n, prim, dirs, t, out));
     }
     void sample_emitter(const Device &device, uint32_t n, const float *points, const float *rands, uint32_t *prim, uint32_t *sampled, float *y, float *wi, float *dist, float *cl,
                         float *p_a, float *E) const {

@@ -293,6 +293,16 @@ int lpt_scene_set_material_alpha_blend(lpt_scene *scene, uint32_t material_index
 int lpt_scene_set_material_transmission(lpt_scene *scene, uint32_t material_index, float factor, float ior, uint32_t thin_walled);
 int lpt_scene_get_material_transmission(const lpt_scene *scene, uint32_t material_index, float *factor, float *ior, uint32_t *thin_walled);
 
+/* build-only extension (SPEC.md §28; the reference's loader reads no KHR_materials_volume): volume attenuation, glTF's
+ * KHR_materials_volume.attenuationColor and .attenuationDistance.  Kept beside the transmission state and independent of it (factor 0 and
+ * back keeps it); default colour (1, 1, 1) and distance +inf, which is none.  It acts only while the material is transmissive and solid
+ * (factor > 0, thin_walled 0): a path segment that ends on the inside of the solid's own face is scaled per channel by exp(-sigma_c t),
+ * Beer-Lambert, with sigma_c = -log(color[c]) / distance derived here once (0 for a component of 1 or a distance of +inf, FLT_MAX for a
+ * component of 0 or an overflowing quotient; always finite and >= 0).  LPT_ERR_INVALID_ARG, and nothing changed, for a material index out
+ * of range, a colour component that is non-finite or outside [0, 1], a distance that is NaN or <= 0.  Out-pointers of the getter may be NULL. */
+int lpt_scene_set_material_attenuation(lpt_scene *scene, uint32_t material_index, const float color[3], float distance);
+int lpt_scene_get_material_attenuation(const lpt_scene *scene, uint32_t material_index, float color[3], float *distance, float sigma[3]);
+
 /* build-only extension (SPEC.md §22; the reference's loader reads no emissiveFactor): emissive materials.  A third side table beside
  * the 32-byte lpt_material, non-emissive by default.  Le_c = factor[c] * strength (one float product per channel, made here); a path
  * that hits a triangle of the material, from either side and on any bounce, picks up Le — times the sRGB-decoded rgb of `image` at the
@@ -440,6 +450,13 @@ int lpt_scene_gpu_sample_textures(lpt_device *dev, const lpt_scene_gpu *sg, uint
  * xi), 0, 0, 0}; zeros for a triangle that is no thin-walled transmissive pane (opaque, solid glass) and for a degenerate one (xi is
  * still the pane's there).  LPT_ERR_INVALID_ARG for a prim at or beyond the scene's baked triangle count.  Blocking; host arrays. */
 int lpt_scene_gpu_glass_shadow(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *bary, const float *dirs, float *out);
+
+/* build-only extension (SPEC.md §28), for tests and tools in the manner of lpt_scene_gpu_glass_shadow: the volume attenuation the
+ * shading kernels apply to a ray along the unit direction dirs[i] that hits baked triangle prim[i] at distance t[i], by their own function.
+ * out[n][4] = {A_r, A_g, A_b, applies (0 / 1)}; {1, 1, 1, 0} where the rule does not apply: an opaque, thin-walled or non-attenuating
+ * triangle, a degenerate one, a hit on the front of the face.  LPT_ERR_INVALID_ARG for a prim at or beyond the scene's baked triangle count.
+ * Blocking; host arrays. */
+int lpt_scene_gpu_attenuation(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *dirs, const float *t, float *out);
 
 /* build-only extension (SPEC.md §21), for tests and tools in the manner of lpt_probe_sample: the interface event of the shading kernels
  * (kernels.h interface_sample), once per element.  Inputs, n of each: dirs[n][3] the ray's unit direction d, ns[n][3] the shading

@@ -104,6 +104,8 @@ SIGNATURES = {
     "lpt_scene_set_material_alpha_blend": (_i, [_vp, _u32, _u32]),
     "lpt_scene_set_material_transmission": (_i, [_vp, _u32, _f, _f, _u32]),
     "lpt_scene_get_material_transmission": (_i, [_vp, _u32, C.POINTER(_f), C.POINTER(_f), _pu32]),
+    "lpt_scene_set_material_attenuation": (_i, [_vp, _u32, _vp, _f]),
+    "lpt_scene_get_material_attenuation": (_i, [_vp, _u32, _vp, C.POINTER(_f), _vp]),
     "lpt_scene_set_material_emission": (_i, [_vp, _u32, _vp, _f, _u32]),
     "lpt_scene_get_material_emission": (_i, [_vp, _u32, _vp, _pu32]),
     "lpt_scene_set_material_normal_map": (_i, [_vp, _u32, _u32, _f]),
@@ -136,6 +138,7 @@ SIGNATURES = {
     "lpt_scene_gpu_shading_normal": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "lpt_scene_gpu_sample_textures": (_i, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "lpt_scene_gpu_glass_shadow": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "lpt_scene_gpu_attenuation": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "lpt_interface_sample": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lpt_bsdf_probe": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "lpt_probe_upload": (_i, [_vp, _vp, _u32, _u32, _pvp]),

@@ -256,6 +256,19 @@ class Scene:
         _check(A.lib().lpt_scene_get_material_transmission(self._h, int(material_index), C.byref(factor), C.byref(ior), C.byref(thin)))
         return float(factor.value), float(ior.value), bool(thin.value)
 
+    # SPEC §28: volume attenuation; beside the transmission state and independent of it, none (colour 1, distance +inf) by default
+    def set_material_attenuation(self, material_index, color, distance=float("inf")):
+        """glTF's attenuationColor / attenuationDistance: while the material is transmissive and solid (not thin-walled), a path segment that ends on the
+        inside of the solid's own face is scaled per channel by exp(-sigma t), sigma = -log(color) / distance.  color (1, 1, 1) or distance +inf: none"""
+        c = np.ascontiguousarray(np.broadcast_to(np.asarray(color, np.float32), (3,)))
+        _check(A.lib().lpt_scene_set_material_attenuation(self._h, int(material_index), A.ptr(c), float(distance)))
+
+    def material_attenuation(self, material_index):
+        """-> (color: float32[3], distance, sigma: float32[3], the absorption coefficients derived from them)"""
+        color, distance, sigma = np.zeros(3, np.float32), C.c_float(), np.zeros(3, np.float32)
+        _check(A.lib().lpt_scene_get_material_attenuation(self._h, int(material_index), A.ptr(color), C.byref(distance), A.ptr(sigma)))
+        return color, float(distance.value), sigma
+
     # SPEC §22: emissive materials; a third side table of the materials, non-emissive by default
     def set_material_emission(self, material_index, factor, strength=1.0, image=None):
         """a path that hits a triangle of the material, from either side and on any bounce, picks up Le = factor x strength (x the sRGB-decoded rgb of
@@ -450,6 +463,20 @@ class SceneGPU:
         out = np.zeros((n, 8), np.float32)
         _check(A.lib().lpt_scene_gpu_glass_shadow(self._dev.inner(), self._h, n, A.ptr(pr), A.ptr(ba), A.ptr(di), A.ptr(out)))
         return {"tau": out[:, 0:3].copy(), "xi": out[:, 3].copy(), "bits": out[:, 4].copy().view(np.uint32)}
+
+    def attenuation(self, prim, dirs, t):
+        """The volume attenuation of a hit (SPEC.md §28) by the shading kernels' own function: prim[n], dirs[n, 3] (unit), t[n] (the hit distance) -> a dict of
+        A[n, 3] (float32, the factor per channel) and applies[n] (bool).  (1, 1, 1) and False where the rule does not apply: an opaque, thin-walled or
+        non-attenuating triangle, a degenerate one, a hit on the front of the face."""
+        pr = np.ascontiguousarray(prim, np.uint32).reshape(-1)
+        n = pr.shape[0]
+        di = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        tt = np.ascontiguousarray(t, np.float32).reshape(-1)
+        if di.shape[0] != n or tt.shape[0] != n:
+            raise Error(A.LPT_ERR_INVALID_ARG, "attenuation: one direction and one distance per prim")
+        out = np.zeros((n, 4), np.float32)
+        _check(A.lib().lpt_scene_gpu_attenuation(self._dev.inner(), self._h, n, A.ptr(pr), A.ptr(di), A.ptr(tt), A.ptr(out)))
+        return {"A": out[:, 0:3].copy(), "applies": out[:, 3] != 0}
 
     def sample_emitter(self, points, rands):
         """The emitter sample the shading kernels run (SPEC.md §23) on the GPU: points[n, 3], rands[n, 4] = (ra, rb, r1, r2) -> a dict of prim[n],

@@ -1,6 +1,7 @@
 // common.h — internal declarations shared by the host-side translation units of
 // libloupiote_hip.so.  Nothing here is part of the ABI (include/lpt.h is).
 #pragma once
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
@@ -37,6 +38,20 @@ struct MaterialTransmission {
     uint32_t thin_walled = 1u;
 };
 
+// SPEC §28: a material's volume attenuation, kept beside its transmission state and independent of it; sigma is derived once, here on the host
+struct MaterialAttenuation {
+    float color[3] = {1.0f, 1.0f, 1.0f};
+    float distance = INFINITY;
+    float sigma[3] = {0.0f, 0.0f, 0.0f};   // attenuation_sigma per channel: finite, >= +0
+    bool attenuates() const { return sigma[0] > 0.0f || sigma[1] > 0.0f || sigma[2] > 0.0f; }
+};
+// sigma_c = 0 if c == 1 or D == +inf, else min((float)(-log((double)c) / (double)D), FLT_MAX): c = 0 and an overflowing quotient both give FLT_MAX
+inline float attenuation_sigma(float c, float distance) {
+    if (c == 1.0f || std::isinf(distance)) return 0.0f;
+    const float s = (float)(-std::log((double)c) / (double)distance);
+    return s < FLT_MAX ? s : FLT_MAX;
+}
+
 // SPEC §22: a material's emission, a third side table; Le = 0 in all channels = non-emissive (the default, and no record is kept)
 struct MaterialEmission {
     float le[3] = {0.0f, 0.0f, 0.0f};       // float32(factor_c) * float32(strength), one binary32 product per channel
@@ -67,6 +82,8 @@ struct lpt_scene {
     lpt::MaterialAlpha material_alpha(size_t i) const { return i < alpha.size() ? alpha[i] : lpt::MaterialAlpha(); }
     std::vector<lpt::MaterialTransmission> transmission;   // SPEC §21: side table of `materials`; a material beyond its end is opaque (material_transmission)
     lpt::MaterialTransmission material_transmission(size_t i) const { return i < transmission.size() ? transmission[i] : lpt::MaterialTransmission(); }
+    std::vector<lpt::MaterialAttenuation> attenuation;   // SPEC §28: side table of `materials`; a material beyond its end does not attenuate (material_attenuation)
+    lpt::MaterialAttenuation material_attenuation(size_t i) const { return i < attenuation.size() ? attenuation[i] : lpt::MaterialAttenuation(); }
     std::vector<lpt::MaterialEmission> emission;   // SPEC §22: side table of `materials`; a material beyond its end is non-emissive (material_emission)
     lpt::MaterialEmission material_emission(size_t i) const { return i < emission.size() ? emission[i] : lpt::MaterialEmission(); }
     std::vector<lpt::MaterialNormalMap> normal_map;   // SPEC §24: side table of `materials`; a material beyond its end has no normal map (material_normal_map)

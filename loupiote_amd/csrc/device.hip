@@ -849,7 +849,7 @@ static int upload_punctual(lpt_scene_gpu *sg, const lpt_scene &scene) {
     return LPT_OK;
 }
 
-// SPEC §20, §21, §22, §24: one material side table (material_tables.h) onto the device and into the view the kernels get; the caller has made sure nothing in flight
+// SPEC §20, §21, §22, §24, §28: one material side table (material_tables.h) onto the device and into the view the kernels get; the caller has made sure nothing in flight
 // reads the old tables, and waits for the stream before the host vectors go
 struct DSceneTable { const uint32_t *DScene::*tri; const float4 *DScene::*recs; uint32_t DScene::*n; };
 static const DSceneTable kDSceneTables[MAT_KINDS] = {
@@ -867,7 +867,11 @@ static int commit_table(lpt_scene_gpu *sg, int kind, const MaterialTable &t) {
         return LPT_OK;
     }
     TRY(upload(mem.tri, t.tri, sg->dev->stream));
-    TRY(upload(mem.recs, t.recs, sg->dev->stream));
+    // SPEC §28: the second records (the transmission table's sigma rows) stand behind the first ones, record i's at [n + i] — there only while some record needs one
+    TRY(mem.recs.alloc(sizeof(MaterialRec) * (t.recs.size() + t.more.size())));
+    HIP_TRY(hipMemcpyAsync(mem.recs.get(), t.recs.data(), sizeof(MaterialRec) * t.recs.size(), hipMemcpyHostToDevice, sg->dev->stream));
+    if (!t.more.empty())
+        HIP_TRY(hipMemcpyAsync(mem.recs.get() + sizeof(MaterialRec) * t.recs.size(), t.more.data(), sizeof(MaterialRec) * t.more.size(), hipMemcpyHostToDevice, sg->dev->stream));
     sg->d.*view.tri = as<const uint32_t>(mem.tri);
     sg->d.*view.recs = as<const float4>(mem.recs);
     sg->d.*view.n = (uint32_t)t.recs.size();
@@ -1250,6 +1254,16 @@ int lpt_scene_gpu_glass_shadow(lpt_device *dev, const lpt_scene_gpu *sg, uint32_
     TRY(check_prims("lpt_scene_gpu_glass_shadow", sg->d, prim, n));
     return run_probe(dev, n, kBlock, {{prim, sizeof(uint32_t)}, {bary, sizeof(float[2])}, {dirs, kF3}}, {{out, sizeof(GlassRow)}}, [&](dim3 grid, const DevMem *d) {
         hipLaunchKernelGGL(k_glass_shadow, grid, dim3(kBlock), 0, dev->stream, sg->d, as<const uint32_t>(d[0]), as<const float>(d[1]), as<const float>(d[2]), n, as<GlassRow>(d[3]));
+    });
+}
+
+// SPEC §28: volume_attenuate — what a hit of baked triangle prim[i] by a ray along dirs[i] at distance t[i] does to a throughput of 1 —, once per element.  out[n] is {A rgb, applies}
+int lpt_scene_gpu_attenuation(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t n, const uint32_t *prim, const float *dirs, const float *t, float *out) {
+    if (!dev || !sg || (n && (!prim || !dirs || !t || !out))) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_attenuation: null");
+    if (sg->dev != dev) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_gpu_attenuation: the scene belongs to another device");
+    TRY(check_prims("lpt_scene_gpu_attenuation", sg->d, prim, n));
+    return run_probe(dev, n, kBlock, {{prim, sizeof(uint32_t)}, {dirs, kF3}, {t, sizeof(float)}}, {{out, sizeof(float4)}}, [&](dim3 grid, const DevMem *d) {
+        hipLaunchKernelGGL(k_attenuation, grid, dim3(kBlock), 0, dev->stream, sg->d, as<const uint32_t>(d[0]), as<const float>(d[1]), as<const float>(d[2]), n, as<float4>(d[3]));
     });
 }
 

@@ -285,6 +285,8 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size, uint32_t flags) {
     std::vector<Mask> masks;
     struct Glass { uint32_t material; float factor, ior; uint32_t thin; };
     std::vector<Glass> glasses;
+    struct Tint { uint32_t material; float color[3], distance; };
+    std::vector<Tint> tints;
     struct Emitter { uint32_t material; float factor[3], strength; uint32_t image; };
     std::vector<Emitter> emitters;
     struct Bump { uint32_t material, image; float scale; };
@@ -328,6 +330,26 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size, uint32_t flags) {
             if (factor < 0.0 || factor > 1.0) bad("transmissionFactor outside [0, 1]");
             if (ior < 1.0) bad("ior below 1");
             if (factor > 0.0) glasses.push_back(Glass{(uint32_t)tmp.materials.size() - 1u, (float)factor, (float)ior, thickness > 0.0 ? 0u : 1u});
+            // KHR_materials_volume.attenuationColor / attenuationDistance (SPEC §28, §14(8)): stored whatever the factor and the thickness say; they act only on
+            // a solid transmissive material.  A file that states neither touches nothing
+            const Json *vol = ext->find("KHR_materials_volume");
+            const Json *jc = vol ? vol->find("attenuationColor") : nullptr, *jd = vol ? vol->find("attenuationDistance") : nullptr;
+            if (jc || jd) {
+                Tint t{(uint32_t)tmp.materials.size() - 1u, {1.f, 1.f, 1.f}, INFINITY};
+                if (jc) {
+                    if (!jc->is_arr() || jc->size() != 3) bad("attenuationColor is not three numbers");
+                    for (size_t c = 0; c < 3; ++c) {
+                        const Json &n = (*jc)[c];
+                        if (!n.is_num() || !std::isfinite(n.num) || n.num < 0.0 || n.num > 1.0) bad("attenuationColor outside [0, 1]");
+                        t.color[c] = (float)n.num;
+                    }
+                }
+                if (jd) {
+                    if (!jd->is_num() || !std::isfinite(jd->num) || !(jd->num > 0.0) || !std::isfinite((float)jd->num) || !((float)jd->num > 0.f)) bad("attenuationDistance is not a finite positive number");
+                    t.distance = (float)jd->num;
+                }
+                tints.push_back(t);
+            }
         }
         // emissiveFactor / emissiveTexture / KHR_materials_emissive_strength (SPEC §22, §14(9)): a non-zero product sets the side table once the images are
         // decoded (below).  What is stated is checked whatever the product; a file that states none of the three touches nothing
@@ -428,6 +450,8 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size, uint32_t flags) {
     }
     for (const Glass &g : glasses)
         if (lpt_scene_set_material_transmission(&tmp, g.material, g.factor, g.ior, g.thin) != LPT_OK) bad(std::string("KHR_materials_transmission rejected: ") + lpt_last_error());
+    for (const Tint &t : tints)
+        if (lpt_scene_set_material_attenuation(&tmp, t.material, t.color, t.distance) != LPT_OK) bad(std::string("KHR_materials_volume attenuation rejected: ") + lpt_last_error());
     for (const Emitter &e : emitters)
         if (lpt_scene_set_material_emission(&tmp, e.material, e.factor, e.strength, e.image) != LPT_OK) bad(std::string("emissive material rejected: ") + lpt_last_error());
     for (const Bump &b : bumps)

@@ -100,6 +100,8 @@ struct DScene {
     const float4 *alpha_recs;
     uint32_t n_alpha;
     // SPEC §21: transmissive materials.  trans_tri[prim] = 0 for an opaque triangle, else 1 + the index of its record {transmission, ior, thin (1 / 0), 0}.
+    // SPEC §28: the record's fourth float is 1 iff the material is solid and attenuates; then, and only while some record of the scene does, its row
+    // {sigma_r, sigma_g, sigma_b, 0} stands at trans_recs[n_trans + index] (volume_attenuate).
     // Null / 0 for a scene without a transmissive material in use; read only by the TRANS instantiations of shade_hit / k_shade
     const uint32_t *trans_tri;
     const float4 *trans_recs;
@@ -1816,6 +1818,35 @@ __device__ __forceinline__ InterfaceOut interface_sample(const f3 d, const f3 Ns
     return io;
 }
 
+// ------------------------------------------------------------------ volume attenuation (SPEC §28)
+// A(sigma, t) = exp(-sigma t) as §28 writes it: binary32, no fma, these parentheses.  0 from y >= 125 on (+inf and NaN too), else a normal number
+__device__ __forceinline__ float beer_lambert(const float sigma, const float t) {
+    const float x = sigma * t;
+    const float y = x * 1.44269502f;
+    if (!(y < 125.0f)) return 0.0f;
+    const float k = floorf(y + 0.5f);
+    const float f = y - k;
+    const float g = f * 0.693147182f;
+    float p = (float)(-1.0 / 5040.0);
+    p = (p * g) + (float)(1.0 / 720.0);
+    p = (p * g) + (float)(-1.0 / 120.0);
+    p = (p * g) + (float)(1.0 / 24.0);
+    p = (p * g) + (float)(-1.0 / 6.0);
+    p = (p * g) + 0.5f;
+    p = (p * g) + -1.0f;
+    p = (p * g) + 1.0f;
+    return p * __uint_as_float((uint32_t)(127 - (int)k) << 23);
+}
+// The hit as a whole, before anything at it reads T: a ray that hits the inside of a face (`entering` false) of a solid attenuating triangle — `rec` is its
+// transmission record, `row` the place of its sigma row, read only when the record's fourth float is set — has gone its whole length t inside that solid.
+// Returns whether the rule applied.  shade_hit<TRANS> and k_attenuation (probe_kernels.h) call it.
+__device__ __forceinline__ bool volume_attenuate(const float4 rec, const float4 *row, const bool entering, const float t, f3 &T) {
+    if (entering || rec.w == 0.0f) return false;
+    const float4 sg = *row;
+    T = mk3(T.x * beer_lambert(sg.x, t), T.y * beer_lambert(sg.y, t), T.z * beer_lambert(sg.z, t));
+    return true;
+}
+
 // ------------------------------------------------------------------ SPEC §15 helpers (denoiser path)
 __device__ __forceinline__ uint32_t oct_encode(f3 n) {
     float l1 = (fabsf(n.x) + fabsf(n.y)) + fabsf(n.z);
@@ -1925,7 +1956,7 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DEnv &ev, cons
     out.want_next = false; out.want_shadow = false; out.is_surface = false;
     const uint32_t pxy = __float_as_uint(T4.w);  // x | y << 13 | sample << 26 (k_raygen)
     const f3 d = mk3(d4.x, d4.y, d4.z);
-    const f3 T = mk3(T4.x, T4.y, T4.z);
+    f3 T = mk3(T4.x, T4.y, T4.z);   // (changed only by TRANS: SPEC §28)
     const uint32_t prim = __float_as_uint(h4.w);
     // primary-hit record for the G-buffer (SPEC §15.1); defaults cover miss / emitter / degenerate
     f3 g_n = neg(d), g_alb = mk3(1.0f, 1.0f, 1.0f);
@@ -1972,6 +2003,8 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DEnv &ev, cons
         if (EMIS) em = sc.emis_tri[prim];
         uint32_t nm = 0u;   // NMAP: 0, or 1 + the triangle's normal-map record; as `em`, the word goes out with the record
         if (NMAP) nm = sc.nmap_tri[prim];
+        uint32_t te = 0u;   // TRANS: 0, or 1 + the triangle's transmission record; as `em`, the word goes out with the record
+        if (TRANS) te = sc.trans_tri[prim];
         float bw = (1.0f - hu) - hv;
         const f3 p0 = mk3(P0.x, P0.y, P0.z), p1 = mk3(P1.x, P1.y, P1.z), p2 = mk3(P2.x, P2.y, P2.z);
         f3 P = mk3((p0.x * bw + p1.x * hu) + p2.x * hv, (p0.y * bw + p1.y * hu) + p2.y * hv, (p0.z * bw + p1.z * hu) + p2.z * hv);
@@ -1985,6 +2018,11 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DEnv &ev, cons
             Ns = n2 > 0.0f ? Ns * (1.0f / sqrtf(n2)) : Ng;
             const bool entering = !(dot(Ng, d) > 0.0f);   // (read by TRANS only)
             if (dot(Ng, d) > 0.0f) Ng = neg(Ng);
+            // SPEC §28: behind the rare branch, and before the texture taps and everything at the hit that reads T
+            if (TRANS && te != 0u && !entering) {
+                const DScene &vs = cold().sc;
+                volume_attenuate(vs.trans_recs[te - 1u], vs.trans_recs + (vs.n_trans + (te - 1u)), entering, h4.x, T);
+            }
             const f3 Nv = Ns;   // (read by NMAP only: §12's normal before the flip)
             const bool flip = dot(Ns, Ng) < 0.0f;
             if (flip) Ns = neg(Ns);
@@ -2061,7 +2099,6 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DEnv &ev, cons
             const f3 Po = mk3(P.x + Ng.x * eps, P.y + Ng.y * eps, P.z + Ng.z * eps);
             bool glass = false;   // TRANS: this hit is an interface event (SPEC §21)
             if (TRANS) {
-                const uint32_t te = cs.trans_tri[prim];
                 if (te != 0u) {
                     const float4 tr = cs.trans_recs[te - 1u];   // transmission, ior, thin
                     const float pt = tr.x * (1.0f - clampf(metal, 0.0f, 1.0f));

@@ -13,7 +13,8 @@ namespace lpt {
 
 struct MaterialRec { float x, y, z, w; };   // device.hip uploads these as float4
 static_assert(sizeof(MaterialRec) == 16, "a material record is one float4");
-struct MaterialTable { std::vector<MaterialRec> recs; std::vector<uint32_t> tri; };
+// `more`: a second record per entry of `recs`, parallel to it, for a kind that has one (SPEC §28: the transmission table's sigma rows); empty where no record needs it
+struct MaterialTable { std::vector<MaterialRec> recs; std::vector<uint32_t> tri; std::vector<MaterialRec> more; };
 
 static inline float bits_as_float(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }   // an index rides in a record as its bit pattern
 
@@ -23,6 +24,7 @@ struct MaterialKind {
     int section;   // of SPEC.md
     bool (*state)(const lpt_scene &scene, uint32_t mat, MaterialRec &rec, uint32_t &plain_image);
     const char *names;   // "material %u now <names> was uploaded only as half of a pair"
+    bool (*more)(const lpt_scene &scene, uint32_t mat, MaterialRec &row) = nullptr;   // the second record of a material that has the feature; false: it needs none (a zero row stands in)
 };
 enum { MAT_ALPHA = 0, MAT_TRANS, MAT_EMIS, MAT_NMAP, MAT_KINDS };
 
@@ -34,11 +36,21 @@ static inline bool alpha_state(const lpt_scene &scene, uint32_t mat, MaterialRec
     rec = MaterialRec{a.cutoff, scene.materials[mat].color[3], bits_as_float(plain_image), a.mode == LPT_ALPHA_BLEND ? 1.0f : 0.0f};
     return true;
 }
+// SPEC §28: the sigma row {sigma_r, sigma_g, sigma_b, 0} of a material that is transmissive, solid and has some sigma_c > 0; the record's fourth float says so
+static inline bool trans_sigma(const lpt_scene &scene, uint32_t mat, MaterialRec &row) {
+    const MaterialTransmission t = scene.material_transmission(mat);
+    const MaterialAttenuation a = scene.material_attenuation(mat);
+    row = MaterialRec{0.0f, 0.0f, 0.0f, 0.0f};
+    if (!(t.factor > 0.0f) || t.thin_walled || !a.attenuates()) return false;
+    row = MaterialRec{a.sigma[0], a.sigma[1], a.sigma[2], 0.0f};
+    return true;
+}
 static inline bool trans_state(const lpt_scene &scene, uint32_t mat, MaterialRec &rec, uint32_t &plain_image) {
     const MaterialTransmission t = scene.material_transmission(mat);
     if (!(t.factor > 0.0f)) return false;
     plain_image = LPT_INVALID_INDEX;
-    rec = MaterialRec{t.factor, t.ior, t.thin_walled ? 1.0f : 0.0f, 0.0f};
+    MaterialRec sigma;
+    rec = MaterialRec{t.factor, t.ior, t.thin_walled ? 1.0f : 0.0f, trans_sigma(scene, mat, sigma) ? 1.0f : 0.0f};
     return true;
 }
 static inline bool emis_state(const lpt_scene &scene, uint32_t mat, MaterialRec &rec, uint32_t &plain_image) {
@@ -57,7 +69,7 @@ static inline bool nmap_state(const lpt_scene &scene, uint32_t mat, MaterialRec 
 }
 static const MaterialKind kMaterialKinds[MAT_KINDS] = {
     {20, alpha_state, "masks with an image that"},
-    {21, trans_state, ""},   // names no image
+    {21, trans_state, "", trans_sigma},   // names no image
     {22, emis_state, "emits with an image that"},
     {24, nmap_state, "has a normal map whose image"},
 };
@@ -70,6 +82,7 @@ static inline int derive_material_tables(const lpt_scene &scene, const std::vect
         MaterialTable &t = out[k];
         t = MaterialTable();
         std::vector<uint32_t> rec_of(scene.materials.size(), 0u);   // 1 + record index
+        bool any_more = false;
         for (size_t i = 0; i < scene.instances.size() && i < inst_count.size(); ++i) {
             const uint32_t n = inst_count[i];
             if (!n) continue;
@@ -81,12 +94,18 @@ static inline int derive_material_tables(const lpt_scene &scene, const std::vect
                 if (image != LPT_INVALID_INDEX && !(image < image_resident.size() && image_resident[image]))
                     return fail(LPT_ERR_INVALID_ARG, "material %u now %s was uploaded only as half of an (albedo, mra) pair: upload the scene again", mat, kMaterialKinds[k].names);
                 t.recs.push_back(rec);
+                if (kMaterialKinds[k].more) {
+                    MaterialRec row;
+                    if (kMaterialKinds[k].more(scene, mat, row)) any_more = true;
+                    t.more.push_back(row);
+                }
                 rec_of[mat] = (uint32_t)t.recs.size();
             }
             if (t.tri.empty()) t.tri.assign(std::max(n_tris, 1u), 0u);
             if ((size_t)inst_first[i] + n > t.tri.size()) return fail(LPT_ERR_INVALID_ARG, "instance %zu lies beyond the baked triangles", i);
             std::fill(t.tri.begin() + inst_first[i], t.tri.begin() + inst_first[i] + n, rec_of[mat]);
         }
+        if (!any_more) t.more.clear();
     }
     return LPT_OK;
 }

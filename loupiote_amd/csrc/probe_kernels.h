@@ -232,6 +232,30 @@ __global__ __launch_bounds__(kBlock) void k_glass_shadow(DScene sc, const uint32
     out[i] = row;
 }
 
+// lpt_scene_gpu_attenuation: volume_attenuate, the function shade_hit<TRANS> runs, on T = (1, 1, 1), one (prim, direction, t) per thread.  `entering` comes from the baked
+// triangle exactly as in shade_hit: the raw geometric normal, normalised, against d.  {1, 1, 1, 0} where the rule does not apply; a degenerate triangle is no surface hit
+__global__ __launch_bounds__(kBlock) void k_attenuation(DScene sc, const uint32_t *prims, const float *dirs, const float *ts, uint32_t n, float4 *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    f3 T = mk3(1.0f, 1.0f, 1.0f);
+    bool applies = false;
+    const uint32_t prim = prims[i];
+    const uint32_t te = sc.n_trans != 0u ? sc.trans_tri[prim] : 0u;
+    if (te != 0u) {
+        const float4 *tv = sc.tri_verts + kTriRec * (size_t)prim;
+        const float4 P0 = tv[0], P1 = tv[2], P2 = tv[4];
+        const f3 p0 = mk3(P0.x, P0.y, P0.z), p1 = mk3(P1.x, P1.y, P1.z), p2 = mk3(P2.x, P2.y, P2.z);
+        f3 Ng = cross(p1 - p0, p2 - p0);
+        const float l2 = dot(Ng, Ng);
+        if (l2 > 0.0f) {
+            Ng = Ng * (1.0f / sqrtf(l2));
+            const bool entering = !(dot(Ng, get3(dirs + 3u * (size_t)i)) > 0.0f);
+            applies = volume_attenuate(sc.trans_recs[te - 1u], sc.trans_recs + (sc.n_trans + (te - 1u)), entering, ts[i], T);
+        }
+    }
+    out[i] = make_float4(T.x, T.y, T.z, applies ? 1.0f : 0.0f);
+}
+
 // ------------------------------------------------------------------ scattering (SPEC §10, §21)
 // lpt_interface_sample: interface_sample, the function shade_hit runs, one element per thread
 __global__ __launch_bounds__(kBlock) void k_interface_sample(const InterfaceRowIn *in, uint32_t n, InterfaceRowOut *out) {

@@ -243,6 +243,30 @@ int lpt_scene_get_material_transmission(const lpt_scene *s, uint32_t material_in
     return LPT_OK;
 }
 
+// ---- volume attenuation (SPEC §28): beside the transmission table and independent of it, so factor 0 and back keeps it; sigma is derived here, once
+int lpt_scene_set_material_attenuation(lpt_scene *s, uint32_t material_index, const float color[3], float distance) {
+    if (!s || !color) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_attenuation: null");
+    if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_attenuation: material %u of %zu", material_index, s->materials.size());
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(color[c]) || color[c] < 0.f || color[c] > 1.f) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_attenuation: the colour must lie in [0, 1]");
+    if (!(distance > 0.f)) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_attenuation: the distance must be > 0 (+inf: none)");
+    if (s->attenuation.size() < s->materials.size()) s->attenuation.resize(s->materials.size());
+    MaterialAttenuation &a = s->attenuation[material_index];
+    a.distance = distance;
+    for (int c = 0; c < 3; ++c) { a.color[c] = color[c]; a.sigma[c] = attenuation_sigma(color[c], distance); }
+    return LPT_OK;
+}
+
+int lpt_scene_get_material_attenuation(const lpt_scene *s, uint32_t material_index, float color[3], float *distance, float sigma[3]) {
+    if (!s) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_attenuation: null");
+    if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_attenuation: material %u of %zu", material_index, s->materials.size());
+    const MaterialAttenuation a = s->material_attenuation(material_index);
+    if (color) for (int c = 0; c < 3; ++c) color[c] = a.color[c];
+    if (distance) *distance = a.distance;
+    if (sigma) for (int c = 0; c < 3; ++c) sigma[c] = a.sigma[c];
+    return LPT_OK;
+}
+
 // ---- emissive materials (SPEC §22): a third side table of `materials`, grown on the first write; Le = 0 in all channels drops the record
 int lpt_scene_set_material_emission(lpt_scene *s, uint32_t material_index, const float factor[3], float strength, uint32_t image) {
     if (!s || !factor) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_emission: null");
