@@ -74,6 +74,14 @@ impl Device {
         })?;
         Ok((wi, weight, kind))
     }
+    /// the interface event of a material whose rough bit is set (SPEC.md §29), once per element: rows of {d, Ns, Ngf, entering, base, ior, thin, roughness, r4, u1, u2} ->
+    /// (rows of {wi, weight}, kind: 0 reflected / 1 transmitted / 2 ended, + 4 where the smooth event was taken)
+    pub fn interface_sample_rough(&self, rows: &[[f32; 19]]) -> Result<(Vec<[f32; 6]>, Vec<u32>), Error> {
+        let n = rows.len();
+        let (mut out, mut kind) = (vec![[0f32; 6]; n], vec![0u32; n]);
+        check(unsafe { ffi::lpt_interface_sample_rough(self.h(), n as u32, rows.as_ptr() as *const f32, out.as_mut_ptr() as *mut f32, kind.as_mut_ptr()) })?;
+        Ok((out, kind))
+    }
     /// the shading kernels' BSDF on the GPU (SPEC.md §10), once per element: rows of {base, roughness, metallic, N, Ng, V, L, r3, r4, r5} ->
     /// (rows of {pspec, f, pdf, L_s, weight, pdf_s}, ok: 1 where the sample exists)
     pub fn bsdf_probe(&self, rows: &[[f32; 20]]) -> Result<(Vec<[f32; 12]>, Vec<u32>), Error> {
@@ -144,6 +152,15 @@ impl Scene {
         let (mut factor, mut ior, mut thin) = (0f32, 0f32, 0u32);
         check(unsafe { ffi::lpt_scene_get_material_transmission(self.h, material, &mut factor, &mut ior, &mut thin) })?;
         Ok((factor, ior, thin != 0))
+    }
+    /// SPEC.md §29: rough transmission; one bit beside the transmission state, which `set_material_transmission` leaves alone.  It frosts the interface by the material's roughness
+    pub fn set_material_transmission_rough(&mut self, material: u32, on: bool) -> Result<(), Error> {
+        check(unsafe { ffi::lpt_scene_set_material_transmission_rough(self.h, material, on as u32) })
+    }
+    pub fn material_transmission_rough(&self, material: u32) -> Result<bool, Error> {
+        let mut on = 0u32;
+        check(unsafe { ffi::lpt_scene_get_material_transmission_rough(self.h, material, &mut on) })?;
+        Ok(on != 0)
     }
     /// SPEC.md §28: volume attenuation (glTF attenuationColor / attenuationDistance) of a solid transmissive material; colour (1, 1, 1) or `f32::INFINITY`: none
     pub fn set_material_attenuation(&mut self, material: u32, color: [f32; 3], distance: f32) -> Result<(), Error> {
@@ -216,7 +233,8 @@ pub mod loaders {
     pub fn load_gltf(data: &[u8], scene: &mut Scene) -> Result<(), Error> {
         check(unsafe { ffi::lpt_load_gltf(scene.h, data.as_ptr(), data.len()) })
     }
-    /// `flags`: `ffi::LPT_GLTF_READ_BLEND` marks `alphaMode: "BLEND"` materials blended (SPEC.md §26) instead of loading them as opaque; 0 is `load_gltf`
+    /// `flags`: `ffi::LPT_GLTF_READ_BLEND` marks `alphaMode: "BLEND"` materials blended (SPEC.md §26) instead of loading them as opaque;
+    /// `ffi::LPT_GLTF_READ_ROUGH_TRANSMISSION` marks transmissive materials rough (SPEC.md §29); 0 is `load_gltf`
     pub fn load_gltf_ex(data: &[u8], scene: &mut Scene, flags: u32) -> Result<(), Error> {
         check(unsafe { ffi::lpt_load_gltf_ex(scene.h, data.as_ptr(), data.len(), flags) })
     }

@@ -37,6 +37,8 @@ class Device {  // device.rs:72-141
                           const uint32_t *thin, const float *r4, float *wi, float *weight, uint32_t *kind) const {
         check(lpt_interface_sample(h_, n, dirs, ns, ngf, entering, base, ior, thin, r4, wi, weight, kind));
     }
+    /// SPEC.md §29, the interface event of a material whose rough bit is set, once per element: in[n][19] -> out[n][6], kind[n] (see lpt_interface_sample_rough)
+    void interface_sample_rough(uint32_t n, const float *in, float *out, uint32_t *kind) const { check(lpt_interface_sample_rough(h_, n, in, out, kind)); }
     /// SPEC.md §10, the shading kernels' BSDF on the GPU, once per element: in[n][20] -> out[n][12], ok[n] (see lpt_bsdf_probe)
     void bsdf_probe(uint32_t n, const float *in, float *out, uint32_t *ok) const { check(lpt_bsdf_probe(h_, n, in, out, ok)); }
 
@@ -106,6 +108,13 @@ class Scene {  // scene.rs:30-54
         check(lpt_scene_get_material_transmission(h_, material, &t.factor, &t.ior, &thin));
         t.thin_walled = thin != 0;
         return t;
+    }
+    // SPEC.md §29: rough transmission; one bit beside the transmission state, which set_material_transmission leaves alone.  It frosts the interface by the material's roughness
+    void set_material_transmission_rough(uint32_t material, bool on) { check(lpt_scene_set_material_transmission_rough(h_, material, on ? 1u : 0u)); }
+    bool material_transmission_rough(uint32_t material) const {
+        uint32_t on = 0;
+        check(lpt_scene_get_material_transmission_rough(h_, material, &on));
+        return on != 0;
     }
     // SPEC.md §28: volume attenuation (glTF attenuationColor / attenuationDistance) of a solid transmissive material; colour (1, 1, 1) or distance +inf: none
     struct MaterialAttenuation { float color[3]; float distance; float sigma[3]; };
@@ -178,7 +187,8 @@ inline lpt_punctual_light directional_light(const Vec3 &direction, const Vec3 &c
 namespace loaders {  // loaders/gltf.rs:46-161
 inline void load_gltf(const uint8_t *data, size_t size, Scene &scene) { check(lpt_load_gltf(scene.handle(), data, size)); }
 inline void load_gltf_path(const std::string &path, Scene &scene) { check(lpt_load_gltf_path(scene.handle(), path.c_str())); }
-// flags: LPT_GLTF_READ_BLEND marks alphaMode "BLEND" materials blended (SPEC.md §26) instead of loading them as opaque; 0 is the loaders above
+// flags: LPT_GLTF_READ_BLEND marks alphaMode "BLEND" materials blended (SPEC.md §26) instead of loading them as opaque; LPT_GLTF_READ_ROUGH_TRANSMISSION marks
+// transmissive materials rough, so their roughnessFactor frosts them (SPEC.md §29); 0 is the loaders above
 inline void load_gltf(const uint8_t *data, size_t size, Scene &scene, uint32_t flags) { check(lpt_load_gltf_ex(scene.handle(), data, size, flags)); }
 inline void load_gltf_path(const std::string &path, Scene &scene, uint32_t flags) { check(lpt_load_gltf_path_ex(scene.handle(), path.c_str(), flags)); }
 /// the decoding half of ApplicationContext::load_env (app.rs:138-155): Radiance .hdr bytes -> RGBE8 pixels for ProbeGPU

@@ -293,6 +293,15 @@ int lpt_scene_set_material_alpha_blend(lpt_scene *scene, uint32_t material_index
 int lpt_scene_set_material_transmission(lpt_scene *scene, uint32_t material_index, float factor, float ior, uint32_t thin_walled);
 int lpt_scene_get_material_transmission(const lpt_scene *scene, uint32_t material_index, float *factor, float *ior, uint32_t *thin_walled);
 
+/* build-only extension (SPEC.md §29): rough transmission, frosted glass.  One bit per material, 0 by default, kept beside the transmission
+ * state and independent of it (lpt_scene_set_material_transmission leaves it alone; factor 0 and back keeps it).  It acts only while the
+ * material is transmissive: with `on` = 1 an interface event on the material whose roughness (the material's, times the mra texture's
+ * green at the hit) is at least 0.045 samples a GGX microfacet normal and reflects or refracts about it — a thin-walled pane mirrors the
+ * reflected direction to the far side —; below 0.045 the event is the smooth one of §21, bit for bit.  LPT_ERR_INVALID_ARG, and nothing
+ * changed, for a material index out of range or `on` > 1.  The getter's out-pointer may be NULL. */
+int lpt_scene_set_material_transmission_rough(lpt_scene *scene, uint32_t material_index, uint32_t on);
+int lpt_scene_get_material_transmission_rough(const lpt_scene *scene, uint32_t material_index, uint32_t *on);
+
 /* build-only extension (SPEC.md §28; the reference's loader reads no KHR_materials_volume): volume attenuation, glTF's
  * KHR_materials_volume.attenuationColor and .attenuationDistance.  Kept beside the transmission state and independent of it (factor 0 and
  * back keeps it); default colour (1, 1, 1) and distance +inf, which is none.  It acts only while the material is transmissive and solid
@@ -344,8 +353,12 @@ int lpt_load_gltf_path(lpt_scene *scene, const char *path);
 /* build-only extension (SPEC.md §14 (7), §26): the two loaders with `flags`.  flags = 0 is lpt_load_gltf / lpt_load_gltf_path byte for
  * byte.  LPT_GLTF_READ_BLEND: a material with alphaMode "BLEND" is marked blended (lpt_scene_set_material_alpha_blend) instead of
  * loading as opaque; its alpha image is chosen as a MASK material's is, and its alphaCutoff is validated and ignored.
- * LPT_ERR_INVALID_ARG, and an untouched scene, for an unknown flag bit; every other rejection as lpt_load_gltf. */
+ * LPT_GLTF_READ_ROUGH_TRANSMISSION (SPEC.md §29): every material the file makes transmissive is also marked rough
+ * (lpt_scene_set_material_transmission_rough), so its roughnessFactor (times the metallicRoughnessTexture's green) frosts it — glTF's
+ * default roughnessFactor of 1 is then fully frosted, glTF's own rule; without the flag such glass loads clear, as before.
+ * LPT_ERR_INVALID_ARG, and an untouched scene, for an unknown flag bit (2 is one); every other rejection as lpt_load_gltf. */
 #define LPT_GLTF_READ_BLEND 1u
+#define LPT_GLTF_READ_ROUGH_TRANSMISSION 4u
 int lpt_load_gltf_ex(lpt_scene *scene, const uint8_t *data, size_t size, uint32_t flags);
 int lpt_load_gltf_path_ex(lpt_scene *scene, const char *path, uint32_t flags);
 
@@ -465,6 +478,15 @@ int lpt_scene_gpu_attenuation(lpt_device *dev, const lpt_scene_gpu *sg, uint32_t
  * Outputs: wi[n][3] the next direction, weight[n][3], kind[n] (0 = reflected, 1 = transmitted).  Blocking; host arrays. */
 int lpt_interface_sample(lpt_device *dev, uint32_t n, const float *dirs, const float *ns, const float *ngf, const uint32_t *entering,
                          const float *base, const float *ior, const uint32_t *thin, const float *r4, float *wi, float *weight, uint32_t *kind);
+
+/* build-only extension (SPEC.md §29), for tests and tools in the manner of lpt_bsdf_probe: the interface event of a material whose rough
+ * bit is set, by the shading kernels' own function (kernels.h interface_sample_rough), once per element.  in[n][19] = {d[3] the ray's unit
+ * direction, Ns[3] the shading normal, Ngf[3] the geometric normal flipped against d, entering (non-zero: the geometric normal was not
+ * flipped), base[3], ior, thin (non-zero: thin-walled), roughness (the hit's, before any clamp), r4 (picks reflection against the Fresnel
+ * term), u1 (the azimuth: the kernels pass r5), u2 (the kernels pass r1)}.  out[n][6] = {wi[3] the next direction, weight[3]}; kind[n] =
+ * 0 reflected, 1 transmitted, 2 the path ended (wi and weight are zero), plus 4 where the roughness was below 0.045 and the smooth event
+ * of §21 was taken (then wi, weight and the low bits are lpt_interface_sample's).  Blocking; host arrays. */
+int lpt_interface_sample_rough(lpt_device *dev, uint32_t n, const float *in, float *out, uint32_t *kind);
 
 /* build-only extension (SPEC.md §10), for tests and tools in the manner of lpt_interface_sample: the BSDF of the shading kernels
  * (device_math.h), once per element, set up as a surface hit sets it up: make_surface, NoV = max(dot(N, V), LPT_MIN_NOV),

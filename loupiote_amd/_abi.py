@@ -41,6 +41,7 @@ PUNCTUAL_POINT, PUNCTUAL_SPOT, PUNCTUAL_DIRECTIONAL = 0, 1, 2
 ALPHA_OPAQUE, ALPHA_MASK = 0, 1   # lpt_scene_set_material_alpha's mode (SPEC §20)
 ALPHA_BLEND = 2                   # reported by lpt_scene_get_material_alpha, set by lpt_scene_set_material_alpha_blend (SPEC §26)
 GLTF_READ_BLEND = 1               # lpt_load_gltf_ex's flag: alphaMode BLEND marks the material blended (SPEC §14 (7))
+GLTF_READ_ROUGH_TRANSMISSION = 4  # lpt_load_gltf_ex's flag: a transmissive material is also marked rough (SPEC §14 (8), §29); 2 is no flag
 INSTANCE_DT = np.dtype([("model_to_world", "<f4", 16), ("blas_index", "<u4"), ("material_index", "<u4"),
                         ("pad", "<u4", 2)])
 ENTRY_DT = np.dtype([("vertex_offset", "<u4"), ("vertex_count", "<u4"), ("index_offset", "<u4"),
@@ -104,6 +105,8 @@ SIGNATURES = {
     "lpt_scene_set_material_alpha_blend": (_i, [_vp, _u32, _u32]),
     "lpt_scene_set_material_transmission": (_i, [_vp, _u32, _f, _f, _u32]),
     "lpt_scene_get_material_transmission": (_i, [_vp, _u32, C.POINTER(_f), C.POINTER(_f), _pu32]),
+    "lpt_scene_set_material_transmission_rough": (_i, [_vp, _u32, _u32]),
+    "lpt_scene_get_material_transmission_rough": (_i, [_vp, _u32, _pu32]),
     "lpt_scene_set_material_attenuation": (_i, [_vp, _u32, _vp, _f]),
     "lpt_scene_get_material_attenuation": (_i, [_vp, _u32, _vp, C.POINTER(_f), _vp]),
     "lpt_scene_set_material_emission": (_i, [_vp, _u32, _vp, _f, _u32]),
@@ -140,6 +143,7 @@ SIGNATURES = {
     "lpt_scene_gpu_glass_shadow": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "lpt_scene_gpu_attenuation": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "lpt_interface_sample": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lpt_interface_sample_rough": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "lpt_bsdf_probe": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "lpt_probe_upload": (_i, [_vp, _vp, _u32, _u32, _pvp]),
     "lpt_probe_destroy": (_i, [_vp]),

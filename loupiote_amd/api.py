@@ -79,6 +79,16 @@ class Device:
                                             A.ptr(wi), A.ptr(weight), A.ptr(kind)))
         return wi, weight, kind
 
+    def interface_sample_rough(self, rows):
+        """The interface event of a material whose rough bit is set (SPEC.md §29) by the shading kernels' own function, once per element: rows [n, 19] =
+        {d[3], Ns[3], Ngf[3], entering, base[3], ior, thin, roughness, r4, u1, u2} -> (wi[n, 3], weight[n, 3], kind[n]: 0 reflected, 1 transmitted, 2 the
+        path ended, + 4 where the roughness was below 0.045 and §21's smooth event was taken)."""
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 19)
+        n = rows.shape[0]
+        out, kind = np.zeros((n, 6), np.float32), np.zeros(n, np.uint32)
+        _check(A.lib().lpt_interface_sample_rough(self._h, n, A.ptr(rows), A.ptr(out), A.ptr(kind)))
+        return out[:, 0:3].copy(), out[:, 3:6].copy(), kind
+
     def bsdf_probe(self, rows):
         """The BSDF of the shading kernels (SPEC.md §10) on the GPU, once per element: rows [n, 20] = {base[3], roughness, metallic, N[3], Ng[3],
         V[3], L[3], r3, r4, r5} -> (out[n, 12] = {pspec, f[3], pdf, L_s[3], weight[3], pdf_s}, ok[n])."""
@@ -245,10 +255,19 @@ class Scene:
         return int(mode.value), float(cutoff.value), int(image.value)
 
     # SPEC §21: transmissive materials; a second side table of the materials, opaque (factor 0) by default
-    def set_material_transmission(self, material_index, factor, ior=1.5, thin_walled=True):
+    def set_material_transmission(self, material_index, factor, ior=1.5, thin_walled=True, rough=False):
         """a hit on the material is, with probability factor x (1 - metallic), a smooth dielectric interface of index `ior` (Fresnel reflection or
-        refraction, tinted by the base colour); thin_walled: a pane without thickness, else the boundary of a closed solid.  factor 0: opaque again"""
+        refraction, tinted by the base colour); thin_walled: a pane without thickness, else the boundary of a closed solid.  factor 0: opaque again.
+        rough (SPEC §29): the material's roughness frosts the interface — a GGX microfacet event wherever the hit's roughness is at least 0.045.  The call
+        states the whole state, the rough bit included; the C ABI keeps that bit apart (lpt_scene_set_material_transmission_rough)"""
         _check(A.lib().lpt_scene_set_material_transmission(self._h, int(material_index), float(factor), float(ior), 1 if thin_walled else 0))
+        _check(A.lib().lpt_scene_set_material_transmission_rough(self._h, int(material_index), 1 if rough else 0))
+
+    def material_transmission_rough(self, material_index):
+        """-> whether the material's rough bit is set (SPEC §29); it acts only while the material is transmissive"""
+        on = C.c_uint32()
+        _check(A.lib().lpt_scene_get_material_transmission_rough(self._h, int(material_index), C.byref(on)))
+        return bool(on.value)
 
     def material_transmission(self, material_index):
         """-> (factor, ior, thin_walled)"""
@@ -941,18 +960,21 @@ class loaders:
     """crates/lib/src/loaders/mod.rs"""
 
     @staticmethod
-    def load_gltf(data, scene, blend=False):
-        """blend: alphaMode "BLEND" marks the material blended (SPEC §26) instead of loading as opaque (SPEC §14 (7))"""
+    def load_gltf(data, scene, blend=False, rough_transmission=False):
+        """blend: alphaMode "BLEND" marks the material blended (SPEC §26) instead of loading as opaque (SPEC §14 (7)); rough_transmission: a material the
+        file makes transmissive is also marked rough, so its roughnessFactor frosts it (SPEC §29, §14 (8))"""
         buf = np.frombuffer(bytes(data), np.uint8)
-        if blend:
-            _check(A.lib().lpt_load_gltf_ex(scene._h, A.ptr(buf), buf.size, A.GLTF_READ_BLEND))
+        flags = (A.GLTF_READ_BLEND if blend else 0) | (A.GLTF_READ_ROUGH_TRANSMISSION if rough_transmission else 0)
+        if flags:
+            _check(A.lib().lpt_load_gltf_ex(scene._h, A.ptr(buf), buf.size, flags))
         else:
             _check(A.lib().lpt_load_gltf(scene._h, A.ptr(buf), buf.size))
 
     @staticmethod
-    def load_gltf_path(path, scene, blend=False):
-        if blend:
-            _check(A.lib().lpt_load_gltf_path_ex(scene._h, str(path).encode(), A.GLTF_READ_BLEND))
+    def load_gltf_path(path, scene, blend=False, rough_transmission=False):
+        flags = (A.GLTF_READ_BLEND if blend else 0) | (A.GLTF_READ_ROUGH_TRANSMISSION if rough_transmission else 0)
+        if flags:
+            _check(A.lib().lpt_load_gltf_path_ex(scene._h, str(path).encode(), flags))
         else:
             _check(A.lib().lpt_load_gltf_path(scene._h, str(path).encode()))
 

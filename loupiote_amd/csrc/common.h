@@ -36,6 +36,7 @@ struct MaterialTransmission {
     float factor = 0.0f;
     float ior = 1.5f;
     uint32_t thin_walled = 1u;
+    uint32_t rough_interface = 0u;   // SPEC §29: the interface event is the microfacet one; set and kept apart from the three above (factor 0 and back keeps it)
 };
 
 // SPEC §28: a material's volume attenuation, kept beside its transmission state and independent of it; sigma is derived once, here on the host

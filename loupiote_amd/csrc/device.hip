@@ -1299,6 +1299,22 @@ int lpt_interface_sample(lpt_device *dev, uint32_t n, const float *dirs, const f
     return LPT_OK;
 }
 
+// SPEC §29: interface_sample_rough with the rough bit set, once per element.  in[n] is the row; out[n] = {wi, weight}: the row without its `kind`
+int lpt_interface_sample_rough(lpt_device *dev, uint32_t n, const float *in, float *out, uint32_t *kind) {
+    if (!dev || (n && (!in || !out || !kind))) return fail(LPT_ERR_INVALID_ARG, "lpt_interface_sample_rough: null");
+    std::vector<RoughRowOut> res(n);
+    TRY((run_probe(dev, n, kBlock, {{in, sizeof(RoughRowIn)}}, {{res.data(), sizeof(RoughRowOut)}}, [&](dim3 grid, const DevMem *d) {
+        hipLaunchKernelGGL(k_interface_sample_rough, grid, dim3(kBlock), 0, dev->stream, as<const RoughRowIn>(d[0]), n, as<RoughRowOut>(d[1]));
+    })));
+    for (size_t i = 0; i < n; ++i) {
+        RoughAbiOut o;
+        memcpy(o.wi, res[i].wi, kF3); memcpy(o.weight, res[i].weight, kF3);
+        memcpy(out + 6u * i, &o, sizeof o);
+        kind[i] = res[i].kind;
+    }
+    return LPT_OK;
+}
+
 // SPEC §10: the BSDF as shade_hit sets it up (device_math.h make_surface, spec_probability, bsdf_eval, bsdf_sample), once per element.  in[n] is the row;
 // out[n] = {pspec, f, pdf}, then {L_s, weight, pdf_s}: the row without its `ok`
 int lpt_bsdf_probe(lpt_device *dev, uint32_t n, const float *in, float *out, uint32_t *ok) {

@@ -450,6 +450,10 @@ void load(lpt_scene *scene, const uint8_t *data, size_t size, uint32_t flags) {
     }
     for (const Glass &g : glasses)
         if (lpt_scene_set_material_transmission(&tmp, g.material, g.factor, g.ior, g.thin) != LPT_OK) bad(std::string("KHR_materials_transmission rejected: ") + lpt_last_error());
+    // SPEC §29, §14(8): LPT_GLTF_READ_ROUGH_TRANSMISSION marks every material the file made transmissive, and no other; its roughness is §10's (roughnessFactor x mra green)
+    if (flags & LPT_GLTF_READ_ROUGH_TRANSMISSION)
+        for (const Glass &g : glasses)
+            if (lpt_scene_set_material_transmission_rough(&tmp, g.material, 1u) != LPT_OK) bad(std::string("rough transmission rejected: ") + lpt_last_error());
     for (const Tint &t : tints)
         if (lpt_scene_set_material_attenuation(&tmp, t.material, t.color, t.distance) != LPT_OK) bad(std::string("KHR_materials_volume attenuation rejected: ") + lpt_last_error());
     for (const Emitter &e : emitters)
@@ -466,7 +470,7 @@ extern "C" {
 
 int lpt_load_gltf_ex(lpt_scene *scene, const uint8_t *data, size_t size, uint32_t flags) {
     if (!scene || !data) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf_ex: null");
-    if (flags & ~LPT_GLTF_READ_BLEND) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf_ex: unknown flags 0x%x", flags);
+    if (flags & ~(LPT_GLTF_READ_BLEND | LPT_GLTF_READ_ROUGH_TRANSMISSION)) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf_ex: unknown flags 0x%x", flags);
     try {
         lpt::load(scene, data, size, flags);
     } catch (const lpt::GltfError &e) {
@@ -485,7 +489,7 @@ int lpt_load_gltf(lpt_scene *scene, const uint8_t *data, size_t size) {
 
 int lpt_load_gltf_path_ex(lpt_scene *scene, const char *path, uint32_t flags) {
     if (!scene || !path) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf_path_ex: null");
-    if (flags & ~LPT_GLTF_READ_BLEND) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf_path_ex: unknown flags 0x%x", flags);
+    if (flags & ~(LPT_GLTF_READ_BLEND | LPT_GLTF_READ_ROUGH_TRANSMISSION)) return lpt::fail(LPT_ERR_INVALID_ARG, "lpt_load_gltf_path_ex: unknown flags 0x%x", flags);
     std::ifstream f(path, std::ios::binary);
     if (!f) return lpt::fail(LPT_ERR_FILE_NOT_FOUND, "file not found: %s", path);
     std::vector<uint8_t> bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());

@@ -100,6 +100,7 @@ struct DScene {
     const float4 *alpha_recs;
     uint32_t n_alpha;
     // SPEC §21: transmissive materials.  trans_tri[prim] = 0 for an opaque triangle, else 1 + the index of its record {transmission, ior, thin (1 / 0), 0}.
+    // SPEC §29: the sign bit of `thin` is the material's rough bit (-0 / -1: rough), so `thin != 0` reads what it read.
     // SPEC §28: the record's fourth float is 1 iff the material is solid and attenuates; then, and only while some record of the scene does, its row
     // {sigma_r, sigma_g, sigma_b, 0} stands at trans_recs[n_trans + index] (volume_attenuate).
     // Null / 0 for a scene without a transmissive material in use; read only by the TRANS instantiations of shade_hit / k_shade
@@ -1818,6 +1819,64 @@ __device__ __forceinline__ InterfaceOut interface_sample(const f3 d, const f3 Ns
     return io;
 }
 
+// ------------------------------------------------------------------ rough transmission (SPEC §29)
+// What shade_hit<TRANS> runs at an interface event: §21's smooth event — interface_sample's operations, one for one — unless the material's rough bit is set and the
+// hit's roughness rr = clamp(rough, 0, 1) reaches LPT_MIN_ROUGHNESS; then a GGX normal m is drawn from the normals visible from V = -d (the spherical-cap form, draws
+// u1 and u2) and interface_once reflects or refracts about it: the Fresnel term, the two directions and the pick against r4 are §21's own code with N = m.  A
+// thin-walled pane sends the transmitted ray along the reflected direction mirrored in the plane of N.  The result must lie on its side of BOTH N and Ngf, else the path
+// ends (`ended`; no retry: the retry with Ngf is the smooth event's); the weight is Smith's G1 of the outgoing direction, times `base` when transmitted, and <= 1.
+// Every operation is binary32 with the parentheses of the SPEC.
+struct RoughInterfaceOut { InterfaceOut io; bool ended, smooth; };
+__device__ __forceinline__ RoughInterfaceOut interface_sample_rough(const f3 d, const f3 Ns, const f3 Ngf, const bool entering, const f3 base, const float ior, const bool thin,
+                                                                    const bool rough_bit, const float rough, const float r4, const float u1, const float u2) {
+    RoughInterfaceOut ro;
+    ro.ended = false;
+    // SPEC §29's rr = clampf(rough, 0, 1) tested against LPT_MIN_ROUGHNESS, written as make_surface writes its own clamp: where the event is rough the two are one value
+    // (and a NaN roughness is smooth either way), so shade_hit keeps ONE alpha and a2 for §10 and for this — k_shade<8> and <24> keep their fourth wave by it
+    const float rr = clampf(rough, LPT_MIN_ROUGHNESS, 1.0f);
+    ro.smooth = !rough_bit || !(rough >= LPT_MIN_ROUGHNESS);
+    const float eta = (thin || entering) ? 1.0f / ior : ior;
+    const f3 V = neg(d);
+    const f3 N = dot(V, Ns) > 0.0f ? Ns : Ngf;
+    const float alpha = rr * rr;
+    f3 m = N;
+    if (!ro.smooth) {
+        f3 T, B;
+        onb(N, T, B);
+        const f3 Vh = normalize(mk3(alpha * dot(V, T), alpha * dot(V, B), dot(V, N)));
+        float sn, cs;
+        sincos2pi(u1, sn, cs);
+        const float z = (1.0f - u2) * (1.0f + Vh.z) - Vh.z;
+        const float st = sqrtf(max2(0.0f, 1.0f - z * z));
+        const f3 ml = normalize(mk3(alpha * (st * cs + Vh.x), alpha * (st * sn + Vh.y), max2(0.0f, z + Vh.z)));
+        m = (T * ml.x + B * ml.y) + N * ml.z;
+    }
+    // one call for both events: smooth, it is interface_sample's first; rough, `thin` is held back so that the pick, the reflection and the refraction about m come out of it
+    const bool ok = interface_once(d, m, Ngf, eta, thin && ro.smooth, r4, ro.io.wi, ro.io.transmit);
+    if (ro.smooth) {
+        if (!ok) interface_once(d, Ngf, Ngf, eta, thin, r4, ro.io.wi, ro.io.transmit);
+        ro.io.weight = ro.io.transmit ? base : mk3(1.0f, 1.0f, 1.0f);
+        return ro;
+    }
+    if (ro.io.transmit && thin) {   // the reflected direction about m, mirrored to the far side
+        const float cm = min2(dot(V, m), 1.0f);
+        const f3 wr = normalize(m * (2.0f * cm) + d);
+        ro.io.wi = wr - N * (2.0f * dot(wr, N));
+    }
+    // m faces V up to rounding: a normal that rounding turned away (dot(V, m) <= 0, which needs dot(V, N) at or near 0: N = Ngf seen edge-on) ends the path
+    const float wn = dot(ro.io.wi, N), wg = dot(ro.io.wi, Ngf);
+    const bool valid = dot(V, m) > 0.0f && (ro.io.transmit ? (wn < 0.0f && wg < 0.0f) : (wn > 0.0f && wg > 0.0f));
+    const float a2 = alpha * alpha;
+    const float x = fabsf(wn);
+    const float g1 = (2.0f * x) / (x + sqrtf(a2 + (1.0f - a2) * (x * x)));
+    ro.io.weight = ro.io.transmit ? mk3(base.x * g1, base.y * g1, base.z * g1) : mk3(g1, g1, g1);
+    if (!valid) {
+        ro.ended = true;
+        ro.io.wi = mk3(0.0f, 0.0f, 0.0f); ro.io.weight = mk3(0.0f, 0.0f, 0.0f);
+    }
+    return ro;
+}
+
 // ------------------------------------------------------------------ volume attenuation (SPEC §28)
 // A(sigma, t) = exp(-sigma t) as §28 writes it: binary32, no fma, these parentheses.  0 from y >= 125 on (+inf and NaN too), else a normal number
 __device__ __forceinline__ float beer_lambert(const float sigma, const float t) {
@@ -2105,9 +2164,12 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DEnv &ev, cons
                     if (r3 < pt) {
                         glass = true;
                         if (!last_bounce) {
-                            const InterfaceOut io = interface_sample(d, Ns, Ng, entering, base, tr.y, tr.z != 0.0f, r4);
+                            // SPEC §29: the record's `thin` carries the rough bit in its sign (-0 / -1), so its test against 0 reads as before; u1 = r5, u2 = r1 are drawn
+                            // and unused at an interface event
+                            const RoughInterfaceOut ro = interface_sample_rough(d, Ns, Ng, entering, base, tr.y, tr.z != 0.0f, (__float_as_uint(tr.z) >> 31) != 0u, rough, r4, r5, r1);
+                            const InterfaceOut io = ro.io;
                             const f3 Tn = mk3(T.x * io.weight.x, T.y * io.weight.y, T.z * io.weight.z);
-                            if (Tn.x > 0.0f || Tn.y > 0.0f || Tn.z > 0.0f) {
+                            if (!ro.ended && (Tn.x > 0.0f || Tn.y > 0.0f || Tn.z > 0.0f)) {
                                 const f3 Pn = io.transmit ? mk3(P.x - Ng.x * eps, P.y - Ng.y * eps, P.z - Ng.z * eps) : Po;
                                 out.want_next = true;
                                 out.no4 = make_float4(Pn.x, Pn.y, Pn.z, -1.0f);   // no pdf: what this ray finds is taken with weight 1

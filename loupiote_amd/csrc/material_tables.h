@@ -50,7 +50,10 @@ static inline bool trans_state(const lpt_scene &scene, uint32_t mat, MaterialRec
     if (!(t.factor > 0.0f)) return false;
     plain_image = LPT_INVALID_INDEX;
     MaterialRec sigma;
-    rec = MaterialRec{t.factor, t.ior, t.thin_walled ? 1.0f : 0.0f, trans_sigma(scene, mat, sigma) ? 1.0f : 0.0f};
+    // SPEC §29: the rough bit is the SIGN of `thin` (-0 solid, -1 thin-walled), so a non-rough record keeps its bits and every reader that tests `thin` against
+    // 0 (shade_hit, §27's glass_shadow_eval) reads what it read
+    const float thin = t.thin_walled ? 1.0f : 0.0f;
+    rec = MaterialRec{t.factor, t.ior, t.rough_interface ? -thin : thin, trans_sigma(scene, mat, sigma) ? 1.0f : 0.0f};
     return true;
 }
 static inline bool emis_state(const lpt_scene &scene, uint32_t mat, MaterialRec &rec, uint32_t &plain_image) {

@@ -20,6 +20,11 @@ struct TextureRow { float albedo[3], mra_g, mra_b, emissive[3], normal[3]; uint3
 // lpt_interface_sample
 struct InterfaceRowIn { float d[3], Ns[3], Ngf[3], base[3], ior, r4; uint32_t entering, thin; };
 struct InterfaceRowOut { float wi[3], weight[3]; uint32_t kind; };
+// lpt_interface_sample_rough: the ABI's in[n][19] and out[n][6] as they stand; entering and thin are floats (non-zero: set)
+struct RoughRowIn { float d[3], Ns[3], Ngf[3], entering, base[3], ior, thin, roughness, r4, u1, u2; };
+struct RoughRowOut { float wi[3], weight[3]; uint32_t kind; };
+struct RoughAbiOut { float wi[3], weight[3]; };   // host only: the row without its `kind`
+static_assert(sizeof(RoughRowIn) == 19 * 4 && sizeof(RoughRowOut) == 7 * 4 && sizeof(RoughAbiOut) == 6 * 4, "probe rows: the word counts of the C ABI's callers");
 // lpt_bsdf_probe: the ABI's in[n][20] as it stands; out = what bsdf_eval gives for L, whether bsdf_sample gave a sample, and the sample (zeros without one)
 struct BsdfRowIn { float base[3], roughness, metallic, N[3], Ng[3], V[3], L[3], r3, r4, r5; };
 struct BsdfEval { float pspec, f[3], pdf; };
@@ -265,6 +270,18 @@ __global__ __launch_bounds__(kBlock) void k_interface_sample(const InterfaceRowI
     const InterfaceOut io = interface_sample(get3(e.d), get3(e.Ns), get3(e.Ngf), e.entering != 0u, get3(e.base), e.ior, e.thin != 0u, e.r4);
     InterfaceRowOut row;
     put3(row.wi, io.wi); put3(row.weight, io.weight); row.kind = io.transmit ? 1u : 0u;
+    out[i] = row;
+}
+// lpt_interface_sample_rough: interface_sample_rough with the rough bit set, the function shade_hit<TRANS> runs, one element per thread.
+// kind: 0 reflected, 1 transmitted, 2 the path ended; + 4 where the roughness was below LPT_MIN_ROUGHNESS and the smooth event of §21 was taken
+__global__ __launch_bounds__(kBlock) void k_interface_sample_rough(const RoughRowIn *in, uint32_t n, RoughRowOut *out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const RoughRowIn e = in[i];
+    const RoughInterfaceOut ro = interface_sample_rough(get3(e.d), get3(e.Ns), get3(e.Ngf), e.entering != 0.0f, get3(e.base), e.ior, e.thin != 0.0f, true, e.roughness, e.r4, e.u1, e.u2);
+    RoughRowOut row;
+    put3(row.wi, ro.io.wi); put3(row.weight, ro.io.weight);
+    row.kind = (ro.ended ? 2u : ro.io.transmit ? 1u : 0u) | (ro.smooth ? 4u : 0u);
     out[i] = row;
 }
 // lpt_bsdf_probe: §10 as shade_hit sets it up (make_surface, the clamped NoV, spec_probability), then bsdf_eval on L and bsdf_sample on (r3, r4, r5); one element per thread

@@ -243,6 +243,23 @@ int lpt_scene_get_material_transmission(const lpt_scene *s, uint32_t material_in
     return LPT_OK;
 }
 
+// ---- rough transmission (SPEC §29): one bit beside the transmission state, which lpt_scene_set_material_transmission leaves alone
+int lpt_scene_set_material_transmission_rough(lpt_scene *s, uint32_t material_index, uint32_t on) {
+    if (!s) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_transmission_rough: null");
+    if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_transmission_rough: material %u of %zu", material_index, s->materials.size());
+    if (on > 1u) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_transmission_rough: on must be 0 or 1");
+    if (s->transmission.size() < s->materials.size()) s->transmission.resize(s->materials.size());
+    s->transmission[material_index].rough_interface = on;
+    return LPT_OK;
+}
+
+int lpt_scene_get_material_transmission_rough(const lpt_scene *s, uint32_t material_index, uint32_t *on) {
+    if (!s) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_transmission_rough: null");
+    if (material_index >= s->materials.size()) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_get_material_transmission_rough: material %u of %zu", material_index, s->materials.size());
+    if (on) *on = s->material_transmission(material_index).rough_interface;
+    return LPT_OK;
+}
+
 // ---- volume attenuation (SPEC §28): beside the transmission table and independent of it, so factor 0 and back keeps it; sigma is derived here, once
 int lpt_scene_set_material_attenuation(lpt_scene *s, uint32_t material_index, const float color[3], float distance) {
     if (!s || !color) return fail(LPT_ERR_INVALID_ARG, "lpt_scene_set_material_attenuation: null");
