@@ -22,3 +22,11 @@ constexpr bool path_form_valid(uint32_t form) { return form < kPathForms; }
 // (ENV §5.2a, PUNCT §5.2b, TRANS §5.2d, EMIS §5.2e, ESAMP §5.2f, NMAP §5.2g)
 constexpr int shade_waves(uint32_t form) { return (form & ~kShadeGbuf) ? 3 : 4; }
 constexpr int path_waves(uint32_t form) { return (form & ~kShadeGbuf) ? 3 : 4; }
+
+// Whether the form's k_shade issues a hit's first loads together (kernels.h shade_hit_early).  All but six words do: with GBUF | TRANS | EMIS | ESAMP and
+// ENV or NMAP on top (59, 63, 121, 123, 125, 127) the loop would move one or two more scalars through VGPR lanes than it does, so those keep shade_hit, every load in
+// its branch, and are the kernels they were.  k_path keeps shade_hit in every form (no register to spare, and its LDS is budgeted per wave).
+constexpr bool shade_early(uint32_t form) {
+    constexpr uint32_t full = kShadeGbuf | kShadeTrans | kShadeEmis | kShadeEsamp;
+    return !((form & full) == full && (form & (kShadeEnv | kShadeNmap)));
+}

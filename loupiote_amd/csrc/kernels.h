@@ -229,6 +229,26 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ld_nt(const float4 *p) { const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v *>(p)); return make_float4(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ void st_nt(float4 *p, const float4 v) { const f4v w = {v.x, v.y, v.z, v.w}; __builtin_nontemporal_store(w, reinterpret_cast<f4v *>(p)); }
 
+// A lane's loads that do not depend on one another, issued together and waited for once (shade_hit's issue point).  Each load stands behind its lane's
+// predicate; `row_any` / `word_any` give the lanes it leaves out a register as it is, at no instruction; `landed` is where the wave waits: the optimiser can sink no load
+// past it into the branch that reads it — which is what put one memory round trip behind the other —, and with the value taken as changed it keeps every dword of a row.
+__device__ __forceinline__ f4v row_any() { f4v v; asm volatile("" : "=v"(v)); return v; }
+__device__ __forceinline__ uint32_t word_any() { uint32_t v; asm volatile("" : "=v"(v)); return v; }
+__device__ __forceinline__ f4v ld_row(const float4 *p) { return *reinterpret_cast<const f4v *>(p); }
+__device__ __forceinline__ float4 row4(const f4v v) { return make_float4(v.x, v.y, v.z, v.w); }
+__device__ __forceinline__ void landed(f4v &a, f4v &b, f4v &c, f4v &d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
+__device__ __forceinline__ void landed(uint32_t &a, uint32_t &b, uint32_t &c, f4v &d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
+// four rows of a table in LDS, read HERE: left to itself the optimiser folds the read into the one from memory in the other branch — one load through a pointer
+// picked between the two, a flat load that goes the slow way round to LDS
+__device__ __forceinline__ void lds_rows(const float4 *t, float4 &a, float4 &b, float4 &c, float4 &d) {
+    f4v r0 = ld_row(t), r1 = ld_row(t + 1), r2 = ld_row(t + 2), r3 = ld_row(t + 3);
+    landed(r0, r1, r2, r3);
+    a = row4(r0); b = row4(r1); c = row4(r2); d = row4(r3);
+}
+__device__ __forceinline__ void waited(const float a, const float b, const float c) { asm volatile("" : : "v"(a), "v"(b), "v"(c)); }   // the loads these came from are complete here
+__device__ __forceinline__ void landed(uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
+__device__ __forceinline__ void landed(uint32_t &a) { asm volatile("" : "+v"(a)); }
+
 // pixel slot -> pixel.  Slots enumerate this rank's tiles in ascending tile id (period after period of V tiles, the rank's
 // virtual ranks inside a period; with unit weights: tile ids rank, rank+world, ...) and the pixels inside each tile row-major,
 // (in 8x8 blocks when the tile sides allow, within_to_xy below), so a wave64 covers an 8x8 pixel block.
@@ -336,6 +356,23 @@ __device__ __forceinline__ uint32_t block_compact_binned(bool valid, uint32_t ke
 }
 __device__ __forceinline__ uint32_t dir_octant(float x, float y, float z) { return (x < 0.0f ? 1u : 0u) | (y < 0.0f ? 2u : 0u) | (z < 0.0f ? 4u : 0u); }
 
+// The noise texture's shift of two draws, in two halves: the texel's first two bytes (one aligned 16-bit load: a texel is four bytes), which depend on the pixel
+// alone, and the shift itself.  `nz.enabled` guards both; noise_shift is the two back to back.
+__device__ __forceinline__ uint32_t noise_fetch(const DNoise &nz, uint32_t x, uint32_t y) {
+    return *reinterpret_cast<const uint16_t *>(nz.rgba + 4u * ((size_t)(y % nz.h) * nz.w + (x % nz.w)));
+}
+__device__ __forceinline__ void noise_apply(const uint32_t t01, uint32_t seed_counter, float &r0, float &r1) {
+    float g = (float)(seed_counter & 1023u) * 0.61803398875f;
+    float a = r0 + ((float)(t01 & 0xFFu) + 0.5f) * 0.00390625f + g;
+    float b = r1 + ((float)(t01 >> 8) + 0.5f) * 0.00390625f + g;
+    a = a - floorf(a);
+    b = b - floorf(b);
+    if (a >= 1.0f) a = 0.0f;
+    if (b >= 1.0f) b = 0.0f;
+    r0 = a;
+    r1 = b;
+}
+// the two in one, as every caller but k_shade's issue point runs it (the same operations on the same bytes)
 __device__ __forceinline__ void noise_shift(const DNoise &nz, uint32_t x, uint32_t y, uint32_t seed_counter, float &r0, float &r1) {
     if (!nz.enabled) return;
     const uint8_t *t = nz.rgba + 4u * ((size_t)(y % nz.h) * nz.w + (x % nz.w));
@@ -1621,6 +1658,47 @@ __device__ __forceinline__ f3 rgbe_decode(uchar4 p) {
     return mk3((float)p.x * scale, (float)p.y * scale, (float)p.z * scale);
 }
 
+// env_lookup in two halves: the four RGBE texels under the direction with their bilinear weights (a 1 x 1 probe: its texel alone), and their decoding and blend.
+// shade_hit's issue point fetches a miss's texels with the hit's other first loads and blends them where they have arrived.
+struct EnvTaps { uint32_t p00, p10, p01, p11; float tx, ty; };
+__device__ __forceinline__ uchar4 rgbe_word(const uint32_t w) { return make_uchar4((uint8_t)(w & 0xFFu), (uint8_t)((w >> 8) & 0xFFu), (uint8_t)((w >> 16) & 0xFFu), (uint8_t)(w >> 24)); }
+__device__ __forceinline__ void env_fetch(const DProbe &pr, f3 d, EnvTaps &t) {
+    const int W = (int)pr.w, H = (int)pr.h;
+    const uint32_t *tex = reinterpret_cast<const uint32_t *>(pr.rgbe);
+    t.tx = 0.0f; t.ty = 0.0f;
+    // a 1 x 1 probe skips the direction's arithmetic and reads its one texel four times: the four loads stand in ONE place for either size, so that no value is
+    // copied where the two ways meet — a copy of a loaded word is a wait for it, and this function is called where nothing may wait (shade_hit's issue point)
+    // (so a miss on a 1 x 1 probe makes four requests for one texel where env_lookup makes one: the one place where the issue point asks memory for more than the
+    // branches did; they hit the same line, and a scene with such a probe has no texel traffic to speak of)
+    int x0 = 0, x1 = 0, y0 = 0, y1 = 0;
+    if (!(W == 1 && H == 1)) {
+        float phi = atan2_approx(d.z, d.x);
+        float u = phi * LPT_INV_2PI + 0.5f;
+        float th = acos_approx(clampf(d.y, -1.0f, 1.0f));
+        float v = th * LPT_INV_PI;
+        float fx = u * (float)W - 0.5f, fy = v * (float)H - 0.5f;
+        float x0f = floorf(fx), y0f = floorf(fy);
+        t.tx = fx - x0f; t.ty = fy - y0f;
+        x0 = wrap_i((int)x0f, W); x1 = wrap_next(x0, W);
+        y0 = (int)y0f; y1 = (int)y0f + 1;
+        y0 = y0 < 0 ? 0 : (y0 > H - 1 ? H - 1 : y0);
+        y1 = y1 < 0 ? 0 : (y1 > H - 1 ? H - 1 : y1);
+    }
+    t.p00 = tex[(size_t)y0 * W + x0]; t.p10 = tex[(size_t)y0 * W + x1];
+    t.p01 = tex[(size_t)y1 * W + x0]; t.p11 = tex[(size_t)y1 * W + x1];
+}
+__device__ __forceinline__ f3 env_blend(const DProbe &pr, const EnvTaps &t) {
+    if (pr.w == 1u && pr.h == 1u) return rgbe_decode(rgbe_word(t.p00));
+    const float tx = t.tx, ty = t.ty;
+    const f3 c00 = rgbe_decode(rgbe_word(t.p00)), c10 = rgbe_decode(rgbe_word(t.p10));
+    const f3 c01 = rgbe_decode(rgbe_word(t.p01)), c11 = rgbe_decode(rgbe_word(t.p11));
+    f3 r;
+    { float top = c00.x * (1.0f - tx) + c10.x * tx, bot = c01.x * (1.0f - tx) + c11.x * tx; r.x = top * (1.0f - ty) + bot * ty; }
+    { float top = c00.y * (1.0f - tx) + c10.y * tx, bot = c01.y * (1.0f - tx) + c11.y * tx; r.y = top * (1.0f - ty) + bot * ty; }
+    { float top = c00.z * (1.0f - tx) + c10.z * tx, bot = c01.z * (1.0f - tx) + c11.z * tx; r.z = top * (1.0f - ty) + bot * ty; }
+    return r;
+}
+// the two in one, as every caller but k_shade's issue point runs it: the same operations on the same texels (a 1 x 1 probe reads its texel once here)
 __device__ __forceinline__ f3 env_lookup(const DProbe &pr, f3 d) {
     const int W = (int)pr.w, H = (int)pr.h;
     const uchar4 *tex = reinterpret_cast<const uchar4 *>(pr.rgbe);
@@ -2064,270 +2142,125 @@ __device__ __forceinline__ void shade_hit(const DScene &sc, const DEnv &ev, cons
         if (NMAP) nm = sc.nmap_tri[prim];
         uint32_t te = 0u;   // TRANS: 0, or 1 + the triangle's transmission record; as `em`, the word goes out with the record
         if (TRANS) te = sc.trans_tri[prim];
-        float bw = (1.0f - hu) - hv;
-        const f3 p0 = mk3(P0.x, P0.y, P0.z), p1 = mk3(P1.x, P1.y, P1.z), p2 = mk3(P2.x, P2.y, P2.z);
-        f3 P = mk3((p0.x * bw + p1.x * hu) + p2.x * hv, (p0.y * bw + p1.y * hu) + p2.y * hv, (p0.z * bw + p1.z * hu) + p2.z * hv);
-        f3 Ng = cross(p1 - p0, p2 - p0);
-        float l2 = dot(Ng, Ng);
-        if (l2 > 0.0f) {
-            out.is_surface = true;
-            Ng = Ng * (1.0f / sqrtf(l2));
-            f3 Ns = mk3((N0.x * bw + N1.x * hu) + N2.x * hv, (N0.y * bw + N1.y * hu) + N2.y * hv, (N0.z * bw + N1.z * hu) + N2.z * hv);
-            float n2 = dot(Ns, Ns);
-            Ns = n2 > 0.0f ? Ns * (1.0f / sqrtf(n2)) : Ng;
-            const bool entering = !(dot(Ng, d) > 0.0f);   // (read by TRANS only)
-            if (dot(Ng, d) > 0.0f) Ng = neg(Ng);
-            // SPEC §28: behind the rare branch, and before the texture taps and everything at the hit that reads T
-            if (TRANS && te != 0u && !entering) {
-                const DScene &vs = cold().sc;
-                volume_attenuate(vs.trans_recs[te - 1u], vs.trans_recs + (vs.n_trans + (te - 1u)), entering, h4.x, T);
-            }
-            const f3 Nv = Ns;   // (read by NMAP only: §12's normal before the flip)
-            const bool flip = dot(Ns, Ng) < 0.0f;
-            if (flip) Ns = neg(Ns);
-            float tu = (P0.w * bw + P1.w * hu) + P2.w * hv;
-            float tvv = (N0.w * bw + N1.w * hu) + N2.w * hv;
-            // SPEC §24: behind the divergent branch, and before the material's own taps, so that the edges and the uv deltas are dead by then
-            if (NMAP && nm != 0u) normal_map(cold().sc, s_lut, nm, Nv, Ng, flip, p1 - p0, p2 - p0, P1.w - P0.w, N1.w - N0.w, P2.w - P0.w, N2.w - N0.w, tu, tvv, Ns);
-            f3 base = mk3(mc.x, mc.y, mc.z);
-            float rough = mp.x, metal = mp.y;
-            const uint32_t atex = __float_as_uint(mp.z), mtex = __float_as_uint(mp.w);
-            const DScene &ts = cold().sc;   // the texture tables
-            if ((atex >> 30) == 1u) {   // kPairedBit set, not LPT_INVALID_INDEX: both textures of the material from one set of taps
-                f3 alb;
-                float mg, mb;
-                texture_lookup_pair(ts, s_lut, atex & ~kPairedBit, mtex, tu, tvv, alb, mg, mb);
-                base.x *= alb.x; base.y *= alb.y; base.z *= alb.z;
-                rough *= mg; metal *= mb;
-            } else {
-                if (atex < ts.n_images) {
-                    const float4 tex = texture_lookup(ts, s_lut, atex, tu, tvv, true);
-                    base.x *= tex.x; base.y *= tex.y; base.z *= tex.z;
-                }
-                if (mtex < ts.n_images) {
-                    const float4 tex = texture_lookup(ts, s_lut, mtex, tu, tvv, false);
-                    rough *= tex.y; metal *= tex.z;
-                }
-            }
-            if (EMIS && em != 0u) {   // SPEC §22: weight 1 whatever the ray's pdf, both sides (the flipped Ng plays no part), the last bounce included
-                const DScene &cs = cold().sc;
-                const float4 er = cs.emis_recs[em - 1u];
-                f3 E = mk3(er.x, er.y, er.z);
-                const uint32_t etex = __float_as_uint(er.w);
-                if (etex < sc.n_images) {
-                    const float4 tex = texture_lookup(sc, s_lut, etex, tu, tvv, true);
-                    E.x *= tex.x; E.y *= tex.y; E.z *= tex.z;
-                }
-                if (ESAMP) {   // SPEC §23: the BSDF strategy's weight against the emitter sample that could have found this point; a ray without a pdf keeps weight 1
-                    const float pdf_prev = load_o().w;
-                    if (pdf_prev >= 0.0f) {
-                        const float cl = fabsf(dot(Ng, d));
-                        const float pA = lum(mk3(er.x, er.y, er.z)) * cs.emit_inv_W;
-                        const float p_sel = (ENV ? 0.5f : 1.0f) * ((PUNCT || cs.n_lights) ? 0.5f : 1.0f);
-                        const float pl = (((h4.x * h4.x) / cl) * pA) * p_sel;
-                        const float pb2 = pdf_prev * pdf_prev;
-                        const float w = pb2 / (pb2 + pl * pl);
-                        E = mk3(E.x * w, E.y * w, E.z * w);
-                    }
-                }
-                add_l(T.x * E.x, T.y * E.y, T.z * E.z);
-            }
-            g_n = Ns; g_P = P;
-            g_alb = mk3(clampf(base.x, 0.0f, 1.0f), clampf(base.y, 0.0f, 1.0f), clampf(base.z, 0.0f, 1.0f));
-            const Surface sf = make_surface(base, rough, metal);
-            const f3 V = neg(d);
-            const float NoV = max2(dot(Ns, V), LPT_MIN_NOV);
-            const float pspec = spec_probability(sf, NoV);
-            const uint32_t x = pxy & 0x1FFFu, y = (pxy >> 13) & 0x1FFFu, sample = pxy >> 26;
-            const uint32_t pixel = y * p.width + x;
-            const uint32_t seed_counter = seed_base + sample * p.max_bounces;
-            Rng rg = rng_init(pixel, stage_seed(p.user_seed, seed_counter), LPT_TAG_SHADE);
-            float r0 = rng_next(rg), r1 = rng_next(rg), r2 = rng_next(rg);
-            float r3 = rng_next(rg), r4 = rng_next(rg), r5 = rng_next(rg);
-            const ShadeCold c = cold();   // the noise texture here, the lights and the side tables in next-event estimation below
-            const DScene &cs = c.sc;
-            noise_shift(c.nz, x, y, seed_counter, r4, r5);
-            float r6 = 0.0f, r7 = 0.0f, r8 = 0.0f, r9 = 0.0f;
-            if (ENV) { r6 = rng_next(rg); r7 = rng_next(rg); r8 = rng_next(rg); r9 = rng_next(rg); }
-            float ra = 0.0f, rb = 0.0f;   // ESAMP: the alias pick, behind every draw the other modes make
-            if (ESAMP) { ra = rng_next(rg); rb = rng_next(rg); }
-            const float p_env = (PUNCT || ESAMP || cs.n_lights) ? 0.5f : 1.0f;   // ENV: the probe's share of the light samples
-            const float p_m = (PUNCT || cs.n_lights) ? 0.5f : 1.0f;   // ESAMP: the emitters' share of the non-probe light samples
-            float am = max2(max2(fabsf(P.x), fabsf(P.y)), fabsf(P.z));
-            float eps = 1.0e-4f * (1.0f + am);
-            const f3 Po = mk3(P.x + Ng.x * eps, P.y + Ng.y * eps, P.z + Ng.z * eps);
-            bool glass = false;   // TRANS: this hit is an interface event (SPEC §21)
-            if (TRANS) {
-                if (te != 0u) {
-                    const float4 tr = cs.trans_recs[te - 1u];   // transmission, ior, thin
-                    const float pt = tr.x * (1.0f - clampf(metal, 0.0f, 1.0f));
-                    if (r3 < pt) {
-                        glass = true;
-                        if (!last_bounce) {
-                            // SPEC §29: the record's `thin` carries the rough bit in its sign (-0 / -1), so its test against 0 reads as before; u1 = r5, u2 = r1 are drawn
-                            // and unused at an interface event
-                            const RoughInterfaceOut ro = interface_sample_rough(d, Ns, Ng, entering, base, tr.y, tr.z != 0.0f, (__float_as_uint(tr.z) >> 31) != 0u, rough, r4, r5, r1);
-                            const InterfaceOut io = ro.io;
-                            const f3 Tn = mk3(T.x * io.weight.x, T.y * io.weight.y, T.z * io.weight.z);
-                            if (!ro.ended && (Tn.x > 0.0f || Tn.y > 0.0f || Tn.z > 0.0f)) {
-                                const f3 Pn = io.transmit ? mk3(P.x - Ng.x * eps, P.y - Ng.y * eps, P.z - Ng.z * eps) : Po;
-                                out.want_next = true;
-                                out.no4 = make_float4(Pn.x, Pn.y, Pn.z, -1.0f);   // no pdf: what this ray finds is taken with weight 1
-                                out.nd4 = make_float4(io.wi.x, io.wi.y, io.wi.z, d4.w);
-                                out.nT4 = make_float4(Tn.x, Tn.y, Tn.z, T4.w);
-                            }
-                        }
-                    } else {
-                        r3 = (r3 - pt) / (1.0f - pt);
-                    }
-                }
-            }
-            // next-event estimation
-            if (TRANS && glass) {   // none at an interface
-            } else if (ENV && r0 < p_env) {   // the probe (SPEC §18)
-                f3 wi;
-                float ps;
-                if (env_sample(ev, r6, r7, r8, r9, r1, r2, wi, ps)) {
-                    Hit hl;
-                    hl.t = LPT_T_INF; hl.u = 0.f; hl.v = 0.f; hl.prim = 0xFFFFFFFFu;
-                    intersect_lights(cs, Po, wi, hl);   // a BSDF ray this way would stop at the light's front: not the probe's direction
-                    if (hl.prim == 0xFFFFFFFFu) {
-                        f3 f;
-                        float pb;
-                        bsdf_eval(sf, Ns, Ng, V, NoV, pspec, wi, f, pb);
-                        if (pb > 0.0f) {
-                            const f3 Le = env_lookup(c.probe, wi);
-                            const float pe = p_env * env_pdf(ev, wi);
-                            const float pe2 = pe * pe;
-                            const float wm = last_bounce ? 1.0f : pe2 / (pe2 + pb * pb);   // the last bounce: no BSDF ray carries the other half
-                            const float NoL = dot(Ns, wi);
-                            const float k = (NoL * wm) / (p_env * ps);
-                            f3 contrib = mk3(((T.x * f.x) * Le.x) * k, ((T.y * f.y) * Le.y) * k, ((T.z * f.z) * Le.z) * k);
-                            if (contrib.x > 0.0f || contrib.y > 0.0f || contrib.z > 0.0f) {
-                                out.want_shadow = true;
-                                out.so4 = make_float4(Po.x, Po.y, Po.z, LPT_T_INF);
-                                out.sd4 = make_float4(wi.x, wi.y, wi.z, d4.w);
-                                out.sc4 = make_float4(contrib.x, contrib.y, contrib.z, 0.f);
-                            }
-                        }
-                    }
-                }
-            } else if (ESAMP && light_rl<ENV, false>(r0, p_env, p_m) < p_m) {   // the emissive triangles (SPEC §23)
-                // the last bounce draws none: a sample there would stand for emission one bounce deeper than §22 adds
-                EmitterSample es;
-                if (!last_bounce && emitter_sample(cs, s_lut, ra, rb, r1, r2, Po, es)) {
-                    Hit hl;
-                    hl.t = es.dist; hl.u = 0.f; hl.v = 0.f; hl.prim = 0xFFFFFFFFu;
-                    intersect_lights(cs, Po, es.wi, hl);   // §19's rule: a rectangle light's front on the segment
-                    if (hl.prim == 0xFFFFFFFFu) {
-                        f3 f;
-                        float pb;
-                        bsdf_eval(sf, Ns, Ng, V, NoV, pspec, es.wi, f, pb);
-                        if (pb > 0.0f) {
-                            const float pl = ((es.d2 / es.cl) * es.pA) * ((ENV ? 0.5f : 1.0f) * p_m);
-                            const float pl2 = pl * pl;
-                            const float wm = pl2 / (pl2 + pb * pb);
-                            const float NoL = dot(Ns, es.wi);
-                            f3 contrib = mk3((T.x * f.x) * (((NoL * es.E.x) * wm) / pl), (T.y * f.y) * (((NoL * es.E.y) * wm) / pl), (T.z * f.z) * (((NoL * es.E.z) * wm) / pl));
-                            if (contrib.x > 0.0f || contrib.y > 0.0f || contrib.z > 0.0f) {
-                                out.want_shadow = true;
-                                out.so4 = make_float4(Po.x, Po.y, Po.z, es.dist * 0.999f);
-                                out.sd4 = make_float4(es.wi.x, es.wi.y, es.wi.z, d4.w);
-                                out.sc4 = make_float4(contrib.x, contrib.y, contrib.z, 0.f);
-                            }
-                        }
-                    }
-                }
-            } else if (PUNCT && light_rl<ENV, ESAMP>(r0, p_env, p_m) < pk.p_p) {   // a punctual light (SPEC §19): a delta light, so MIS weight 1 and no draw beyond r0
-                const float rl = light_rl<ENV, ESAMP>(r0, p_env, p_m);
-                uint32_t li = (uint32_t)((rl / pk.p_p) * (float)cs.n_punctual);
-                if (li > cs.n_punctual - 1u) li = cs.n_punctual - 1u;
-                f3 wi, E;
-                float dist;
-                if (punctual_sample(cs, li, Po, wi, dist, E)) {
-                    Hit hl;
-                    hl.t = dist; hl.u = 0.f; hl.v = 0.f; hl.prim = 0xFFFFFFFFu;
-                    intersect_lights(cs, Po, wi, hl);   // a rectangle light's front on the segment: shadow rays test triangles only, and it would stop a BSDF ray too
-                    if (hl.prim == 0xFFFFFFFFu) {
-                        f3 f;
-                        float pb;
-                        bsdf_eval(sf, Ns, Ng, V, NoV, pspec, wi, f, pb);
-                        if (pb > 0.0f) {
-                            const float NoL = dot(Ns, wi);
-                            f3 contrib = mk3((T.x * f.x) * ((NoL * E.x) / pk.p_pick), (T.y * f.y) * ((NoL * E.y) / pk.p_pick), (T.z * f.z) * ((NoL * E.z) / pk.p_pick));
-                            if (contrib.x > 0.0f || contrib.y > 0.0f || contrib.z > 0.0f) {
-                                out.want_shadow = true;
-                                out.so4 = make_float4(Po.x, Po.y, Po.z, dist < LPT_T_INF ? dist * 0.999f : LPT_T_INF);
-                                out.sd4 = make_float4(wi.x, wi.y, wi.z, d4.w);
-                                out.sc4 = make_float4(contrib.x, contrib.y, contrib.z, 1.0f);   // SPEC §27's mark: a delta light's ray may pass thin panes (read by k_trace_glass alone)
-                            }
-                        }
-                    }
-                }
-            } else if (cs.n_lights) {
-                float rl = light_rl<ENV, ESAMP>(r0, p_env, p_m);
-                if (PUNCT) rl = (rl - pk.p_p) / (1.0f - pk.p_p);
-                uint32_t li = (uint32_t)(rl * (float)cs.n_lights);
-                if (li > cs.n_lights - 1u) li = cs.n_lights - 1u;
-                const float4 *Lt = reinterpret_cast<const float4 *>(cs.lights + li);
-                const float4 n4 = Lt[0], t4 = Lt[1], b4 = Lt[2], lo4 = Lt[3];
-                const float Le = lo4.w, hw = t4.w, hh = b4.w;
-                float a = (2.0f * r1 - 1.0f) * hw, bq = (2.0f * r2 - 1.0f) * hh;
-                f3 qp = mk3((lo4.x + t4.x * a) + b4.x * bq, (lo4.y + t4.y * a) + b4.y * bq, (lo4.z + t4.z * a) + b4.z * bq);
-                f3 w = qp - Po;
-                float d2 = dot(w, w);
-                if (Le > 0.0f && d2 > 0.0f) {
-                    float dist = sqrtf(d2);
-                    f3 wi = w * (1.0f / dist);
-                    float cl = -dot(mk3(n4.x, n4.y, n4.z), wi);
-                    if (cl > 0.0f) {
-                        f3 f;
-                        float pb;
-                        bsdf_eval(sf, Ns, Ng, V, NoV, pspec, wi, f, pb);
-                        if (pb > 0.0f) {
-                            float area = 4.0f * (hw * hh);
-                            float pl = (d2 / (cl * area)) * inv_nl;
-                            float pl2 = pl * pl;
-                            float wm = pl2 / (pl2 + pb * pb);
-                            float NoL = dot(Ns, wi);
-                            float k = ((NoL * Le) * wm) / pl;
-                            f3 contrib = mk3((T.x * f.x) * k, (T.y * f.y) * k, (T.z * f.z) * k);
-                            if (contrib.x > 0.0f || contrib.y > 0.0f || contrib.z > 0.0f) {
-                                out.want_shadow = true;
-                                out.so4 = make_float4(Po.x, Po.y, Po.z, dist * 0.999f);
-                                out.sd4 = make_float4(wi.x, wi.y, wi.z, d4.w);
-                                out.sc4 = make_float4(contrib.x, contrib.y, contrib.z, 0.f);
-                            }
-                        }
-                    }
-                }
-            }
-            // BSDF sample -> next ray
-            if (!last_bounce && !(TRANS && glass)) {
-                f3 Ln, wgt;
-                float pdf;
-                if (bsdf_sample(sf, Ns, Ng, V, NoV, pspec, r3, r4, r5, Ln, wgt, pdf)) {
-                    f3 Tn = mk3(T.x * wgt.x, T.y * wgt.y, T.z * wgt.z);
-                    if (Tn.x > 0.0f || Tn.y > 0.0f || Tn.z > 0.0f) {
-                        out.want_next = true;
-                        out.no4 = make_float4(Po.x, Po.y, Po.z, pdf);
-                        out.nd4 = make_float4(Ln.x, Ln.y, Ln.z, d4.w);
-                        out.nT4 = make_float4(Tn.x, Tn.y, Tn.z, T4.w);
-                    }
-                }
+#define LPT_SHADE_EMIS_TABLES sc
+#define LPT_SHADE_ADD_L(r, g, b) add_l(r, g, b)
+#define LPT_SHADE_NOISE(nz, x, y, s, a, b) noise_shift(nz, x, y, s, a, b)
+#define LPT_SHADE_LIGHT_ROWS(cs, li, n4, t4, b4, lo4) const float4 *Lt = reinterpret_cast<const float4 *>(cs.lights + li); const float4 n4 = Lt[0], t4 = Lt[1], b4 = Lt[2], lo4 = Lt[3]
+#include "shade_surface.inc"
+#undef LPT_SHADE_EMIS_TABLES
+#undef LPT_SHADE_ADD_L
+#undef LPT_SHADE_NOISE
+#undef LPT_SHADE_LIGHT_ROWS
+
+// shade_hit with ONE ISSUE POINT for a hit's first loads (k_shade): the same hit, the same arithmetic, the same stores — shade_surface.inc is the body of
+// both.  `load_l()` returns the row the path's radiance is added to (k_shade: the slot's Lsum row) and `add_l(row, r, g, b)` adds to it: a miss and an emitter hit read
+// the row with their other first loads.  `s_lt`: the first kLightTable rectangle lights, four rows each, in LDS.
+template <uint32_t FORM, typename LoadO, typename LoadL, typename AddL, typename Cold>
+__device__ __forceinline__ void shade_hit_early(const DScene &sc, const DEnv &ev, const FrameParams &p, const float *s_lut, const float4 *s_lt,
+                                                const uint32_t bounce, const bool last_bounce, const uint32_t seed_base, const float inv_nl, const PunctPick &pk,
+                                                const float4 d4, const float4 T4, const float4 h4, LoadO load_o, LoadL load_l, AddL add_l, Cold cold, ShadeOut &out) {
+    constexpr bool GBUF = FORM & kShadeGbuf, ENV = FORM & kShadeEnv, PUNCT = FORM & kShadePunct, TRANS = FORM & kShadeTrans, EMIS = FORM & kShadeEmis,
+                   ESAMP = FORM & kShadeEsamp, NMAP = FORM & kShadeNmap;   // kernel_forms.h
+    out.want_next = false; out.want_shadow = false; out.is_surface = false;
+    const uint32_t pxy = __float_as_uint(T4.w);  // x | y << 13 | sample << 26 (k_raygen)
+    const f3 d = mk3(d4.x, d4.y, d4.z);
+    f3 T = mk3(T4.x, T4.y, T4.z);   // (changed only by TRANS: SPEC §28)
+    const uint32_t prim = __float_as_uint(h4.w);
+    // primary-hit record for the G-buffer (SPEC §15.1); defaults cover miss / emitter / degenerate
+    f3 g_n = neg(d), g_alb = mk3(1.0f, 1.0f, 1.0f);
+    f3 g_P = mk3(0.f, 0.f, 0.f);
+    if (GBUF && bounce == 0) {   // (the G-buffer's origin row stays in front of the issue point, for every lane, as it was: once per frame)
+        const float4 o4 = load_o();
+        g_P = mk3(fmaf(d.x, h4.x, o4.x), fmaf(d.y, h4.x, o4.y), fmaf(d.z, h4.x, o4.z));
+    }
+    // THE ISSUE POINT.  What kind of hit this is stands in `prim`, and with the kind the address of everything the hit reads first: a surface hit's shading record (with
+    // its side-table words) and noise texel, a miss's four probe texels, and for a miss or an emitter hit its radiance row and the pdf in its origin row.  Every lane
+    // issues its own under its predicate, all of them before the wave waits ONCE (`landed`); the branches below then read registers.  Taken branch by branch
+    // (shade_hit) the same loads make a chain of round trips: the record in two halves, the noise texel behind the texture taps, and a miss's texels, its row and its
+    // store behind the whole surface branch of the other lanes.  The queue rows are waited for in full before the first guarded load: behind a branch that only some
+    // lanes take, a wait for an older load can only be a wait for everything.
+    f4v rP0 = row_any(), rN0 = row_any(), rP1 = row_any(), rN1 = row_any(), rP2 = row_any(), rN2 = row_any(), rmc = row_any(), rmp = row_any(), rL = row_any();
+    uint32_t em = 0u;   // EMIS: 0, or 1 + the triangle's emission record.  The word depends on `prim` alone, so its load goes out with the record's
+    uint32_t nm = 0u;   // NMAP: 0, or 1 + the triangle's normal-map record; as `em`
+    uint32_t te = 0u;   // TRANS: 0, or 1 + the triangle's transmission record; as `em`
+    uint32_t nz01 = word_any(), pdf_o = word_any();   // the noise texel's two bytes; the bits of the origin row's pdf
+    EnvTaps taps;
+    taps.p00 = word_any(); taps.p10 = word_any(); taps.p01 = word_any(); taps.p11 = word_any(); taps.tx = 0.0f; taps.ty = 0.0f;
+    uint32_t kind = prim;   // what the branches below tell the kinds by: behind the issue point a word of its own, so that no lane mask of the issue point lives on
+    {
+        const bool is_miss = prim == 0xFFFFFFFFu, is_emit = !is_miss && (prim & LPT_LIGHT_BIT) != 0u, is_surf = !is_miss && !is_emit;
+        waited(d4.w, T4.w, h4.w);
+        if (is_surf) {
+            const float4 *tv = sc.tri_verts + kTriRec * (size_t)prim;
+            rP0 = ld_row(tv); rN0 = ld_row(tv + 1); rP1 = ld_row(tv + 2); rN1 = ld_row(tv + 3); rP2 = ld_row(tv + 4); rN2 = ld_row(tv + 5);
+            rmc = ld_row(tv + 6); rmp = ld_row(tv + 7);
+            if (EMIS) em = sc.emis_tri[prim];
+            if (NMAP) nm = sc.nmap_tri[prim];
+            if (TRANS) te = sc.trans_tri[prim];
+        }
+        const ShadeCold c = cold();
+        if (is_surf && c.nz.enabled) nz01 = noise_fetch(c.nz, pxy & 0x1FFFu, (pxy >> 13) & 0x1FFFu);
+        if (is_miss) env_fetch(c.probe, d, taps);
+        if (is_miss || is_emit) rL = load_l();
+        if (is_emit || (ENV && is_miss)) pdf_o = __float_as_uint(load_o().w);
+        landed(rP0, rN0, rP1, rN1); landed(rP2, rN2, rmc, rmp);
+        if (EMIS) landed(em);
+        if (NMAP) landed(nm);
+        if (TRANS) landed(te);
+        landed(nz01, pdf_o, kind, taps.p00); landed(taps.p10, taps.p01, taps.p11, rL);
+    }
+    // a miss and an emitter hit first: they add to their row and are done, and what they read is dead before the surface branch needs its registers
+    if (kind == 0xFFFFFFFFu) {
+        const ShadeCold c = cold();
+        f3 e = env_blend(c.probe, taps);
+        if (ENV) {
+            const float pdf_prev = __uint_as_float(pdf_o);
+            if (pdf_prev >= 0.0f) {   // not a camera ray: the BSDF strategy's MIS weight against the probe's
+                const float pe = ((PUNCT || ESAMP || c.sc.n_lights) ? 0.5f : 1.0f) * env_pdf(ev, d);
+                const float pb2 = pdf_prev * pdf_prev;
+                const float w = pb2 / (pb2 + pe * pe);
+                e = mk3(e.x * w, e.y * w, e.z * w);
             }
         }
-    }
-    if (GBUF && bounce == 0) {
-        const GBufArgs &gb = cold().gb;
-        const uint32_t gx = pxy & 0x1FFFu, gy = (pxy >> 13) & 0x1FFFu;
-        const size_t px = (size_t)gy * p.width + gx;
-        gb.gbuf[px] = make_uint4(prim, __float_as_uint(h4.x), oct_encode(g_n), pack_albedo(g_alb));
-        float mu = 0.0f, mv = 0.0f, cu, cv, pu, pv;
-        if (prim != 0xFFFFFFFFu && project(gb.cur, g_P, cu, cv) && project(gb.prev, g_P, pu, pv)) { mu = pu - cu; mv = pv - cv; }
-        gb.motion[px] = make_float2(mu, mv);
-    }
-}
+        add_l(rL, T.x * e.x, T.y * e.y, T.z * e.z);
+    } else if (kind & LPT_LIGHT_BIT) {
+        // the first kLightTable lights from the kernel's copy in LDS (k_shade stages one, as k_trace does), the others, rare twice over, from memory here
+        const uint32_t eli = prim & ~LPT_LIGHT_BIT;
+        float4 n4, t4, b4, lo4;
+        if (eli < kLightTable) {
+            lds_rows(s_lt + 4u * eli, n4, t4, b4, lo4);
+        } else {
+            const float4 *Lt = reinterpret_cast<const float4 *>(cold().sc.lights + eli);
+            n4 = Lt[0]; t4 = Lt[1]; b4 = Lt[2]; lo4 = Lt[3];
+        }
+        const float Le = lo4.w;
+        g_n = mk3(n4.x, n4.y, n4.z);
+        float w = 1.0f;
+        const float pdf_prev = __uint_as_float(pdf_o);   // emitter hits are rare: the origin record is read only for them (and, ENV, for a miss)
+        if (pdf_prev >= 0.0f) {
+            float cl = -dot(mk3(n4.x, n4.y, n4.z), d);
+            float area = 4.0f * (t4.w * b4.w);
+            float pl = ((h4.x * h4.x) / (cl * area)) * inv_nl;
+            float pb2 = pdf_prev * pdf_prev;
+            w = pb2 / (pb2 + pl * pl);
+        }
+        float k = Le * w;
+        add_l(rL, T.x * k, T.y * k, T.z * k);
+    } else {
+        const float hu = h4.y, hv = h4.z;
+        const float4 P0 = row4(rP0), N0 = row4(rN0), P1 = row4(rP1), N1 = row4(rN1), P2 = row4(rP2), N2 = row4(rN2);
+        const float4 mc = row4(rmc), mp = row4(rmp);
+// `cs`, not `sc`, for the emissive image: kept with the parameter, the image table left k_shade a dead spill slot here (ShadeKernargs).  The noise texel came with the
+// record.  The first kLightTable lights from the table in LDS: no memory round trip behind the draw.
+#define LPT_SHADE_EMIS_TABLES cs
+#define LPT_SHADE_ADD_L(r, g, b) add_l(load_l(), r, g, b)   /* rare: the row is read here, not at the issue point */
+#define LPT_SHADE_NOISE(nz, x, y, s, a, b) do { if (nz.enabled) noise_apply(nz01, s, a, b); } while (0)
+#define LPT_SHADE_LIGHT_ROWS(cs, li, n4, t4, b4, lo4) float4 n4, t4, b4, lo4; if (li < kLightTable) lds_rows(s_lt + 4u * li, n4, t4, b4, lo4); else { const float4 *Lt = reinterpret_cast<const float4 *>(cs.lights + li); n4 = Lt[0]; t4 = Lt[1]; b4 = Lt[2]; lo4 = Lt[3]; }
+#include "shade_surface.inc"
+#undef LPT_SHADE_EMIS_TABLES
+#undef LPT_SHADE_ADD_L
+#undef LPT_SHADE_NOISE
+#undef LPT_SHADE_LIGHT_ROWS
 
 // k_shade's arguments: ONE struct, so that the kernel-argument segment IS this struct (as TraceKernargs for k_trace).  The per-hit loop is deeply divergent — every
 // nesting level holds an exec mask in two SGPRs — and whatever the kernel takes from the parameter stays in SGPRs across the whole loop: with everything taken from there
@@ -2368,7 +2301,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(shade_wa
     // gets is whatever the atomics' order gives, as before; results are keyed by pixel slot.
     __shared__ float4 s_park[6 * kBlock];
     __shared__ uint32_t s_at[2 * kBlock];
+    constexpr bool EARLY = shade_early(FORM);   // kernel_forms.h: the form takes shade_hit_early and its table of lights
+    __shared__ float4 s_lights[EARLY ? 4u * kLightTable : 1u];   // the first rectangle lights, as k_trace stages them: what next-event estimation draws and an emitter hit reads
     s_lut[threadIdx.x] = sc.srgb_lut[threadIdx.x];  // kBlock == 256
+    if (EARLY && threadIdx.x < 4u * min(sc.n_lights, kLightTable)) s_lights[threadIdx.x] = reinterpret_cast<const float4 *>(sc.lights)[threadIdx.x];
     __syncthreads();
     bool parked = false;                   // block-uniform: the previous iteration's rows are waiting in s_park (its per-wave counts in lds[16..19])
     const uint32_t count = QC(a.ctr, bounce);
@@ -2385,15 +2321,27 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(shade_wa
         if (i < count) {
             const float4 d4 = ld_nt(qin_d + i), T4 = ld_nt(qin_T + i), h4 = ld_nt(hits + i);
             const uint32_t slot = __float_as_uint(d4.w);
-            shade_hit<FORM>(sc, a.ev, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, d4, T4, h4,
-                            [&]() { return ld_nt(shade_kernargs()->qin.o + i); },
-                            [&](float r, float g, float b) {
-                                float4 *const Lsum = shade_kernargs()->Lsum;
-                                float4 L = Lsum[slot];
-                                L.x = L.x + r; L.y = L.y + g; L.z = L.z + b;
-                                Lsum[slot] = L;
-                            },
-                            []() { const ShadeKernargs *k = (const ShadeKernargs *)shade_kernargs(); return ShadeCold{k->sc, k->probe, k->nz, k->gb}; }, so);
+            if constexpr (EARLY) {
+                shade_hit_early<FORM>(sc, a.ev, p, s_lut, s_lights, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, d4, T4, h4,
+                                      [&]() __attribute__((always_inline)) { return ld_nt(shade_kernargs()->qin.o + i); },
+                                      [&]() __attribute__((always_inline)) { return ld_row(shade_kernargs()->Lsum + slot); },
+                                      [&](const f4v row, float r, float g, float b) __attribute__((always_inline)) {
+                                          float4 L = row4(row);
+                                          L.x = L.x + r; L.y = L.y + g; L.z = L.z + b;
+                                          shade_kernargs()->Lsum[slot] = L;
+                                      },
+                                      []() { const ShadeKernargs *k = (const ShadeKernargs *)shade_kernargs(); return ShadeCold{k->sc, k->probe, k->nz, k->gb}; }, so);
+            } else {
+                shade_hit<FORM>(sc, a.ev, p, s_lut, (uint32_t)bounce, last_bounce, seed_base, inv_nl, pk, d4, T4, h4,
+                                [&]() { return ld_nt(shade_kernargs()->qin.o + i); },
+                                [&](float r, float g, float b) {
+                                    float4 *const Lsum = shade_kernargs()->Lsum;
+                                    float4 L = Lsum[slot];
+                                    L.x = L.x + r; L.y = L.y + g; L.z = L.z + b;
+                                    Lsum[slot] = L;
+                                },
+                                []() { const ShadeKernargs *k = (const ShadeKernargs *)shade_kernargs(); return ShadeCold{k->sc, k->probe, k->nz, k->gb}; }, so);
+            }
         }
         // `sorted` (wave-uniform; bit 0: next-bounce queue, bit 1: shadow queue): the queue leaves the block ordered by direction octant
         if (!(sorted & 3)) {   // the default: both queues' slots with one atomic (the last bounce emits no next ray: its word gets + 0) per TWO iterations
