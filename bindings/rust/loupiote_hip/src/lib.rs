@@ -307,6 +307,16 @@ impl ProbeGPU {
 #[repr(i32)]
 pub enum BlitMode { Pahtrace = 0, DenoisedPathrace = 1, Temporal = 2, GBuffer = 3, MotionVector = 4 }
 
+/// SPEC.md §30: the tone curve of `Renderer::set_display` (`ffi::LPT_DISPLAY_*`)
+#[derive(Copy, Clone, Debug, PartialEq, Eq)]
+#[repr(u32)]
+pub enum DisplayOperator { Clamp = 0, PbrNeutral = 1, Aces = 2 }
+
+/// what `Renderer::meter` returns (SPEC.md §30.3): the suggested exposure, the luminance histogram (384 bins, 8 per octave from 2^-24), the samples the
+/// exposure rests on behind the trim, and the sampled pixels without a bin (NaN, infinite, below 2^-24, at or above 2^24)
+#[derive(Clone, Debug)]
+pub struct Metering { pub ev: f32, pub histogram: Vec<u32>, pub counted: u32, pub skipped: u32 }
+
 /// reference `crates/lib/src/renderer.rs:169-811`
 pub struct Renderer {
     h: *mut ffi::lpt_renderer,
@@ -413,6 +423,27 @@ impl Renderer {
         let (mut r, mut f) = (0f32, 0f32);
         check(unsafe { ffi::lpt_renderer_get_lens(self.h, &mut r, &mut f) })?;
         Ok((r, f))
+    }
+    /// SPEC.md §30: the display transform of `blit` / `read_pixels` — the mean times 2^`exposure_ev`, then the operator's curve, then sRGB; `(0.0, Clamp)`, the
+    /// default, is every byte as before.  Nothing is rendered or reset, and the float outputs stay linear
+    pub fn set_display(&mut self, exposure_ev: f32, op: DisplayOperator) -> Result<(), Error> { check(unsafe { ffi::lpt_renderer_set_display(self.h, exposure_ev, op as u32) }) }
+    /// (exposure, operator)
+    pub fn display(&self) -> Result<(f32, DisplayOperator), Error> {
+        let (mut ev, mut op) = (0f32, 0u32);
+        check(unsafe { ffi::lpt_renderer_get_display(self.h, &mut ev, &mut op) })?;
+        let op = match op as std::os::raw::c_int {
+            ffi::LPT_DISPLAY_PBR_NEUTRAL => DisplayOperator::PbrNeutral,
+            ffi::LPT_DISPLAY_ACES => DisplayOperator::Aces,
+            _ => DisplayOperator::Clamp,
+        };
+        Ok((ev, op))
+    }
+    /// SPEC.md §30.3: the exposure that puts the mean log2 luminance of the presented frame at 18 % grey, without its darkest `low` and brightest `high`
+    /// fraction, with the 384-bin histogram it comes from.  `counted == 0`: no sample was left and `ev` is 0.  Nothing is set: pass `ev` to `set_display`
+    pub fn meter(&mut self, low: f32, high: f32) -> Result<Metering, Error> {
+        let mut m = Metering { ev: 0.0, histogram: vec![0u32; 384], counted: 0, skipped: 0 };
+        check(unsafe { ffi::lpt_renderer_meter(self.h, low, high, &mut m.ev, m.histogram.as_mut_ptr(), &mut m.counted, &mut m.skipped) })?;
+        Ok(m)
     }
     /// SPEC.md §25, for tests and tools: the primary rays of sample `sample` of the next `raytrace` call, `(origins, dirs)` with 3 floats per pixel of the
     /// full frame (zeros at pixels this rank does not own)

@@ -318,6 +318,11 @@ class Renderer {  // renderer.rs:169-811
     /// SPEC.md §25: a thin-lens camera — lens radius in world units (0, the default: the pinhole) and the distance of the plane in focus; frames change with it, so reset_accumulation() belongs after the call
     void set_lens(float radius, float focus_distance = 1.0f) { check(lpt_renderer_set_lens(h_, radius, focus_distance)); }
     std::pair<float, float> lens() const { float r = 0.f, f = 0.f; check(lpt_renderer_get_lens(h_, &r, &f)); return {r, f}; }
+    /// SPEC.md §30: the display transform of blit / read_pixels — the mean times 2^exposure_ev, then LPT_DISPLAY_CLAMP (the default), LPT_DISPLAY_PBR_NEUTRAL or LPT_DISPLAY_ACES, then sRGB; nothing is rendered or reset, the float outputs stay linear
+    void set_display(float exposure_ev = 0.0f, uint32_t op = LPT_DISPLAY_CLAMP) { check(lpt_renderer_set_display(h_, exposure_ev, op)); }
+    std::pair<float, uint32_t> display() const { float ev = 0.f; uint32_t op = 0; check(lpt_renderer_get_display(h_, &ev, &op)); return {ev, op}; }
+    /// SPEC.md §30.3: the exposure that puts the mean log2 luminance of the presented frame at 18 % grey, without its darkest `low` and brightest `high` fraction; `hist384` (384 words) may be null.  Nothing is set: pass the result to set_display
+    float meter(float low = 0.5f, float high = 0.02f, uint32_t *hist384 = nullptr, uint32_t *counted = nullptr, uint32_t *skipped = nullptr) { float ev = 0.f; check(lpt_renderer_meter(h_, low, high, &ev, hist384, counted, skipped)); return ev; }
     /// SPEC.md §25, for tests and tools: the primary rays of sample `sample` of the next raytrace(), 3 floats per pixel of the full frame each (zeros at pixels this rank does not own)
     void primary_rays(const Mat4 &view_transform, uint32_t sample, float *origins, float *dirs) { check(lpt_renderer_primary_rays(h_, view_transform.data(), sample, origins, dirs)); }
     void set_seed(uint32_t s) { check(lpt_renderer_set_seed(h_, s)); }

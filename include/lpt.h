@@ -606,6 +606,33 @@ int lpt_renderer_blit_rgba8(lpt_renderer *r, uint8_t *dst, size_t row_bytes);
 /* replaces: async Renderer::read_pixels -> Result<Vec<u8>,Error> (renderer.rs:727-811).
  * Blocking (the reference's device.poll(Wait), :791); w*h*4 bytes, tight rows. */
 int lpt_renderer_read_pixels(lpt_renderer *r, uint8_t *dst);
+/* new (SPEC.md §30; no reference counterpart): the display transform between the mean radiance and the sRGB bytes of lpt_renderer_blit_rgba8 and
+ * lpt_renderer_read_pixels — per pixel c = max(mean * 2^exposure_ev, 0), then the operator's curve, then the sRGB encoding as it was.  LPT_DISPLAY_CLAMP
+ * (the default, with exposure 0: every byte, launch and kernel is what it was) is the identity, LPT_DISPLAY_PBR_NEUTRAL the Khronos PBR Neutral curve of the
+ * glTF sample viewer, LPT_DISPLAY_ACES Hill's fitted ACES curve.  `exposure_ev` is finite with |ev| <= 64; an unknown operator or any other exposure is
+ * LPT_ERR_INVALID_ARG and changes nothing.  The state is read when pixels are presented: the call submits nothing, renders nothing and does not reset the
+ * accumulation, and every float output (lpt_renderer_read_radiance*, lpt_write_hdr's input, the denoiser's buffers, the exchange, the G-buffer and motion
+ * views) stays linear and untouched.  The getter's out-pointers may be NULL. */
+enum { LPT_DISPLAY_CLAMP = 0, LPT_DISPLAY_PBR_NEUTRAL = 1, LPT_DISPLAY_ACES = 2 };
+int lpt_renderer_set_display(lpt_renderer *r, float exposure_ev, uint32_t op);
+int lpt_renderer_get_display(const lpt_renderer *r, float *exposure_ev, uint32_t *op);
+/* new (SPEC.md §30.3): metering.  Submits a recorded frame, builds the luminance histogram of the presented target on the GPU — 384 bins, 8 per octave over
+ * [2^-24, 2^24), of the un-exposed mean's Y = 0.2126 r + 0.7152 g + 0.0722 b, so the answer does not depend on the current exposure — and evaluates it on
+ * the host: the darkest floor(low * N) and the brightest floor(high * N) of the N histogram samples are left out, and *ev = log2(0.18) - (the mean log2
+ * luminance of the rest, taken at the bin centres), the exposure that puts that mean at 18 % grey.  *counted = the samples the mean rests on (0: *ev = 0),
+ * *skipped = the sampled pixels without a bin (NaN, infinite, below 2^-24, at or above 2^24); hist384 (384 words) may be NULL, as may every other
+ * out-pointer.  low and high lie in [0, 1) with low + high < 1, else LPT_ERR_INVALID_ARG.  Nothing is set: the caller passes *ev to
+ * lpt_renderer_set_display if it wants it.  Blocking. */
+int lpt_renderer_meter(lpt_renderer *r, float low, float high, float *ev, uint32_t *hist384, uint32_t *counted, uint32_t *skipped);
+/* the evaluation alone, pure host arithmetic (no GPU): what lpt_renderer_meter does with its histogram.  The 384 counts must sum to less than 2^32
+ * (*counted is 32 bits wide; a frame has fewer pixels), else LPT_ERR_INVALID_ARG with nothing written. */
+int lpt_meter_from_histogram(const uint32_t *hist384, float low, float high, float *ev, uint32_t *counted);
+/* build-only extensions (SPEC.md §30), for tests and tools in the manner of lpt_bsdf_probe.  lpt_display_probe: the display kernel's own body over n
+ * caller-supplied accumulators accum_rgba[n][4] (sum r, g, b and the sample count) -> rgba8[n][4]; exposure and operator as for lpt_renderer_set_display.
+ * lpt_meter_probe: the metering kernel itself over such accumulators -> hist384[384] and *skipped.  n = 0 launches nothing (the meter's outputs are zero).
+ * Blocking; host arrays. */
+int lpt_display_probe(lpt_device *dev, uint32_t n, const float *accum_rgba, float exposure_ev, uint32_t op, uint8_t *rgba8);
+int lpt_meter_probe(lpt_device *dev, uint32_t n, const float *accum_rgba, uint32_t *hist384, uint32_t *skipped);
 /* Parity surface (no reference twin): mean radiance, w*h*4 floats, a = 1 where
  * this process owns the pixel and has accumulated at least one sample.  Blocking.  `dst` may be pageable memory (the
  * HIP runtime stages the copy: 27 GB/s measured) or memory from lpt_host_alloc (one DMA at link speed).  When the frame is

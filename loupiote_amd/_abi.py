@@ -42,6 +42,8 @@ ALPHA_OPAQUE, ALPHA_MASK = 0, 1   # lpt_scene_set_material_alpha's mode (SPEC §
 ALPHA_BLEND = 2                   # reported by lpt_scene_get_material_alpha, set by lpt_scene_set_material_alpha_blend (SPEC §26)
 GLTF_READ_BLEND = 1               # lpt_load_gltf_ex's flag: alphaMode BLEND marks the material blended (SPEC §14 (7))
 GLTF_READ_ROUGH_TRANSMISSION = 4  # lpt_load_gltf_ex's flag: a transmissive material is also marked rough (SPEC §14 (8), §29); 2 is no flag
+DISPLAY_OPERATORS = {"clamp": 0, "pbr_neutral": 1, "aces": 2}   # LPT_DISPLAY_* (SPEC §30): lpt_renderer_set_display's operator
+METER_BINS = 384                  # lpt_renderer_meter's histogram: 8 bins per octave over [2^-24, 2^24)
 INSTANCE_DT = np.dtype([("model_to_world", "<f4", 16), ("blas_index", "<u4"), ("material_index", "<u4"),
                         ("pad", "<u4", 2)])
 ENTRY_DT = np.dtype([("vertex_offset", "<u4"), ("vertex_count", "<u4"), ("index_offset", "<u4"),
@@ -184,6 +186,12 @@ SIGNATURES = {
     "lpt_renderer_set_blit_mode": (_i, [_vp, _i]),
     "lpt_renderer_blit_rgba8": (_i, [_vp, _vp, _sz]),
     "lpt_renderer_read_pixels": (_i, [_vp, _vp]),
+    "lpt_renderer_set_display": (_i, [_vp, _f, _u32]),
+    "lpt_renderer_get_display": (_i, [_vp, C.POINTER(_f), _pu32]),
+    "lpt_renderer_meter": (_i, [_vp, _f, _f, C.POINTER(_f), _vp, _pu32, _pu32]),
+    "lpt_meter_from_histogram": (_i, [_vp, _f, _f, C.POINTER(_f), _pu32]),
+    "lpt_display_probe": (_i, [_vp, _u32, _vp, _f, _u32, _vp]),
+    "lpt_meter_probe": (_i, [_vp, _u32, _vp, _vp, _pu32]),
     "lpt_renderer_read_radiance": (_i, [_vp, _vp]),
     "lpt_renderer_read_denoiser": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "lpt_renderer_get_timings": (_i, [_vp, _vp, C.POINTER(_i)]),

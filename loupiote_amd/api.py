@@ -31,6 +31,25 @@ def _check(status):
         raise Error(status, A.lib().lpt_last_error().decode("utf-8", "replace"))
 
 
+def _display_operator(operator):
+    """an LPT_DISPLAY_* value from its name ("clamp", "pbr_neutral", "aces") or the value itself; an unknown value goes to the library, which refuses it"""
+    if isinstance(operator, str):
+        if operator not in A.DISPLAY_OPERATORS:
+            raise Error(A.LPT_ERR_INVALID_ARG, "display operator %r: one of %s" % (operator, ", ".join(A.DISPLAY_OPERATORS)))
+        return A.DISPLAY_OPERATORS[operator]
+    return int(operator)
+
+
+def meter_from_histogram(hist, low=0.5, high=0.02):
+    """SPEC.md §30.3, pure host arithmetic: (ev, counted) of a 384-bin luminance histogram, as `Renderer.meter` evaluates its own"""
+    hist = np.ascontiguousarray(hist, np.uint32)
+    if hist.shape != (A.METER_BINS,):
+        raise ValueError("meter_from_histogram: %d bins" % A.METER_BINS)
+    ev, counted = C.c_float(), C.c_uint32()
+    _check(A.lib().lpt_meter_from_histogram(A.ptr(hist), float(low), float(high), C.byref(ev), C.byref(counted)))
+    return ev.value, counted.value
+
+
 class BlitMode(enum.IntEnum):
     """renderer.rs:160-167 (spelling `Pahtrace` is the reference's)."""
     Pahtrace = 0
@@ -97,6 +116,21 @@ class Device:
         out, ok = np.zeros((n, 12), np.float32), np.zeros(n, np.uint32)
         _check(A.lib().lpt_bsdf_probe(self._h, n, A.ptr(rows), A.ptr(out), A.ptr(ok)))
         return out, ok
+
+    def display_probe(self, accum, exposure_ev=0.0, operator="clamp"):
+        """The display kernel's own body (SPEC.md §30) on the GPU, once per element: accum [n, 4] = {sum r, g, b, sample count} -> rgba8 [n, 4]."""
+        accum = np.ascontiguousarray(accum, np.float32).reshape(-1, 4)
+        n = accum.shape[0]
+        out = np.zeros((n, 4), np.uint8)
+        _check(A.lib().lpt_display_probe(self._h, n, A.ptr(accum), float(exposure_ev), _display_operator(operator), A.ptr(out)))
+        return out
+
+    def meter_probe(self, accum):
+        """The metering kernel itself (SPEC.md §30.3) on the GPU over accum [n, 4] -> (hist[384], skipped)."""
+        accum = np.ascontiguousarray(accum, np.float32).reshape(-1, 4)
+        hist, skipped = np.zeros(A.METER_BINS, np.uint32), C.c_uint32()
+        _check(A.lib().lpt_meter_probe(self._h, accum.shape[0], A.ptr(accum), A.ptr(hist), C.byref(skipped)))
+        return hist, skipped.value
 
     def close(self):
         if self._h:
@@ -679,6 +713,27 @@ class Renderer:
         out = np.zeros((h, w, 4), np.uint8)
         _check(A.lib().lpt_renderer_read_pixels(self._h, A.ptr(out)))
         return out
+
+    def set_display(self, exposure_ev=0.0, operator="clamp"):
+        """SPEC.md §30: the display transform of `blit` and `read_pixels` — the mean times 2^exposure_ev, then "clamp" (the default: with exposure 0 every byte is
+        what it was), "pbr_neutral" (Khronos PBR Neutral) or "aces" (Hill's fitted ACES), then the sRGB encoding.  Read when pixels are presented: nothing is
+        rendered or reset, and the float outputs stay linear"""
+        _check(A.lib().lpt_renderer_set_display(self._h, float(exposure_ev), _display_operator(operator)))
+
+    @property
+    def display(self):
+        """(exposure_ev, operator name)"""
+        ev, op = C.c_float(), C.c_uint32()
+        _check(A.lib().lpt_renderer_get_display(self._h, C.byref(ev), C.byref(op)))
+        return ev.value, {v: k for k, v in A.DISPLAY_OPERATORS.items()}[op.value]
+
+    def meter(self, low=0.5, high=0.02):
+        """SPEC.md §30.3: (ev, hist[384], counted, skipped) — the exposure that puts the mean log2 luminance of the presented frame at 18 % grey, leaving out the
+        darkest `low` and the brightest `high` fraction of its pixels, and the histogram it comes from.  Nothing is set: pass `ev` to `set_display`"""
+        ev, counted, skipped = C.c_float(), C.c_uint32(), C.c_uint32()
+        hist = np.zeros(A.METER_BINS, np.uint32)
+        _check(A.lib().lpt_renderer_meter(self._h, float(low), float(high), C.byref(ev), A.ptr(hist), C.byref(counted), C.byref(skipped)))
+        return ev.value, hist, counted.value, skipped.value
 
     # ---- build-only extensions
     def read_radiance(self, out=None):

@@ -321,6 +321,10 @@ struct lpt_renderer : RendererSync, FrameBuffers, Denoiser {
     float occ_cell = 0.25f;          // its grid cell (scene units); LPT_EXP_OCC_CELL_MILLI
     DevMem default_probe;
     DevBuf<float> srgb_thr;      // 256 floats: the linear value at which sRGB code i starts (k_tonemap, SPEC §13.2)
+    // SPEC §30 (lpt_renderer_set_display): read where pixels are presented as sRGB bytes, by nothing else.  (0, CLAMP), the default: k_tonemap, as before
+    float display_ev = 0.0f, display_gain = 1.0f;   // the gain = (float)exp2((double)ev), rounded once
+    uint32_t display_op = LPT_DISPLAY_CLAMP;
+    DevBuf<uint32_t> meter_hist;   // kMeterWords: k_meter's histogram and its skipped count; allocated by the first lpt_renderer_meter
     DevMem noise;
     uint32_t noise_w = 0, noise_h = 0;
     CamBasis prev_cam{};          // prev_model_to_screen (renderer.rs:201,319,542-546), identity at start
@@ -361,6 +365,30 @@ static int flush_device(lpt_device *dev) {
 }
 // what read_radiance / read_pixels / blit show: the exchanged whole frame after lpt_renderer_exchange, else the local target
 static inline const float4 *presented_target(const lpt_renderer *r) { return (r->presented && r->frame) ? r->frame : r->accum; }
+// SPEC §13.2: the linear value at which sRGB code i starts
+static void srgb_thresholds(float thr[256]) {
+    thr[0] = 0.0f;
+    for (int i = 1; i < 256; ++i) {   // inverse OETF at (i - 0.5) / 255 in binary64, rounded once
+        const double v = ((double)i - 0.5) / 255.0;
+        thr[i] = (float)(v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4));
+    }
+}
+// n accumulators to sRGB bytes, on `s`: the one decision of both sites that present bytes (a recorded frame's piecewise read-back, lpt_renderer_blit_rgba8).  While
+// the display state is its default, (0, CLAMP), this is the k_tonemap launch of SPEC §13.2 as it always was; any other state launches §30's k_display<op>
+static_assert((uint32_t)kDisplayClamp == (uint32_t)LPT_DISPLAY_CLAMP && (uint32_t)kDisplayPbrNeutral == (uint32_t)LPT_DISPLAY_PBR_NEUTRAL &&
+              (uint32_t)kDisplayAces == (uint32_t)LPT_DISPLAY_ACES && (uint32_t)kDisplayOps == 3u,
+              "display_math.h's operators are the header's LPT_DISPLAY_* values");
+// k_display<op> over n accumulators: the one place that turns an operator (checked by display_args) into a kernel, for the renderer and for lpt_display_probe
+static void launch_display(uint32_t op, hipStream_t s, const float4 *src, uchar4 *dst, uint32_t n, const float *thr, float gain) {
+    const dim3 grid(div_up(n, kBlock)), block(kBlock);
+    if (op == kDisplayClamp) hipLaunchKernelGGL(k_display<kDisplayClamp>, grid, block, 0, s, src, dst, n, thr, gain);
+    else if (op == kDisplayPbrNeutral) hipLaunchKernelGGL(k_display<kDisplayPbrNeutral>, grid, block, 0, s, src, dst, n, thr, gain);
+    else hipLaunchKernelGGL(k_display<kDisplayAces>, grid, block, 0, s, src, dst, n, thr, gain);
+}
+static void launch_present(const lpt_renderer *r, hipStream_t s, const float4 *src, uchar4 *dst, uint32_t n) {
+    if (r->display_op == kDisplayClamp && r->display_ev == 0.0f) hipLaunchKernelGGL(k_tonemap, dim3(div_up(n, kBlock)), dim3(kBlock), 0, s, src, dst, n, r->srgb_thr);
+    else launch_display(r->display_op, s, src, dst, n, r->srgb_thr, r->display_gain);
+}
 // The device's error word (a page-locked host word the kernels write when a bounded wait runs out; no shipped kernel has one since k_pool left the library in round 6).  Read behind a
 // blocking call, once the stream has been waited for: the frame that raised it is void.
 static int check_device_error(lpt_renderer *r) {
@@ -376,21 +404,25 @@ static inline size_t stack_bytes(const DScene &sc) { return (size_t)sc.stack_ent
 // input and output is a host array and its bytes per element; `launch(grid, d)` gets the grid of `block`-thread blocks that covers n and the device arrays, the inputs
 // first, each list in its order.  Everything runs on dev->stream and is waited for once at the end, so nothing depends on how the null stream orders against a
 // non-blocking one; the host arrays are the caller's until then.  Argument checks are the entry point's.
-struct ProbeIn { const void *host; size_t stride; };
-struct ProbeOut { void *host; size_t stride; };
+// An array with `whole` set is not per element: it has `whole` bytes whatever n is (a table going up, a histogram coming back), and such an output is zero at the launch.
+struct ProbeIn { const void *host; size_t stride; size_t whole = 0; };
+struct ProbeOut { void *host; size_t stride; size_t whole = 0; };
 template <typename Launch>
 static int run_probe(lpt_device *dev, uint32_t n, uint32_t block, std::initializer_list<ProbeIn> ins, std::initializer_list<ProbeOut> outs, Launch &&launch) {
     if (!n) return LPT_OK;
     HIP_TRY(hipSetDevice(dev->ordinal));
     std::vector<DevMem> d(ins.size() + outs.size());
+    const auto bytes = [n](const auto &b) { return b.whole ? b.whole : b.stride * n; };
     size_t k = 0;
-    for (const ProbeIn &b : ins) TRY(d[k++].alloc(b.stride * n));
-    for (const ProbeOut &b : outs) TRY(d[k++].alloc(b.stride * n));
+    for (const ProbeIn &b : ins) TRY(d[k++].alloc(bytes(b)));
+    for (const ProbeOut &b : outs) TRY(d[k++].alloc(bytes(b)));
     k = 0;
-    for (const ProbeIn &b : ins) HIP_TRY(hipMemcpyAsync(d[k++].get(), b.host, b.stride * n, hipMemcpyHostToDevice, dev->stream));
+    for (const ProbeIn &b : ins) HIP_TRY(hipMemcpyAsync(d[k++].get(), b.host, bytes(b), hipMemcpyHostToDevice, dev->stream));
+    for (const ProbeOut &b : outs) { if (b.whole) HIP_TRY(hipMemsetAsync(d[k].get(), 0, b.whole, dev->stream)); ++k; }
+    k = ins.size();
     launch(dim3(div_up(n, block)), d.data());
     HIP_TRY(hipGetLastError());
-    for (const ProbeOut &b : outs) HIP_TRY(hipMemcpyAsync(b.host, d[k++].get(), b.stride * n, hipMemcpyDeviceToHost, dev->stream));
+    for (const ProbeOut &b : outs) HIP_TRY(hipMemcpyAsync(b.host, d[k++].get(), bytes(b), hipMemcpyDeviceToHost, dev->stream));
     HIP_TRY(hipStreamSynchronize(dev->stream));
     return LPT_OK;
 }
@@ -1592,11 +1624,7 @@ int lpt_renderer_create(lpt_device *dev, uint32_t width, uint32_t height, lpt_re
     HIP_TRY(hipMemset(r->default_probe, 0, 4));  // 1x1 zero texel: black environment (device.rs:13-26)
     TRY(r->srgb_thr.alloc(256));
     float thr[256];
-    thr[0] = 0.0f;
-    for (int i = 1; i < 256; ++i) {   // inverse OETF at (i - 0.5) / 255 in binary64, rounded once
-        const double v = ((double)i - 0.5) / 255.0;
-        thr[i] = (float)(v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4));
-    }
+    srgb_thresholds(thr);
     HIP_TRY(hipMemcpy(r->srgb_thr, thr, sizeof thr, hipMemcpyHostToDevice));
     TRY(alloc_frame_buffers(r.get()));
     dev->renderers.push_back(r.get());
@@ -2251,7 +2279,7 @@ static int wavefront_finish(lpt_renderer *r, const Ticket &tk, const ReadPlan *r
                     HIP_TRY(hipMemcpyAsync(read->radiance + 4u * off, r->scratch + off, sizeof(float4) * cnt, hipMemcpyDeviceToHost, sm));
                 } else {
                     uchar4 *px = reinterpret_cast<uchar4 *>(r->scratch.get()) + off;
-                    hipLaunchKernelGGL(k_tonemap, dim3(div_up((uint32_t)cnt, kBlock)), dim3(kBlock), 0, sm, r->accum + off, px, (uint32_t)cnt, r->srgb_thr);
+                    launch_present(r, sm, r->accum + off, px, (uint32_t)cnt);
                     HIP_TRY(hipMemcpy2DAsync(read->rgba8 + (size_t)row0 * read->row_bytes, read->row_bytes, px, (size_t)r->w * 4, (size_t)r->w * 4, row1 - row0, hipMemcpyDeviceToHost, sm));
                 }
             }
@@ -2570,7 +2598,7 @@ int lpt_renderer_blit_rgba8(lpt_renderer *r, uint8_t *dst, size_t row_bytes) {
             hipLaunchKernelGGL(k_debug_view, dim3(div_up(n, kBlock)), dim3(kBlock), 0, r->stream, r->den_gbuf[r->den_cur], r->den_motion,
                                (uchar4 *)r->scratch.get(), (int)r->w, (int)r->h, r->mode);
         else
-            hipLaunchKernelGGL(k_tonemap, dim3(div_up(n, kBlock)), dim3(kBlock), 0, r->stream, presented_target(r), (uchar4 *)r->scratch.get(), n, r->srgb_thr);
+            launch_present(r, r->stream, presented_target(r), (uchar4 *)r->scratch.get(), n);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy2DAsync(dst, row_bytes, r->scratch, (size_t)r->w * 4, (size_t)r->w * 4, r->h, hipMemcpyDeviceToHost, r->stream);
@@ -2586,6 +2614,90 @@ int lpt_renderer_read_pixels(lpt_renderer *r, uint8_t *dst) {
     const int st = lpt_renderer_blit_rgba8(r, dst, (size_t)r->w * 4);
     r->mode = mode;
     return st;
+}
+
+// ------------------------------------------------------------------ display transform and metering (SPEC §30)
+// what lpt_renderer_set_display and lpt_display_probe accept: a known operator and a finite |ev| <= 64; the gain is rounded once, here
+static bool display_args(float ev, uint32_t op, float *gain) {
+    if (op >= kDisplayOps || !std::isfinite(ev) || !(std::fabs(ev) <= 64.0f)) return false;
+    *gain = (float)std::exp2((double)ev);
+    return true;
+}
+static bool meter_args(float low, float high) {   // a NaN fails every comparison
+    return low >= 0.0f && low < 1.0f && high >= 0.0f && high < 1.0f && (double)low + (double)high < 1.0;
+}
+// k_meter's grid: fixed by the device, whatever the frame's size.  One block per CU measured fastest of 1, 2, 4 and 16 at 1920x1080 (each block ends by
+// adding its non-zero words to the same global words); an A/B build may override it
+#ifndef LPT_EXP_METER_BLOCKS
+#define LPT_EXP_METER_BLOCKS 1u
+#endif
+static inline uint32_t meter_grid(const lpt_device *dev) { return (uint32_t)std::max(1, dev->compute_units) * LPT_EXP_METER_BLOCKS; }
+
+int lpt_renderer_set_display(lpt_renderer *r, float exposure_ev, uint32_t op) {
+    if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_display: null");
+    float gain;
+    if (!display_args(exposure_ev, op, &gain)) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_set_display: the operator must be an LPT_DISPLAY_* value and the exposure finite with |ev| <= 64");
+    r->display_ev = exposure_ev; r->display_gain = gain; r->display_op = op;   // read when pixels are presented: nothing is submitted or reset here
+    return LPT_OK;
+}
+int lpt_renderer_get_display(const lpt_renderer *r, float *exposure_ev, uint32_t *op) {
+    if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_get_display: null");
+    if (exposure_ev) *exposure_ev = r->display_ev;
+    if (op) *op = r->display_op;
+    return LPT_OK;
+}
+
+int lpt_meter_from_histogram(const uint32_t *hist384, float low, float high, float *ev, uint32_t *counted) {
+    if (!hist384) return fail(LPT_ERR_INVALID_ARG, "lpt_meter_from_histogram: null");
+    if (!meter_args(low, high)) return fail(LPT_ERR_INVALID_ARG, "lpt_meter_from_histogram: low and high must lie in [0, 1) with low + high < 1");
+    uint64_t total = 0;
+    for (uint32_t b = 0; b < kMeterBins; ++b) total += hist384[b];
+    if (total > 0xFFFFFFFFull) return fail(LPT_ERR_INVALID_ARG, "lpt_meter_from_histogram: the histogram's counts must sum to less than 2^32 (*counted is 32 bits wide)");
+    meter_evaluate(hist384, low, high, ev, counted);
+    return LPT_OK;
+}
+
+int lpt_renderer_meter(lpt_renderer *r, float low, float high, float *ev, uint32_t *hist384, uint32_t *counted, uint32_t *skipped) {
+    if (!r) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_meter: null");
+    if (!meter_args(low, high)) return fail(LPT_ERR_INVALID_ARG, "lpt_renderer_meter: low and high must lie in [0, 1) with low + high < 1");
+    FLUSH_OR_RETURN(r);
+    if (!r->accum) return fail(LPT_ERR_READBACK, "failed to read pixels from GPU to CPU: no render target");
+    HIP_TRY(hipSetDevice(r->dev->ordinal));
+    if (!r->meter_hist) TRY(r->meter_hist.alloc(kMeterWords));
+    uint32_t words[kMeterWords];
+    HIP_TRY(hipMemsetAsync(r->meter_hist, 0, sizeof words, r->stream));
+    hipLaunchKernelGGL(k_meter, dim3(meter_grid(r->dev)), dim3(kBlock), 0, r->stream, presented_target(r), r->w * r->h, r->meter_hist.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(words, r->meter_hist, sizeof words, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    TRY(check_device_error(r));
+    if (hist384) memcpy(hist384, words, sizeof(uint32_t) * kMeterBins);
+    if (skipped) *skipped = words[kMeterBins];
+    meter_evaluate(words, low, high, ev, counted);
+    return LPT_OK;
+}
+
+// k_display's own body over caller-supplied accumulators
+int lpt_display_probe(lpt_device *dev, uint32_t n, const float *accum_rgba, float exposure_ev, uint32_t op, uint8_t *rgba8) {
+    if (!dev || (n && (!accum_rgba || !rgba8))) return fail(LPT_ERR_INVALID_ARG, "lpt_display_probe: null");
+    float gain;
+    if (!display_args(exposure_ev, op, &gain)) return fail(LPT_ERR_INVALID_ARG, "lpt_display_probe: the operator must be an LPT_DISPLAY_* value and the exposure finite with |ev| <= 64");
+    float thr[256];
+    srgb_thresholds(thr);
+    return run_probe(dev, n, kBlock, {{accum_rgba, sizeof(float4)}, {thr, 0, sizeof thr}}, {{rgba8, sizeof(uchar4)}}, [&](dim3, const DevMem *d) {
+        launch_display(op, dev->stream, as<const float4>(d[0]), as<uchar4>(d[2]), n, as<const float>(d[1]), gain);
+    });
+}
+// k_meter itself over caller-supplied accumulators
+int lpt_meter_probe(lpt_device *dev, uint32_t n, const float *accum_rgba, uint32_t *hist384, uint32_t *skipped) {
+    if (!dev || !hist384 || !skipped || (n && !accum_rgba)) return fail(LPT_ERR_INVALID_ARG, "lpt_meter_probe: null");
+    uint32_t words[kMeterWords] = {};
+    TRY((run_probe(dev, n, kBlock, {{accum_rgba, sizeof(float4)}}, {{words, 0, sizeof words}}, [&](dim3, const DevMem *d) {
+        hipLaunchKernelGGL(k_meter, dim3(meter_grid(dev)), dim3(kBlock), 0, dev->stream, as<const float4>(d[0]), n, as<uint32_t>(d[1]));
+    })));
+    memcpy(hist384, words, sizeof(uint32_t) * kMeterBins);
+    *skipped = words[kMeterBins];
+    return LPT_OK;
 }
 
 int lpt_renderer_read_denoiser(lpt_renderer *r, uint32_t *gbuffer, float *motion, float *radiance, uint32_t *history) {

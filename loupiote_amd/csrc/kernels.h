@@ -13,6 +13,7 @@
 // persistent: a fixed grid of waves pulls 64-ray packets from a device-side head.
 #pragma once
 #include "device_math.h"
+#include "display_math.h"
 #include "kernel_forms.h"
 
 namespace lptd {
@@ -2892,6 +2893,45 @@ __global__ __launch_bounds__(kBlock) void k_tonemap(const float4 *accum, uchar4 
     const float4 a = accum[i];
     const bool ok = a.w > 0.0f;
     out[i] = make_uchar4(encode_srgb8(ok ? a.x / a.w : 0.f, thr), encode_srgb8(ok ? a.y / a.w : 0.f, thr), encode_srgb8(ok ? a.z / a.w : 0.f, thr), 255);
+}
+// SPEC §30: the display transform (display_math.h) between the mean and encode_srgb8, one thread per pixel; `gain` = exp2(exposure_ev), rounded once on the host.
+// The launch sites pick k_tonemap while the state is (0, CLAMP), so this kernel never runs in the default state
+__device__ __forceinline__ rgb3 accum_mean(const float4 a) {
+    rgb3 m;
+    const bool ok = a.w > 0.0f;
+    m.r = ok ? a.x / a.w : 0.f; m.g = ok ? a.y / a.w : 0.f; m.b = ok ? a.z / a.w : 0.f;
+    return m;
+}
+template <uint32_t OP>
+__global__ __launch_bounds__(kBlock) void k_display(const float4 *accum, uchar4 *out, uint32_t n, const float *thr_global, float gain) {
+    __shared__ float thr[256];
+    thr[threadIdx.x] = thr_global[threadIdx.x];  // kBlock == 256
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const rgb3 c = display_transform<OP>(accum_mean(accum[i]), gain);
+    out[i] = make_uchar4(encode_srgb8(c.r, thr), encode_srgb8(c.g, thr), encode_srgb8(c.b, thr), 255);
+}
+// SPEC §30.3: the luminance histogram of n accumulators into out[0 .. kMeterBins) and the pixels that have a sample but no bin into out[kMeterBins]; `out` is
+// zero at the launch.  One histogram per block in LDS, filled by LDS atomics over a grid-stride loop (the grid is sized from the CU count, not from n); behind the
+// barrier a block adds its non-zero words to `out`.  Integer counts: the result does not depend on the order of anything
+constexpr uint32_t kMeterWords = kMeterBins + 1u;
+__global__ __launch_bounds__(kBlock) void k_meter(const float4 *accum, uint32_t n, uint32_t *out) {
+    __shared__ uint32_t hist[kMeterWords];
+    for (uint32_t b = threadIdx.x; b < kMeterWords; b += kBlock) hist[b] = 0u;
+    __syncthreads();
+    for (uint64_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {   // 64 bits: the stride may step past 2^32
+        const float4 a = accum[i];
+        if (!(a.w > 0.0f)) continue;
+        uint32_t bin = kMeterBins;   // skipped
+        meter_bin(meter_luminance(accum_mean(a)), bin);
+        atomicAdd(&hist[bin], 1u);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < kMeterWords; b += kBlock) {
+        const uint32_t c = hist[b];
+        if (c) atomicAdd(&out[b], c);
+    }
 }
 
 // ------------------------------------------------------------------ refit (lpt_scene_gpu_update_instances)
